@@ -9,19 +9,25 @@ libxsmm_gemm_batch with device index arrays).
 
 Output: ONE JSON line (rank 0) with the driver's contract fields plus
   roofline     -- dominant kernel's algorithmic bytes per launch / HIP-event launch time vs 8 TB/s HBM peak
+and, with --full only (each takes runs of its own; a plain run sets up, warms up, times the steps and prints):
+  roofline.stream_probe_gbs -- a plain streaming kernel over the same three arrays
+  headline_variants -- the same workload through index arrays, with the matrix cores off, and as three separate allocations
   cpu_baseline -- the CPU oracle (a port of the reference arithmetic, NOT the product) timed on host cores, N=1 only
   secondary    -- spmdm CSR compute phase (BASELINE config 4 shape), fsspmdm (config 3), CP2K stacks (config 5) and 64^3 batches on this GPU.
+--dump-outputs DIR: after the timed steps, what the timed path left in its output array (C) as DIR/<name>.npy -- the whole array
+or, above the size limit, a fixed seeded sample of whole items. The inputs come from fixed seeds, so two builds run with the same
+arguments can be compared output for output.
 Multi-GPU: one process per GPU (torch.distributed over RCCL); the batch axis shards with no data-path collective
 ("weak" scaling: fixed per-GPU batch). value = work of all ranks / max-over-ranks time.
 
 --config 4 / --config 5 run the two BASELINE configurations that have an exchange step, sharded the same way (readiness
 harness for multi-GPU nodes; at N=1 they are single-GPU runs of the per-GPU shard):
   4: spmdm fp32 M=K=64 N=48, 50 % zeros, 131072 problems per GPU: createSparseSlice + compute chunk by chunk, chunk i's C
-     all-gathered (RCCL all_gather_into_tensor) while chunk i+1 is computed; `collective_ms` = the gathers alone,
-     `compute_ms` = the kernels alone, `ms_per_step` = both, overlapped.
+     all-gathered (RCCL all_gather_into_tensor) while chunk i+1 is computed; `ms_per_step` = both, overlapped; with --full
+     also `collective_ms` = the gathers alone and `compute_ms` = the kernels alone.
   5: CP2K stacks fp64, 27 shapes, 524288 products per GPU in ONE grouped call (libxsmm_amd_gemm_batch_groups). Default
      partition: every rank owns its C blocks (no exchange); --c5-split measures the fallback for stacks cut across
-     ranks: partial C + one fused all-reduce over all C blocks (`collective_ms`).
+     ranks: partial C + one fused all-reduce over all C blocks (`collective_ms`, with --full).
 """
 import argparse
 import ctypes as C
@@ -47,9 +53,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=1048576, help="items per GPU")
     ap.add_argument("--mfma", type=int, default=1, help="1: MFMA kernels where shapes allow, 0: scalar-FMA kernels only")
     ap.add_argument("--mode", default="strided", choices=["strided", "index"])
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip headline_variants (profiling runs: the variants launch the same kernel)")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: config 2: the stream probe, headline_variants, secondary configs and the CPU baseline; configs 4 and 5: compute_ms, collective_ms, hbm_gbs_per_gpu (and config 5's roofline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output array of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip headline_variants and secondary")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip headline_variants (profiling runs: the variants launch the same kernel)")
     ap.add_argument("--cpu-items", type=int, default=131072, help="bounded CPU-baseline sample (items)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5], help="BASELINE configuration (2: the headline)")
     ap.add_argument("--chunks", type=int, default=4, help="config 4: chunks of the per-GPU shard (gather of chunk i overlaps compute of chunk i+1)")
@@ -77,6 +85,27 @@ def time_steps(torch, fn, steps, warmup, dist):
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     return t1 - t0, [e0.elapsed_time(e1) for (e0, e1) in evs]
+
+
+DUMP_BYTES = 60 * 1000 * 1000  # all .npy files of a job together stay under 64 MB
+
+
+def dump_outputs(torch, outdir, arrays, rank, world):
+    """--dump-outputs: `arrays` maps a name to (flat device tensor, elements per item). Each is written as DIR/<name>.npy (more
+    than one rank: <name>_rank<r>.npy), shape (items, elements per item), each item in its storage order (column-major). An
+    array above its share of DUMP_BYTES is cut to a sample of whole items drawn with a fixed seed, kept in ascending order."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_BYTES // (world * len(arrays))
+    for name, (t, per_item) in arrays.items():
+        items = t.numel() // per_item
+        t = t[:items * per_item].view(items, per_item)
+        keep = max(1, budget // (per_item * t.element_size()))
+        if keep < items:
+            pick = np.sort(np.random.default_rng(0).choice(items, keep, replace=False))
+            t = t[torch.from_numpy(pick).to(t.device)]
+        fname = (name if world == 1 else "%s_rank%d" % (name, rank)) + ".npy"
+        np.save(os.path.join(outdir, fname), t.cpu().numpy())
 
 
 def launch_ranks(args):
@@ -174,6 +203,8 @@ def main():
 
     wall, per_step = time_steps(torch, step, args.steps, args.warmup, dist)
     kernel_name = xs.last_kernel()
+    if args.dump_outputs:  # (before --full: its variants run on the same C)
+        dump_outputs(torch, args.dump_outputs, {"c": (c, M * N)}, rank, world)
     wall_t = torch.tensor([wall], device="cuda", dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(wall_t, op=dist.ReduceOp.MAX)
@@ -214,16 +245,17 @@ def main():
             pass
         # a plain streaming kernel over the same three arrays (c += a + b: 3 reads : 1 write, no arithmetic) for comparison. NOT a
         # ceiling: the SMM kernel keeps more bytes in flight per CU and can be faster than this probe (round 2: 1.03 x).
-        nbytes = B * M * K * 4
+        if args.full:
+            nbytes = B * M * K * 4
 
-        def probe():
-            assert 0 == L.libxsmm_amd_stream_probe(xs.dptr(a), xs.dptr(b), xs.dptr(c), nbytes)
-        _, pt = time_steps(torch, probe, 5, 2, None)
-        out["roofline"]["stream_probe_gbs"] = round(4.0 * nbytes / (min(pt) * 1e-3) / 1e9, 1)
+            def probe():
+                assert 0 == L.libxsmm_amd_stream_probe(xs.dptr(a), xs.dptr(b), xs.dptr(c), nbytes)
+            _, pt = time_steps(torch, probe, 5, 2, None)
+            out["roofline"]["stream_probe_gbs"] = round(4.0 * nbytes / (min(pt) * 1e-3) / 1e9, 1)
         out["roofline"]["guide_achievable_gbs"] = 6300.0  # /opt/skills/guides/MI355X_MICROARCH.md: ~6.3 TB/s achievable of the 8 TB/s peak
         out["roofline"]["frac_of_guide_achievable"] = round(achieved / 6300.0, 4)
-        out["roofline"]["operands"] = "A, B, C cut from one allocation, B and C 8 / 16 KiB off the spacing of the arrays (see headline_variants for three separate allocations)"
-    if rank == 0 and world == 1 and not args.no_secondary and not args.no_variants and args.mode == "strided":
+        out["roofline"]["operands"] = "A, B, C cut from one allocation, B and C 8 / 16 KiB off the spacing of the arrays (see headline_variants, with --full, for three separate allocations)"
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not args.no_variants and args.mode == "strided":
         # The same workload (a) through the reference's own entry point, libxsmm_gemm_batch with index arrays (src/libxsmm_gemm.c:1878;
         # negative batchsize: no two items share a C), and (b) with A, B, C as three separate allocations -- what
         # samples/smm/specialized.cpp:143-146 does -- where the arrays may land at the same offset modulo the memory interleave.
@@ -267,12 +299,12 @@ def main():
             out["headline_variants"] = variants
         except Exception as exc:  # noqa: BLE001 (must never take the headline down)
             out["headline_variants"] = {"error": repr(exc)[:200]}
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             out["secondary"] = secondary(torch, xs, L)
         except Exception as exc:  # secondary numbers must never take the headline down
             out["secondary"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(M, N, K, args.cpu_items)
     if dist is not None:
         dist.barrier()
@@ -483,25 +515,30 @@ def config4(args, torch, xs, L, dist, rank, world):
         dist_mod.gather_chunks_overlapped(nch, lambda i: None, local_chunk, lambda i: gathered[i], dist)
     wall, per_step = time_steps(torch, step, args.steps, args.warmup, dist)
     wall_max = dist_mod.max_over_ranks(wall, dist, "cuda")
-    _, t_comp = time_steps(torch, compute_only, max(3, args.steps // 2), 1, dist)
-    t_coll = [0.0]
-    if dist is not None:
-        _, t_coll = time_steps(torch, gather_only, max(3, args.steps // 2), 1, dist)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"c": (c, M * N)}, rank, world)
     nnz = float((a != 0).sum().item()) / B
-    by_item = (4.0 * M * K + 6.0 * nnz + 2.0 * (M + 1)) + (6.0 * nnz + 2.0 * (M + 1) + 4.0 * K * N + 4.0 * M * N)  # create + compute
     ms = 1e3 * wall_max / args.steps
-    L.libxsmm_amd_spmdm_batch_destroy(sb)
-    return {
+    out = {
         "metric": "spmdm fp32 64x48x64 nnz50 GFLOP/s (sparse flops, whole job)", "value": round(world * B * 2.0 * nnz * N / (wall_max / args.steps) / 1e9, 1), "unit": "GFLOP/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "configs[3]: spmdm CSR A-sparse fp32 M=K=64 N=48, 50%% zeros, beta=0, %d problems per GPU in %d chunks, createSparseSlice + compute + all-gather of C"
                    % (B, nch), "batch_per_gpu": B, "parallelism": "batch-shard x%d, chunked all_gather_into_tensor overlapped with compute" % world},
-        "compute_ms": round(sum(t_comp) / len(t_comp), 4), "collective_ms": round(sum(t_coll) / len(t_coll), 4),
         "ms_per_step_per_rank": [round(1e3 * w / args.steps, 4) for w in gather_ranks(wall, dist, world)],
-        "hbm_gbs_per_gpu": round(B * by_item / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9, 1),
         "gathered_bytes_per_gpu": (world - 1) * B * M * N * 4 if dist is not None else 0,
     }
+    if args.full:  # the kernels alone and the gathers alone, each in runs of their own
+        _, t_comp = time_steps(torch, compute_only, max(3, args.steps // 2), 1, dist)
+        t_coll = [0.0]
+        if dist is not None:
+            _, t_coll = time_steps(torch, gather_only, max(3, args.steps // 2), 1, dist)
+        by_item = (4.0 * M * K + 6.0 * nnz + 2.0 * (M + 1)) + (6.0 * nnz + 2.0 * (M + 1) + 4.0 * K * N + 4.0 * M * N)  # create + compute
+        out["compute_ms"] = round(sum(t_comp) / len(t_comp), 4)
+        out["collective_ms"] = round(sum(t_coll) / len(t_coll), 4)
+        out["hbm_gbs_per_gpu"] = round(B * by_item / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9, 1)
+    L.libxsmm_amd_spmdm_batch_destroy(sb)
+    return out
 
 
 def config5(args, torch, xs, L, dist, rank, world):
@@ -544,24 +581,30 @@ def config5(args, torch, xs, L, dist, rank, world):
     wall, per_step = time_steps(torch, step, args.steps, args.warmup, dist)
     wall_max = dist_mod.max_over_ranks(wall, dist, "cuda")
     kernel = xs.last_kernel()
-    _, t_comp = time_steps(torch, stacks, max(3, args.steps // 2), 1, dist)
-    t_coll = [0.0]
-    if dist is not None:
-        _, t_coll = time_steps(torch, lambda: dist_mod.reduce_partial_c(call, dist), max(3, args.steps // 2), 1, dist)
+    if args.dump_outputs:  # all C blocks of this rank, one after the other
+        dump_outputs(torch, args.dump_outputs, {"c": (call, 1)}, rank, world)
     ms = 1e3 * wall_max / args.steps
-    return {
+    out = {
         "metric": "CP2K stacks fp64 27 shapes GFLOP/s (whole job)", "value": round(world * flops / (wall_max / args.steps) / 1e9, 1), "unit": "GFLOP/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": "configs[4]: CP2K-style stacks fp64, 27 shapes {13,23,32}^3, %d products per GPU, one grouped call, sums per C block in batch order; %s"
                    % (products, "stacks cut across ranks: partial C + one fused all-reduce" if args.c5_split else "every rank owns its C blocks (no exchange)"),
                    "products_per_gpu": products, "parallelism": "batch-shard x%d%s" % (world, ", all-reduce of %d C elements" % call.numel() if args.c5_split else "")},
-        "kernel": kernel, "compute_ms": round(sum(t_comp) / len(t_comp), 4), "collective_ms": round(sum(t_coll) / len(t_coll), 4),
-        "ms_per_step_per_rank": [round(1e3 * w / args.steps, 4) for w in gather_ranks(wall, dist, world)],
-        "hbm_gbs_per_gpu": round(byt / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9, 1),
-        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(byt / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(byt / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes_per_launch": byt},
+        "kernel": kernel, "ms_per_step_per_rank": [round(1e3 * w / args.steps, 4) for w in gather_ranks(wall, dist, world)],
     }
+    if args.full:  # the grouped call alone and the all-reduce alone, each in runs of their own
+        _, t_comp = time_steps(torch, stacks, max(3, args.steps // 2), 1, dist)
+        t_coll = [0.0]
+        if dist is not None:
+            _, t_coll = time_steps(torch, lambda: dist_mod.reduce_partial_c(call, dist), max(3, args.steps // 2), 1, dist)
+        gbs = byt / (sum(t_comp) / len(t_comp) * 1e-3) / 1e9
+        out["compute_ms"] = round(sum(t_comp) / len(t_comp), 4)
+        out["collective_ms"] = round(sum(t_coll) / len(t_coll), 4)
+        out["hbm_gbs_per_gpu"] = round(gbs, 1)
+        out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes_per_launch": byt}
+    return out
 
 
 def cpu_baseline(M, N, K, items):
