@@ -155,11 +155,14 @@ LIBXSMM_API int libxsmm_amd_csr_kernel_source(int typesize, int M, int K, const 
  *  batch is launched (one wavefront per item, shape baked in). Same buffer/compile/return conventions as
  *  libxsmm_amd_csr_kernel_source (reference counterpart: libxsmm_generator_gemm_kernel's "noarch" C text).
  *  variant: 0 = strided batch of 16-byte aligned items (widest loads); bit 0 = element-wide accesses (index and pointer
- *  batches); bit 1 = consecutive items with one C accumulate in registers (CP2K stacks, batch-reduce). */
+ *  batches); bit 1 = consecutive items with one C accumulate in registers (CP2K stacks, batch-reduce).
+ *  compile == 2: as compile != 0, and `buffer` then holds the text the library actually builds for it -- a text with
+ *  hand-counted waits (XHANDWAIT 1) whose code object has a private segment or spilled VGPRs is built with the compiler's
+ *  waits instead (XHANDWAIT 0). */
 LIBXSMM_API int libxsmm_amd_smm_kernel_source(const libxsmm_gemm_descriptor* descriptor, int variant, char* buffer, size_t buffer_size, int compile);
 
 /** The text a grouped launch (libxsmm_amd_gemm_batch_groups) compiles for index batches of these descriptors: the run forms
- *  of every shape, each in a namespace of its own, behind one dispatching kernel. Conventions as above. */
+ *  of every shape, each in a namespace of its own, behind one dispatching kernel. Conventions as above (compile == 2 included). */
 LIBXSMM_API int libxsmm_amd_smm_grouped_kernel_source(const libxsmm_gemm_descriptor* const descriptors[], int ndescriptors, char* buffer, size_t buffer_size, int compile);
 
 /** Run-time specialisation off the caller's path. A batch call never waits for the compiler (hiprtc: 0.3-0.5 s per kernel,

@@ -332,16 +332,21 @@ def read_mtx(path, is_csr):
     return out
 
 
-def gemm_batch_groups(prec, shapes, a, b, c, stride_a, stride_b, stride_c, sizes, index_base=0, index_stride=4, beta=1.0, relaxed=False):
-    """libxsmm_amd_gemm_batch_groups: shapes = [(m, n, k)], a/b/c/stride_* = per-group tensors / arrays, sizes = per-group batch sizes"""
+def gemm_batch_groups(prec, shapes, a, b, c, stride_a, stride_b, stride_c, sizes, index_base=0, index_stride=4, beta=1.0, relaxed=False,
+                      transa=None, transb=None, lda=None, ldb=None, ldc=None):
+    """libxsmm_amd_gemm_batch_groups: shapes = [(m, n, k)], a/b/c/stride_* = per-group tensors / arrays, sizes = per-group batch sizes;
+    transa/transb = per-group 'N'/'T' (a string or a list), lda/ldb/ldc = per-group leading dimensions (None: the library's default)"""
     n = len(shapes)
     ints = lambda v: (C.c_int * n)(*[int(x) for x in v])
     ptrs = lambda v: (C.c_void_p * n)(*[dptr(x).value if x is not None else None for x in v])
+    chars = lambda v: None if v is None else C.c_char_p("".join(v).encode())
+    lds = lambda v: None if v is None else ints(v)
+    assert all(v is None or len(v) == n for v in (transa, transb, lda, ldb, ldc)), "one entry per group"
     ct = C.c_double if prec == F64 else C.c_float
     be = ct(beta)
-    return lib().libxsmm_amd_gemm_batch_groups(prec, prec, n, None, None, ints(s[0] for s in shapes), ints(s[1] for s in shapes), ints(s[2] for s in shapes),
-                                               None, None, None, None, C.byref(be), ptrs(a), ptrs(b), ptrs(c), index_base, index_stride,
-                                               ptrs(stride_a), ptrs(stride_b), ptrs(stride_c), ints(sizes), 1 if relaxed else 0)
+    return lib().libxsmm_amd_gemm_batch_groups(prec, prec, n, chars(transa), chars(transb), ints(s[0] for s in shapes), ints(s[1] for s in shapes),
+                                               ints(s[2] for s in shapes), lds(lda), lds(ldb), lds(ldc), None, C.byref(be), ptrs(a), ptrs(b), ptrs(c),
+                                               index_base, index_stride, ptrs(stride_a), ptrs(stride_b), ptrs(stride_c), ints(sizes), 1 if relaxed else 0)
 
 
 def call_kernel(fn_ptr, a, b, c, x3=None):

@@ -1061,9 +1061,13 @@ LIBXSMM_API int libxsmm_amd_smm_kernel_source(const libxsmm_gemm_descriptor* des
     memcpy(buffer, src.data(), n); buffer[n] = 0;
   }
   if (0 != compile) {
-    std::string log;
-    const int rc = jit_check_source(src, &log);
+    std::string log, built;
+    const int rc = jit_check_source(src, &log, &built);
     if (0 != rc && 0 != libxsmm_verbosity) fprintf(stderr, "LIBXSMM-AMD: hiprtc: %s\n", log.c_str());
+    if (0 == rc && 2 == compile && nullptr != buffer && 0 < buffer_size) { // the text the library builds (hand-wait guard applied)
+      const size_t n = (built.size() < buffer_size - 1 ? built.size() : buffer_size - 1);
+      memcpy(buffer, built.data(), n); buffer[n] = 0;
+    }
     return rc;
   }
   return (int)src.size();
@@ -1089,9 +1093,13 @@ LIBXSMM_API int libxsmm_amd_smm_grouped_kernel_source(const libxsmm_gemm_descrip
     memcpy(buffer, src.data(), n); buffer[n] = 0;
   }
   if (0 != compile) {
-    std::string log;
-    const int rc = jit_check_source(src, &log);
+    std::string log, built;
+    const int rc = jit_check_source(src, &log, &built);
     if (0 != rc && 0 != libxsmm_verbosity) fprintf(stderr, "LIBXSMM-AMD: hiprtc: %s\n", log.c_str());
+    if (0 == rc && 2 == compile && nullptr != buffer && 0 < buffer_size) { // the text the library builds (hand-wait guard applied)
+      const size_t n = (built.size() < buffer_size - 1 ? built.size() : buffer_size - 1);
+      memcpy(buffer, built.data(), n); buffer[n] = 0;
+    }
     return rc;
   }
   return (int)src.size();

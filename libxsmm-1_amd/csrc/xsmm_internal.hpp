@@ -121,7 +121,7 @@ bool jit_async_enabled();                                             // LIBXSMM
 void jit_async(std::function<void()> job);                            // run on the compiler thread
 void jit_async_wait();
 void jit_async_drain(); // drop queued compile jobs, wait for the running one                                                // until the compiler thread has nothing left to do
-int jit_check_source(const std::string& src, std::string* log);
+int jit_check_source(const std::string& src, std::string* log, std::string* built = nullptr); // *built: the text the library builds for src
 void jit_release(JitKernel* k);
 int jit_launch_panels(JitKernel* k, const void* B, void* C, long long ncols, long long ldb, long long ldc, int vec, void* stream,
                       const unsigned long long* npanels = nullptr, long long panel = 0);

@@ -2140,7 +2140,12 @@ std::string gen_smm_grouped_source(int typesize, const std::vector<GroupedBody>&
   // The register-tiled bodies are called (inlined, the dispatcher carries the registers of all of them at once: measured slower);
   // the matrix-core bodies are lean enough to be inlined into the switch -- no call, no callee-saved registers through scratch.
   static const int inline_env = []() { const char* e = getenv("XSMM_SMMJIT_GROUPED_INLINE"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
-  s += std::string("#define XENTRY_ATTR ") + ((all_mfma && 0 != inline_env) ? "__forceinline__" : "__attribute__((noinline))") + "\n";
+  const bool inlined = (all_mfma && 0 != inline_env);
+  s += std::string("#define XENTRY_ATTR ") + (inlined ? "__forceinline__" : "__attribute__((noinline))") + "\n";
+  // Hand-counted waits only in bodies inlined into a dispatcher without calls. A called body reads its DevAddr through a generic
+  // pointer into the dispatcher's private copy of the table entry (FLAT loads from scratch, which retire out of order with the
+  // other vector-memory operations) and spills through scratch: traffic the counts do not know (hand-counted waits).
+  const int handwait = inlined ? smm_mfma_handwait() : 0;
   s += SMM_JIT_PRELUDE;
   for (size_t i = 0; i < bodies.size(); ++i) {
     const GroupedBody& b = bodies[i];
@@ -2156,7 +2161,7 @@ std::string gen_smm_grouped_source(int typesize, const std::vector<GroupedBody>&
     s += "#define XDEPTH " + std::to_string(0 != (b.variant & SMM_JIT_MFMA_RUNS) ? smm_mfma_runs_depth(typesize, b.m, b.n, b.k, b.ldb, 0 != (b.variant & SMM_JIT_DEEP)) : smm_jit_depth(typesize, b.m, b.n, b.k, b.variant)) + "\n";
     s += std::string("#define XSPLIT ") + ((b.variant & SMM_JIT_SPLIT) ? "1" : "0") + "\n";
     s += std::string("#define XHASWG ") + ((b.variant & SMM_JIT_HASWG) ? "1" : "0") + "\n";
-    if (0 != (b.variant & SMM_JIT_MFMA_RUNS)) { s += "#define XSTREAM 0\n#define XHANDWAIT " + std::to_string(smm_mfma_handwait()) + "\n"; s += SMM_JIT_MFMA_RUNS_CONST; s += SMM_JIT_CHAIN; s += SMM_JIT_MFMA_RUNS_KERNEL; s += "#undef XNROW\n#undef XSTREAM\n#undef XHANDWAIT\n"; }
+    if (0 != (b.variant & SMM_JIT_MFMA_RUNS)) { s += "#define XSTREAM 0\n#define XHANDWAIT " + std::to_string(handwait) + "\n"; s += SMM_JIT_MFMA_RUNS_CONST; s += SMM_JIT_CHAIN; s += SMM_JIT_MFMA_RUNS_KERNEL; s += "#undef XNROW\n#undef XSTREAM\n#undef XHANDWAIT\n"; }
     else { s += SMM_JIT_SHAPE; s += SMM_JIT_CHAIN; s += SMM_JIT_SHAPE_KERNELS; }
     s += "#undef XM\n#undef XN\n#undef XK\n#undef XBETA0\n#undef XTRANSB\n#undef XLDA\n#undef XLDB\n#undef XLDC\n#undef XPACK\n#undef XWAVES\n"
          "#undef XSCALAR\n#undef XRUNS\n#undef XDEPTH\n#undef XSPLIT\n#undef XHASWG\n#undef WINDOW_AB\n}\n";
