@@ -194,7 +194,7 @@ void bgemm_run(const libxsmm_blocked_gemm_handle* h, const void* a, const void* 
     if (nullptr != d_flags && 0 == launch_c_order_check(j, d_flags, device().stream)) {
       j.sync = SYNC_DEVICE; j.devflags = d_flags; j.relaxed = 1; j.c_atomics = is_host_visible(dc) ? 0 : 1;
       j.uniform_run = h->kb; // every C block's k blocks follow each other in the work list
-      if (smm_jit_eligible(j)) e = launch_smm_jit(j, device().stream, &name);
+      e = launch_smm_jit(j, device().stream, &name);
     }
     flag_slot_commit();
   }

@@ -30,12 +30,9 @@ int run_smm(const SmmBatch& s, int host_visible = -1)
 {
   const char* name = "";
   int e = -1;
-  static const int wave_min = []() { const char* w = getenv("XSMM_SMMJIT_WAVE_MIN"); return (nullptr != w && 0 != *w) ? atoi(w) : 32; }();
-  if (0 == s.general && (wave_min < s.m || wave_min < s.n)) e = launch_smm_jit_mfma(s, device().stream, &name); // matrix-core work-group kernel of this very descriptor
+  e = launch_smm_jit_mfma(s, device().stream, &name);                               // matrix-core kernels of this very descriptor
   if (e < 0 && 0 == s.general) e = launch_smm_special(s, device().stream, &name);  // hand-tuned shapes; the same kernels for any descriptor
-  if (e < 0 && smm_jit_eligible(s)) {                                               // shape-specialised via hiprtc
-    e = launch_smm_jit(s, device().stream, &name); // (SYNC_DEVICE: whatever the verdict on the device, one of its kernels works)
-  }
+  if (e < 0) e = launch_smm_jit(s, device().stream, &name);                         // shape-specialised via hiprtc (SYNC_DEVICE: whatever the verdict on the device, one of its kernels works)
   if (e < 0) e = launch_smm_generic(s, device().stream, &name);                     // any descriptor
   if (SYNC_DEVICE == s.sync) flag_slot_commit(); // the launches that read the verdict are queued
   note_launch(name);
@@ -478,7 +475,7 @@ SmmBatch lowp_from_descriptor(const libxsmm_gemm_descriptor& d, float scf)
 int lowp_launch(const SmmBatch& s)
 {
   const char* name = "";
-  int e = launch_smm_jit_lowp(s, device().stream, &name); // large strided batches of small tight items: specialised streaming form
+  int e = launch_smm_jit(s, device().stream, &name); // large strided batches of small tight items: specialised streaming form
   if (e < 0) e = launch_smm_lowp(s, device().stream, &name);
   note_launch(name);
   if (0 != e) fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);

@@ -16,6 +16,7 @@
 #include <string>
 #include <algorithm>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 namespace xsmm {
@@ -1514,6 +1515,14 @@ extern "C" __global__ __launch_bounds__(64 * XWAVES) void xsmm_smm_op(DevAddr ad
 #endif
 )XSMM";
 
+// A developer knob: the number in environment variable `name`, `dflt` if it is unset or empty. Most knobs are read once, into a
+// static at the one place that uses them; those that tests and tools toggle inside a process are read on every call.
+static long long knob(const char* name, long long dflt)
+{
+  const char* const e = getenv(name);
+  return (nullptr != e && 0 != *e) ? atoll(e) : dflt;
+}
+
 // LDS bytes of a wave of that kernel (mirrors the constexpr arithmetic of the source); 0: the shape is not served
 static size_t smm_mfma_wave_lds(int typesize, int m, int n, int k, int vec = 0, bool transb = false)
 { // vec: elements per memory access (0: a 16-byte chunk)
@@ -1547,7 +1556,7 @@ static int smm_mfma_wave_wpe(size_t lds, int typesize = 0, int m = 0, int n = 0,
   if (lda < m) lda = m;
   if (ldb < k) ldb = k;
   if (ldc < m) ldc = m;
-  static const int env = []() { const char* e = getenv("XSMM_SMMJIT_WAVE_WPE"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }(); // developer knob
+  static const int env = (int)knob("XSMM_SMMJIT_WAVE_WPE", 0);
   if (0 < env) return env;
   if (8 * lds > 160u * 1024u) return 1;
   if (1 == vec) { // element-wise form: a register per element in flight plus what parking them costs (45^3 fp32 spills at two waves per SIMD)
@@ -1570,7 +1579,7 @@ static size_t smm_mfma_runs_lds(int typesize, int m, int n, int k, int ldb, bool
 // products in flight per wave (register sets): as many as fit ~80 registers, four at most
 static int smm_mfma_runs_depth(int typesize, int m, int n, int k, int ldb, bool deep = false)
 { // deep: the tiles of a batch of few runs (smm_tile_split) -- a wave or two per SIMD, the registers are there
-  static const int env = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_RUNS_DEPTH"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }(); // developer knob
+  static const int env = (int)knob("XSMM_SMMJIT_MFMA_RUNS_DEPTH", 0);
   if (0 < env) return env > 4 ? 4 : env;
   if (ldb < k) ldb = k;
   const int regs = (typesize / 4) * (((k + 3) / 4) * ((m + 15) / 16) + (ldb * (n - 1) + k + 63) / 64);
@@ -1580,7 +1589,7 @@ static int smm_mfma_runs_depth(int typesize, int m, int n, int k, int ldb, bool 
 // hand-counted waits in the software pipeline of the run form (XSMM_SMMJIT_HANDWAIT=0: the compiler's: developer knob)
 static int smm_mfma_handwait()
 {
-  static const int env = []() { const char* e = getenv("XSMM_SMMJIT_HANDWAIT"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
+  static const int env = (int)knob("XSMM_SMMJIT_HANDWAIT", 1);
   return 0 != env ? 1 : 0;
 }
 // XSMM_SMMJIT_TILESPLIT=2 (developer knob, re-read on every call): the tiles of a run as the waves of ONE work-group instead of work-groups
@@ -1588,27 +1597,16 @@ static int smm_mfma_handwait()
 // faster for batches of 16 000-30 000 items in short runs (the halves of A and B two tiles share are requested from one CU), but a long run
 // is walked SLOWER than by a single wave (runs of 256: 0.41 ms against 0.18 ms for the tiles as groups and 0.31 ms for a wave per run; one
 // CP2K stack 0.19 against 0.14 ms): not the default.
-static int smm_tile_wg()
-{
-  const char* const e = getenv("XSMM_SMMJIT_TILESPLIT");
-  return (nullptr != e && 2 == atoi(e)) ? 1 : 0;
-}
+// (0: the tiles of a batch of few runs are not split off at all, smm_tile_split)
+static int smm_tilesplit() { return (int)knob("XSMM_SMMJIT_TILESPLIT", 1); }
 static int smm_mfma_runs_waves(size_t lds) { return (0 == lds) ? 0 : ((4 * lds <= 65536) ? 4 : ((2 * lds <= 65536) ? 2 : 1)); }
-// may batch s (shared C: runs) take that form?
-static bool smm_mfma_runs_ok(const SmmBatch& s)
+// may batch s take that form? stream: the streaming form (items that own their C; K up to 256), else the run form (shared C)
+static bool smm_mfma_runs_ok(const SmmBatch& s, bool stream = false)
 {
-  static const int on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_RUNS"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
-  if (0 == on || 0 == s.use_mfma || 0 != s.lowp || 0 != s.general || 0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)) return false;
+  static const int on = (int)knob("XSMM_SMMJIT_MFMA_RUNS", 1);
+  if (0 == on || 0 == s.use_mfma || 0 != s.lowp || 0 != s.general || 0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) || (stream && SYNC_NONE != s.sync)) return false;
   if (s.lda < s.m || s.ldb < s.k || s.ldc < s.m) return false;
-  return 0 != smm_mfma_runs_lds(s.typesize, s.m, s.n, s.k, s.ldb);
-}
-// ... the streaming form (items that own their C; K up to 256)
-static bool smm_mfma_stream_ok(const SmmBatch& s)
-{
-  static const int on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_RUNS"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-  if (0 == on || 0 == s.use_mfma || 0 != s.lowp || 0 != s.general || 0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) || SYNC_NONE != s.sync) return false;
-  if (s.lda < s.m || s.ldb < s.k || s.ldc < s.m) return false;
-  return 0 != smm_mfma_runs_lds(s.typesize, s.m, s.n, s.k, s.ldb, true);
+  return 0 != smm_mfma_runs_lds(s.typesize, s.m, s.n, s.k, s.ldb, stream);
 }
 
 // ---- shapes with 32 < M or N <= 64: one work-group (256 threads, 16 x 16) per item, K in chunks of KC through LDS ------
@@ -1808,18 +1806,17 @@ JitKernel* jit_resolve(MAP& table, const KEY& key, const char* fname, bool wait,
 static int smm_jit_waves(int typesize, int m, int n, int k, int flags, int pack = 1, bool runs = false);
 
 // k-chunk of the work-group-per-item form: the largest of 32/16/8 whose two LDS buffers fit 64 KiB (0: none does)
-static size_t smm_jit_big_buf(int typesize, int m, int n, int kc, int flags)
+static size_t smm_jit_big_buf(int typesize, int m, int n, int kc)
 {
   const size_t mp = 16 * (size_t)((m + 15) / 16), np = 16 * (size_t)((n + 15) / 16);
-  (void)flags;
   const size_t as = (size_t)kc * mp, bs = (size_t)kc * (np + 16 / (size_t)typesize);
   return ((as + bs + 3) / 4) * 4 * (size_t)typesize;
 }
-static int smm_jit_big_kc(int typesize, int m, int n, int k, int flags)
+static int smm_jit_big_kc(int typesize, int m, int n, int k)
 {
   for (int kc = 32; kc >= 8; kc /= 2) {
     if (kc / 2 >= k && kc > 8) continue; // a shorter chunk already covers K
-    if (2 * smm_jit_big_buf(typesize, m, n, kc, flags) <= 65536) return kc;
+    if (2 * smm_jit_big_buf(typesize, m, n, kc) <= 65536) return kc;
   }
   return 0;
 }
@@ -1830,10 +1827,9 @@ static int smm_jit_big_kc(int typesize, int m, int n, int k, int flags)
 // The ring stays in the source as a developer knob (XSMM_SMMJIT_DEPTH).
 static int smm_jit_depth(int typesize, int m, int n, int k, int variant)
 {
-  (void)typesize; (void)m; (void)n; (void)k;
   if (0 == (variant & (SMM_JIT_RUNS | SMM_JIT_WGRUNS))) return 1;
-  static const int env = []() { const char* e = getenv("XSMM_SMMJIT_DEPTH"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }();
-  static const int env_bytes = []() { const char* e = getenv("XSMM_SMMJIT_DEPTH_BYTES"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }(); // (developer knob: only products up to this many operand bytes)
+  static const int env = (int)knob("XSMM_SMMJIT_DEPTH", 0);
+  static const int env_bytes = (int)knob("XSMM_SMMJIT_DEPTH_BYTES", 0); // (only products up to this many operand bytes)
   if (0 < env_bytes && (long long)typesize * ((long long)m * k + (long long)k * n) > env_bytes) return 1;
   return (0 < env && env <= 8) ? env : 1;
 }
@@ -1894,11 +1890,12 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
     return s;
   }
   if (0 != (variant & SMM_JIT_BIG)) { // work-group per item, K chunked
-    s += "#define XKC " + std::to_string(smm_jit_big_kc(typesize, m, n, k, flags)) + "\n";
+    s += "#define XKC " + std::to_string(smm_jit_big_kc(typesize, m, n, k)) + "\n";
     s += SMM_JIT_BIG_BODY;
     return s;
   }
   const int pack = smm_jit_pack_of(variant);
+  static const int defer_env = (int)knob("XSMM_SMMJIT_DEFER", 1); // deferred stores of the streaming form
   s += "#define XLDA " + std::to_string(lda) + "\n#define XLDB " + std::to_string(ldb) + "\n#define XLDC " + std::to_string(ldc) + "\n"; // leading dimensions in memory
   s += "#define XPACK " + std::to_string(pack) + "\n";   // items per wave pass (streaming form of tight strided batches)
   const bool wave_runs = (0 != (variant & SMM_JIT_RUNS) && 0 == (variant & SMM_JIT_WGRUNS)); // (the wave run form keeps C's image over the operands')
@@ -1908,20 +1905,16 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
   s += std::string("#define XRUNS ") + ((variant & SMM_JIT_WGRUNS) ? "2" : ((variant & SMM_JIT_RUNS) ? "1" : "0")) + "\n";
   { // address space of the operand accesses: global for the run forms; the streaming (one wave per item) form measured
     // faster with generic pointers, i.e. FLAT instructions (f64 13^3: 60.7 vs 55.3 %, the fp32 32^3 kernels 72.5 vs 69 %)
-    static const int flat_env = []() { const char* e = getenv("XSMM_SMMJIT_FLAT"); return (nullptr != e && 0 != *e) ? atoi(e) : -1; }();
-    static const int defer_env0 = []() { const char* e = getenv("XSMM_SMMJIT_DEFER"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
+    static const int flat_env = (int)knob("XSMM_SMMJIT_FLAT", -1);
     // (with the stores deferred the global form is the faster one: tools/sweep_defer.sh, profiles/r2_sweep_defer.txt)
-    const int flat = (0 <= flat_env) ? flat_env : ((0 != (variant & (SMM_JIT_RUNS | SMM_JIT_WGRUNS)) || 0 != defer_env0) ? 0 : 1);
+    const int flat = (0 <= flat_env) ? flat_env : ((0 != (variant & (SMM_JIT_RUNS | SMM_JIT_WGRUNS)) || 0 != defer_env) ? 0 : 1);
     s += std::string("#define XFLAT ") + (flat ? "1" : "0") + "\n";
   }
   s += "#define XDEPTH " + std::to_string(smm_jit_depth(typesize, m, n, k, variant)) + "\n";  // register stages of the run forms
   s += std::string("#define XSPLIT ") + ((variant & SMM_JIT_SPLIT) ? "1" : "0") + "\n";  // relaxed order: few long runs are cut into segments (atomics)
   s += std::string("#define XHASWG ") + ((variant & SMM_JIT_HASWG) ? "1" : "0") + "\n";   // wave form: leave long runs to the work-group form
   s += "#define XGROUPED 0\n";
-  { // deferred stores of the streaming form (developer knob)
-    static const int defer_env = []() { const char* e = getenv("XSMM_SMMJIT_DEFER"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-    s += std::string("#define XDEFER ") + (defer_env ? "1" : "0") + "\n";
-  }
+  s += std::string("#define XDEFER ") + (defer_env ? "1" : "0") + "\n";
   s += SMM_JIT_PRELUDE;
   s += SMM_JIT_SHAPE; s += SMM_JIT_CHAIN; s += SMM_JIT_SHAPE_KERNELS;
   return s;
@@ -1947,27 +1940,34 @@ static int smm_jit_waves(int typesize, int m, int n, int k, int flags, int pack,
   return (4 * w <= 65536) ? 4 : ((2 * w <= 65536) ? 2 : ((w <= 65536) ? 1 : 0));
 }
 
+// LIBXSMM_AMD_JIT=0: no specialised dense kernel (read on every call: tests and tools toggle it)
+static bool smm_jit_enabled()
+{
+  const char* const e = getenv("LIBXSMM_AMD_JIT");
+  return nullptr == e || 0 != atoi(e);
+}
+// smallest batch that is specialised unless the caller asks for it (read on every call: tests set it)
+static long long smm_jit_min_batch() { return knob("LIBXSMM_AMD_JIT_MINBATCH", 16); }
+
 bool smm_jit_eligible(const SmmBatch& s)
 {
-  const char* const env_jit = getenv("LIBXSMM_AMD_JIT"); // re-read on every call: tests and tools toggle it
-  const bool enabled = (nullptr == env_jit || 0 != atoi(env_jit));
-  if (!enabled || 0 != s.general || SYNC_ATOMIC == s.sync) return false;
+  if (!smm_jit_enabled() || 0 != s.general || SYNC_ATOMIC == s.sync) return false;
   if (SYNC_NONE != s.sync && 0 != (s.flags & LIBXSMM_GEMM_FLAG_BETA_0)) return false; // (never chosen: beta == 0 needs no care)
   if (SYNC_DEVICE == s.sync && 0 == s.c_atomics) return false;  // C in host memory the GPU maps: the generic kernel adds by compare-and-swap (cas_add, kernels/smm_generic.hip)
   const bool tight = (s.lda == s.m && s.ldc == s.m && (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (s.ldb == s.n) : (s.ldb == s.k)));
   if (!tight) { // leading dimensions with gaps: the wave forms fetch an operand's whole span -- as long as the gaps stay moderate
-    if (s.m > 32 || s.n > 32 || (s.k > 64 && !smm_mfma_stream_ok(s))) return false;
+    if (s.m > 32 || s.n > 32 || (s.k > 64 && !smm_mfma_runs_ok(s, true))) return false;
     const long long span = (long long)s.lda * (s.k - 1) + s.m + (long long)s.ldb * ((0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? s.k : s.n) - 1)
                          + (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? s.n : s.k) + (long long)s.ldc * (s.n - 1) + s.m;
     const long long used = (long long)s.m * s.k + (long long)s.k * s.n + (long long)s.m * s.n;
     if (2 * used < span) return false;
-    if (span * s.typesize > 40960 && !(s.k > 64 && smm_mfma_stream_ok(s))) return false; // (a long K in chunks: no whole operand is ever on chip)
+    if (span * s.typesize > 40960 && !(s.k > 64 && smm_mfma_runs_ok(s, true))) return false; // (a long K in chunks: no whole operand is ever on chip)
   }
-  if (s.m <= 32 && s.n <= 32 && s.k > 64 && smm_mfma_stream_ok(s)) { /* the matrix-core streaming form takes K in chunks of up to 64 */ }
+  if (s.m <= 32 && s.n <= 32 && s.k > 64 && smm_mfma_runs_ok(s, true)) { /* the matrix-core streaming form takes K in chunks of up to 64 */ }
   else if (s.m > 32 || s.n > 32 || s.k > 64) { // work-group-per-item form: 16x16 threads x (<=4x4) tile, K chunked (also small M, N with a long K)
     if (s.m > 64 || s.n > 64 || s.k > 1024) return false;
     if (SYNC_NONE != s.sync && !(0 < s.uniform_run && 0 == s.batch % s.uniform_run)) return false; // shared C only as runs of a known, uniform length
-    if (0 == smm_jit_big_kc(s.typesize, s.m, s.n, s.k, s.flags)) return false;
+    if (0 == smm_jit_big_kc(s.typesize, s.m, s.n, s.k)) return false;
   }
   else {
     if (s.k > 64) return false;                                                // 8x8 lanes x (<=4x4) tile, whole K in LDS
@@ -1976,10 +1976,7 @@ bool smm_jit_eligible(const SmmBatch& s)
   // (the compiler works on a helper thread and its output is kept on disk, so a small batch is enough of a reason: the
   // specialised kernel is the faster one at every size measured -- fp64 23^3: 7.9 vs 12.2 us at 32 items, 8.4 vs 13.5 us at 1024,
   // 50 vs 77 us at 16 384; tools/bench_small_batches.py, profiles/r3_small_batches.txt)
-  const char* const env_min = getenv("LIBXSMM_AMD_JIT_MINBATCH");
-  const long long min_batch = (nullptr != env_min && 0 != *env_min) ? atoll(env_min) : 16LL;
-  if (s.batch < min_batch && 0 == s.jit_always) return false;
-  return true;
+  return s.batch >= smm_jit_min_batch() || 0 != s.jit_always;
 }
 
 // LDS bytes of one operand buffer of the work-group form (mirrors the constexpr arithmetic of the source)
@@ -2013,80 +2010,126 @@ static JitKernel* smm_jit_get(const SmmKey& key, bool wait = false)
     return gen_smm_source(key.typesize, key.m, key.n, key.k, key.flags, key.variant, key.lda, key.ldb, key.ldc); });
 }
 
-// one launch of one flavour; -1 when the kernel is not available
-static int smm_jit_launch_variant(const SmmBatch& s, int variant, void* stream)
+// ---- one launch of a generated kernel ----------------------------------------------------------------------------------
+// the host image of DevAddr (SMM_JIT_PRELUDE), the first argument of every generated kernel
+struct DevAddrH { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; };
+static_assert(sizeof(DevAddrH) == 96, "DevAddrH must have the layout of the device's DevAddr");
+static DevAddrH dev_addr(const SmmBatch& s)
 {
-  const SmmKey key = { s.typesize, s.m, s.n, s.k, s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B), variant, s.lda, s.ldb, s.ldc };
-  JitKernel* const k = smm_jit_get(key);
-  if (nullptr == k) return -1;
-  struct { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; } ad;
+  DevAddrH ad;
+  memset(&ad, 0, sizeof(ad));
   ad.a = (const char*)s.a; ad.b = (const char*)s.b; ad.c = (char*)s.c; ad.ia = (const char*)s.ia; ad.ib = (const char*)s.ib; ad.ic = (const char*)s.ic;
   ad.sa = s.sa; ad.sb = s.sb; ad.sc = s.sc; ad.index_base = s.index_base; ad.index_stride = s.index_stride; ad.mode = s.mode;
-  ad.flags = (SYNC_DEVICE == s.sync ? s.devflags : nullptr);
-  long long batch = s.batch;
-  static const int bpc_env = []() { const char* e = getenv("XSMM_SMMJIT_BPC"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }();
-  if (0 != (variant & SMM_JIT_BIG)) { // one work-group per item, walking the batch with a stride of the grid
-    const size_t lds = 2 * smm_jit_big_buf(s.typesize, s.m, s.n, smm_jit_big_kc(s.typesize, s.m, s.n, s.k, s.flags), s.flags);
-    long long per_cu = (long long)((160 * 1024) / (lds ? lds : 1));
-    if (per_cu > 4) per_cu = 4;
+  ad.flags = (SYNC_DEVICE == s.sync ? s.devflags : nullptr); // the device-side verdict, read by the run forms
+  return ad;
+}
+
+// work-groups per CU: as many as leave each `lds` bytes of the 160 KiB, `cap` at most, one at least
+static long long smm_per_cu(size_t lds, long long cap)
+{
+  const long long per_cu = (long long)((160 * 1024) / (lds ? lds : 1));
+  return per_cu > cap ? cap : (per_cu < 1 ? 1 : per_cu);
+}
+
+// Grid, work-group, dynamic LDS and third kernel argument of a launch of the generated kernel `variant` over batch s. The grids
+// are persistent: at most 256 CUs times the work-groups per CU, each walks the batch with a stride of the grid.
+struct SmmGeom { long long blocks; unsigned threads, lds; long long runlen; bool runlen64; };
+static SmmGeom smm_jit_geometry(const SmmBatch& s, int variant, JitKernel* k)
+{
+  static const int bpc_env = (int)knob("XSMM_SMMJIT_BPC", 0);
+  SmmGeom g = { 0, 256u, 0u, 1, false };
+  const bool verdict = (SYNC_DEVICE == s.sync && nullptr != s.devflags);
+  long long units = s.batch, per_cu = 1; // units: work-groups without the cap
+  if (0 != (variant & SMM_JIT_BIG)) { // one work-group per item (per run of uniform length)
+    per_cu = smm_per_cu(2 * smm_jit_big_buf(s.typesize, s.m, s.n, smm_jit_big_kc(s.typesize, s.m, s.n, s.k)), 4);
     // a persistent grid must not exceed what is resident: a work-group that starts after the others have finished their
     // share is pure tail (measured: f64 64^3 with 150 VGPRs fits 3 per CU; a grid of 4 per CU loses 12 %)
     const int occ = jit_blocks_per_cu(k, 256);
     if (0 < occ && occ < per_cu) per_cu = occ;
-    if (per_cu < 1) per_cu = 1;
     if (0 < bpc_env) per_cu = bpc_env;
-    long long runlen = (0 < s.uniform_run ? s.uniform_run : 1);
-    long long blocks = batch / runlen;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    if (blocks < 1) blocks = 1;
-    void* args[] = { &ad, &batch, &runlen };
-    return jit_launch_args(k, (unsigned)blocks, 256u, args, stream);
+    g.runlen = (0 < s.uniform_run ? s.uniform_run : 1); g.runlen64 = true;
+    units = s.batch / g.runlen;
   }
-  if (0 != (variant & SMM_JIT_WGRUNS)) { // work-groups of 256 threads, dealt chunks of 64 items
+  else if (0 != (variant & SMM_JIT_WGRUNS)) { // work-groups of 256 threads, dealt chunks of 64 items
     const size_t buf = smm_jit_wg_buf(s.typesize, s.m, s.n, s.k, s.flags);
-    const size_t lds = (2 * buf <= 65536 ? 2 : 1) * buf;
-    long long per_cu = (long long)((160 * 1024) / (lds ? lds : 1));
-    if (per_cu > 4) per_cu = 4;
-    if (per_cu < 1) per_cu = 1;
+    per_cu = smm_per_cu((2 * buf <= 65536 ? 2 : 1) * buf, 4);
     if (0 < bpc_env) per_cu = bpc_env;
-    long long blocks = (batch + 63) / 64;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    if (blocks < 1) blocks = 1;
-    return jit_launch_raw(k, (unsigned)blocks, 256u, &ad, sizeof(ad), &batch, stream);
+    units = (s.batch + 63) / 64;
   }
-  if (0 != (variant & SMM_JIT_MFMA_RUNS)) { // a wave per run on the matrix cores, dealt chunks of 64 items (segments of 8 and more if the verdict cuts the batch up)
+  else if (0 != (variant & SMM_JIT_MFMA_RUNS)) { // a wave per run on the matrix cores, dealt chunks of 64 items (segments of 8 and more if the verdict cuts the batch up)
     const bool stream_form = (0 == (variant & SMM_JIT_RUNS)); // every item owns its C: a wave per item, stride of the resident waves
     const size_t wlds = smm_mfma_runs_lds(s.typesize, s.m, s.n, s.k, s.ldb, stream_form);
     const int waves = smm_mfma_runs_waves(wlds);
-    if (0 == waves) return -1;
-    const long long units = stream_form ? batch : ((nullptr != ad.flags) ? (batch + 7) / 8 : (batch + 63) / 64);
-    long long blocks = (units + waves - 1) / waves;
-    long long per_cu = (long long)((160 * 1024) / (wlds * (size_t)waves)); if (per_cu * waves > 16) per_cu = 16 / waves; if (per_cu < 1) per_cu = 1;
+    per_cu = smm_per_cu(wlds * (size_t)waves, 16 / waves);
     if (stream_form) { const int occ = jit_blocks_per_cu(k, 64 * waves); if (0 < occ && occ < per_cu) per_cu = occ; } // (a persistent grid must not exceed what is resident)
     if (0 < bpc_env) per_cu = bpc_env;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    if (blocks < 1) blocks = 1;
-    return jit_launch_raw(k, (unsigned)blocks, 64u * (unsigned)waves, &ad, sizeof(ad), &batch, stream);
+    g.threads = 64u * (unsigned)waves;
+    units = ((stream_form ? s.batch : (verdict ? (s.batch + 7) / 8 : (s.batch + 63) / 64)) + waves - 1) / waves;
   }
-  const int pack = smm_jit_pack_of(variant);
-  if (1 < pack) { // the launch covers batch / pack groups of `pack` consecutive items (the caller handles the remainder)
-    ad.sa *= pack; ad.sb *= pack; ad.sc *= pack; batch /= pack;
-    if (0 == batch) return 0;
+  else if (0 != (variant & SMM_JIT_MFMA_WAVE)) { // one wave per item on the matrix cores
+    const bool transb = (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)), wide = (0 == (variant & SMM_JIT_SCALAR));
+    const int vec = wide ? 16 / s.typesize : 1;
+    const size_t wlds = smm_mfma_wave_lds(s.typesize, s.m, s.n, s.k, vec, transb);
+    g.threads = 64u; g.lds = (unsigned)wlds;
+    if (0 != ((variant >> 11) & 3)) { // 16-bit inputs: eight waves per CU (tools/bench_dense.py lowp, XSMM_SMMJIT_WAVE_PERCU sweep, % of the HBM peak
+      // at 8 / as many as LDS and registers allow: bf16 -> f32 48^3 70.5 / 67.4, 64^3 74.4 / 67.7; bf16 -> bf16 32^3 73.5 / 67.6, 48^3 73.5 / 62.5,
+      // 64^3 60.3 / 54.7; three or four -- the optimum of the fp32 / fp64 wave kernels -- lose 5-30 points here: the widening and rounding
+      // work per item wants more waves to overlap with) -- also where fewer fit: whatever is not resident at once starts as the others finish
+      per_cu = 8;
+    }
+    else {
+      const int by_regs = 4 * smm_mfma_wave_wpe(wlds, s.typesize, s.m, s.n, s.k, vec, s.lda, s.ldb, s.ldc);
+      per_cu = smm_per_cu(wlds, by_regs);
+      // The memory system is at its best with ~100 KB of operands in flight per CU (the fp32 32^3 kernel: twelve waves of 12 KB); a wave
+      // here has a whole item of 19-55 KB in flight. Waves per CU, % of the HBM peak (tools/bench_dense.py, XSMM_SMMJIT_WAVE_PERCU sweep):
+      // f32 40^3 3: 71.8, 4: 73.8, 8: 67.9, 12: 67.5 | f64 40^3 3: 72.2, 4: 69.3, 8: 69.0 | f32 48^3 3: 72.9, 4: 70.3, 8: 68.3 |
+      // f64 48^3 3: 68.8, 8: 69.1, 12: 69.7 | f32 56^3 3: 69.8, 4: 68.6, 8: 67.6; five to seven waves (uneven over the four SIMDs) lose 3-15 points.
+      const size_t item_bytes = (size_t)s.typesize * ((size_t)s.lda * s.k + (size_t)s.ldb * (transb ? s.k : s.n) + (size_t)s.ldc * s.n);
+      if (wide && item_bytes >= 16384) { per_cu = (100u * 1024u / item_bytes >= 4) ? 4 : 3; if (per_cu > by_regs) per_cu = by_regs; }
+    }
+    const long long percu_env = knob("XSMM_SMMJIT_WAVE_PERCU", 0); // (read on every call)
+    if (0 < percu_env) per_cu = percu_env;
   }
-  const bool wave_runs = (0 != (variant & SMM_JIT_RUNS));
-  const int waves = smm_jit_waves(s.typesize, s.m, s.n, s.k, s.flags, pack, wave_runs);
-  const size_t lds = (size_t)waves * smm_jit_wave_lds(s.typesize, s.m, s.n, s.k, s.flags, pack, wave_runs);
-  long long per_cu = (long long)((160 * 1024) / (lds ? lds : 1));
-  if (per_cu * waves > 16) per_cu = 16 / waves; // the streaming rate peaks around 12-16 waves per CU
-  if (per_cu < 1) per_cu = 1;
-  if (0 < bpc_env) per_cu = bpc_env;
-  // run form: a wave scans chunks of 64 items for run heads, so the grid is sized by chunks
-  // (the verdict is on the device: segments of 8 items and more if the batch is cut up -- waves without a chunk leave at once)
-  const long long units = (0 != (variant & SMM_JIT_RUNS)) ? ((nullptr != ad.flags ? (batch + 7) / 8 : (batch + 63) / 64)) : batch;
-  long long blocks = (units + waves - 1) / waves;
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-  if (blocks < 1) blocks = 1;
-  return jit_launch_raw(k, (unsigned)blocks, 64u * (unsigned)waves, &ad, sizeof(ad), &batch, stream);
+  else if (0 != (variant & SMM_JIT_MFMA_WAVE2)) { // ... the columns of C in two halves: four waves per CU
+    g.threads = 64u; g.lds = (unsigned)smm_mfma_wave2_lds(s.typesize, s.m, s.n, s.k);
+    per_cu = 4;
+  }
+  else if (0 != (variant & SMM_JIT_MFMA)) { // matrix-core work-group kernel: an item (a run of uniform length) per work-group
+    static const int bpc64_env = (int)knob("XSMM_SMM64_BPC", 0);
+    per_cu = (0 != (variant & SMM_JIT_MFMA_TIGHTC)) ? 3 : 4; // (48 KiB of LDS with the C image: three work-groups per CU)
+    if (8 == s.typesize) { // (the sizes of the pre-compiled launch, kernels/smm_special.hip)
+      g.lds = (unsigned)((s.k > 32) ? (size_t)2 * 32 * 64 * sizeof(double) : (size_t)2 * (4 * ((s.k + 3) / 4)) * 64 * sizeof(double));
+      per_cu = smm_per_cu(g.lds, 3);
+    }
+    if (0 < bpc64_env) per_cu = bpc64_env;
+    g.runlen = (SYNC_RUNS == s.sync) ? s.uniform_run : 1;
+    units = s.batch / g.runlen;
+  }
+  else { // the register-tiled streaming and wave run forms: work-groups of up to four waves
+    const int pack = smm_jit_pack_of(variant);
+    const bool wave_runs = (0 != (variant & SMM_JIT_RUNS));
+    const int waves = smm_jit_waves(s.typesize, s.m, s.n, s.k, s.flags, pack, wave_runs);
+    per_cu = smm_per_cu((size_t)waves * smm_jit_wave_lds(s.typesize, s.m, s.n, s.k, s.flags, pack, wave_runs), 16 / waves); // (the streaming rate peaks around 12-16 waves per CU)
+    if (0 < bpc_env) per_cu = bpc_env;
+    g.threads = 64u * (unsigned)waves;
+    // run form: a wave scans chunks of 64 items for run heads, so the grid is sized by chunks
+    // (the verdict is on the device: segments of 8 items and more if the batch is cut up -- waves without a chunk leave at once)
+    units = ((wave_runs ? (verdict ? (s.batch + 7) / 8 : (s.batch + 63) / 64) : s.batch) + waves - 1) / waves;
+  }
+  g.blocks = (units > 256 * per_cu) ? 256 * per_cu : units;
+  if (g.blocks < 1) g.blocks = 1;
+  return g;
+}
+
+// one launch of kernel k (the generated kernel `variant`) over batch s
+static int smm_jit_launch(const SmmBatch& s, int variant, JitKernel* k, void* stream)
+{
+  DevAddrH ad = dev_addr(s);
+  long long batch = s.batch;
+  SmmGeom g = smm_jit_geometry(s, variant, k);
+  int runlen = (int)g.runlen;
+  void* args[] = { &ad, &batch, g.runlen64 ? (void*)&g.runlen : (void*)&runlen }; // (kernels of two arguments read two)
+  return jit_launch_dyn(k, (unsigned)g.blocks, g.threads, g.lds, args, stream);
 }
 
 // Items a wave handles at a time. Only for batches laid out back to back (strided, tight, the "wide" flavour): a small or
@@ -2094,7 +2137,7 @@ static int smm_jit_launch_variant(const SmmBatch& s, int variant, void* stream)
 // idle. Developer knob: XSMM_SMMJIT_PACK.
 static int smm_jit_pack(const SmmBatch& s, int width)
 {
-  static const int env = []() { const char* e = getenv("XSMM_SMMJIT_PACK"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }();
+  static const int env = (int)knob("XSMM_SMMJIT_PACK", 0);
   if (0 != width || ADDR_STRIDED != s.mode || 0 == s.sa || 0 == s.sb || 0 == s.sc) return 1;
   int pack = 1;
   if (0 < env) pack = env;
@@ -2139,7 +2182,7 @@ std::string gen_smm_grouped_source(int typesize, const std::vector<GroupedBody>&
   for (const GroupedBody& b : bodies) all_mfma = all_mfma && 0 != (b.variant & SMM_JIT_MFMA_RUNS);
   // The register-tiled bodies are called (inlined, the dispatcher carries the registers of all of them at once: measured slower);
   // the matrix-core bodies are lean enough to be inlined into the switch -- no call, no callee-saved registers through scratch.
-  static const int inline_env = []() { const char* e = getenv("XSMM_SMMJIT_GROUPED_INLINE"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
+  static const int inline_env = (int)knob("XSMM_SMMJIT_GROUPED_INLINE", 1);
   const bool inlined = (all_mfma && 0 != inline_env);
   s += std::string("#define XENTRY_ATTR ") + (inlined ? "__forceinline__" : "__attribute__((noinline))") + "\n";
   // Hand-counted waits only in bodies inlined into a dispatcher without calls. A called body reads its DevAddr through a generic
@@ -2172,7 +2215,7 @@ std::string gen_smm_grouped_source(int typesize, const std::vector<GroupedBody>&
   // on the 27 CP2K shapes: 1.37 ms with four waves per work-group).
   // (two waves per SIMD: the bodies are called, not inlined; without the bound the kernel is given the registers of the
   // hungriest body plus its own -- 308 for the 27 CP2K shapes in fp64 -- and one wave per SIMD)
-  static const int grouped_wpe_env = []() { const char* e = getenv("XSMM_SMMJIT_GROUPED_WPE"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }(); // developer knob: waves per SIMD the dispatcher is compiled for
+  static const int grouped_wpe_env = (int)knob("XSMM_SMMJIT_GROUPED_WPE", 0); // waves per SIMD the dispatcher is compiled for
   // (two waves per SIMD for either kind of body. The matrix-core bodies of 32 x 32 fp64 keep ~155 registers alive -- A fragments,
   // B's flat image, accumulators -- and would just fit three, but inlined next to 26 others they spill at that bound: 27 CP2K
   // shapes, 524 288 products, batch order: 0.80-0.81 ms per call with two waves per SIMD, 0.82 ms with three (1.00 ms when the
@@ -2212,7 +2255,7 @@ struct GroupedKeyHash {
 };
 std::unordered_map<GroupedKey, JitSlot, GroupedKeyHash> g_grouped_cache; // (guarded by g_smm_lock)
 
-// work-groups and LDS bytes one batch needs under a run-form body (the sizing of smm_jit_launch_variant)
+// work-groups and LDS bytes one batch needs under a run-form body (the sizing of smm_jit_geometry)
 void grouped_geometry(const SmmBatch& s, int variant, long long* blocks, size_t* lds)
 {
   if (0 != (variant & SMM_JIT_MFMA_RUNS)) *lds = smm_mfma_runs_lds(s.typesize, s.m, s.n, s.k, s.ldb);
@@ -2235,8 +2278,16 @@ bool smm_jit_grouped_eligible(const SmmBatch& s)
   return 0 != smm_jit_waves(s.typesize, s.m, s.n, s.k, s.flags, 1);
 }
 
-// All batches (same precision, each with its verdict slot in devflags) in one launch. -1: not available (the caller launches
-// them one by one).
+// The run form a batch of shared C gets (SYNC_RUNS, SYNC_DEVICE; alone or as a grouped body): a wave per run on the matrix
+// cores where that form serves, else the register-tiled wave form. deep: a grouped body of a batch split into tiles.
+static int smm_run_variant(const SmmBatch& s, bool deep)
+{
+  const int split = (0 != s.relaxed ? SMM_JIT_SPLIT : 0); // the caller's reference path is unordered as well: segments + atomics
+  if (smm_mfma_runs_ok(s)) return SMM_JIT_SCALAR | split | SMM_JIT_RUNS | SMM_JIT_MFMA_RUNS | (deep ? SMM_JIT_DEEP : 0);
+  return smm_jit_width_variant(s) | split | SMM_JIT_RUNS;
+}
+
+// All batches (same precision, each with its verdict slot in devflags) in one launch.
 namespace {
 struct GroupedEntry { int group, body; long long blocks; };
 struct GroupedPlan { GroupedKey key; std::vector<GroupedEntry> entries; size_t lds_max = 0; };
@@ -2246,12 +2297,11 @@ struct GroupedPlan { GroupedKey key; std::vector<GroupedEntry> entries; size_t l
 // 0.32 ms alone), 1.18 ms with all chains on the wave form.
 bool grouped_plan(const SmmBatch* groups, int ngroups, bool check_eligible, GroupedPlan& plan, bool tiles = false)
 { // tiles: the groups are the tiles of one batch of few runs (smm_tile_split)
-  plan.key.typesize = groups[0].typesize; plan.key.threads = (tiles && 0 != smm_tile_wg()) ? 64 * ngroups : 64; plan.key.bodies.clear(); plan.entries.clear(); plan.lds_max = 0;
+  plan.key.typesize = groups[0].typesize; plan.key.threads = (tiles && 2 == smm_tilesplit()) ? 64 * ngroups : 64; plan.key.bodies.clear(); plan.entries.clear(); plan.lds_max = 0;
   for (int g = 0; g < ngroups; ++g) {
     const SmmBatch& s = groups[g];
     if (s.typesize != groups[0].typesize || (check_eligible && !smm_jit_grouped_eligible(s))) return false;
-    const int variant = smm_mfma_runs_ok(s) ? (SMM_JIT_SCALAR | (0 != s.relaxed ? SMM_JIT_SPLIT : 0) | SMM_JIT_RUNS | SMM_JIT_MFMA_RUNS | (tiles ? SMM_JIT_DEEP : 0))
-                                            : (smm_jit_width_variant(s) | (0 != s.relaxed ? SMM_JIT_SPLIT : 0) | SMM_JIT_RUNS);
+    const int variant = smm_run_variant(s, tiles);
     const GroupedBody body = { s.m, s.n, s.k, s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B), variant, s.lda, s.ldb, s.ldc };
     size_t bi = 0;
     while (bi < plan.key.bodies.size() && !(plan.key.bodies[bi] == body)) ++bi;
@@ -2279,9 +2329,40 @@ bool grouped_plan(const SmmBatch* groups, int ngroups, bool check_eligible, Grou
   return true;
 }
 
-JitKernel* grouped_kernel(const GroupedKey& key)
+// the grouped kernel of these batches (nullptr: not available -- the caller launches them one by one)
+JitKernel* grouped_resolve(const SmmBatch* groups, int ngroups, bool check_eligible, bool tiles, GroupedPlan& plan)
 {
+  if (ngroups < 1 || !grouped_plan(groups, ngroups, check_eligible, plan, tiles) || plan.lds_max > 65536) return nullptr;
+  const GroupedKey& key = plan.key;
   return jit_resolve(g_grouped_cache, key, "xsmm_smm_grouped", false, [&key]() { return gen_smm_grouped_source(key.typesize, key.bodies, key.threads); });
+}
+
+int grouped_launch(const SmmBatch* groups, const GroupedPlan& plan, JitKernel* kern, void* stream)
+{
+  struct GroupEntryH { DevAddrH ad; long long batch; unsigned block_begin, nblocks; int body, pad; };
+  struct GroupTabH { GroupEntryH e[GROUPED_BYVAL]; };
+  static_assert(sizeof(GroupTabH) + 16 <= 4096, "kernel arguments of a launch");
+  if (plan.entries.size() > (size_t)GROUPED_BYVAL) return -1; // (never: the callers fuse at most 32 batches per launch)
+  GroupTabH tab; // (a kernel argument: see gen_smm_grouped_source)
+  memset(&tab, 0, sizeof(tab));
+  int nentries = (int)plan.entries.size();
+  unsigned total = 0;
+  for (int i = 0; i < nentries; ++i) {
+    const SmmBatch& s = groups[plan.entries[(size_t)i].group];
+    GroupEntryH& t = tab.e[i];
+    t.ad = dev_addr(s);
+    t.batch = s.batch; t.block_begin = total; t.nblocks = (unsigned)plan.entries[(size_t)i].blocks; t.body = plan.entries[(size_t)i].body;
+    total += t.nblocks;
+  }
+  size_t lds_bytes = plan.lds_max;
+  if (plan.key.threads > 64) { // a work-group per chunk of 64 items, a wave per tile
+    const size_t per_wave = (plan.lds_max + 15) / 16 * 16;
+    total = tab.e[0].nblocks;
+    for (int i = 0; i < nentries; ++i) { tab.e[i].block_begin = 0; tab.e[i].nblocks = total; tab.e[i].pad = (int)per_wave; }
+    lds_bytes = per_wave * (size_t)nentries;
+  }
+  void* args[] = { (void*)&tab, &nentries };
+  return jit_launch_dyn(kern, total, (unsigned)plan.key.threads, (unsigned)lds_bytes, args, stream);
 }
 }
 
@@ -2293,256 +2374,13 @@ std::string gen_smm_grouped_source_for(const SmmBatch* groups, int ngroups, bool
   return gen_smm_grouped_source(plan.key.typesize, plan.key.bodies, plan.key.threads);
 }
 
-static int launch_smm_jit_grouped_checked(const SmmBatch* groups, int ngroups, bool check_eligible, void* stream, const char** name);
 int launch_smm_jit_grouped(const SmmBatch* groups, int ngroups, void* stream, const char** name)
-{
-  return launch_smm_jit_grouped_checked(groups, ngroups, true, stream, name);
-}
-
-static int launch_smm_jit_grouped_checked(const SmmBatch* groups, int ngroups, bool check_eligible, void* stream, const char** name)
-{
-  if (ngroups < 1) return -1;
+{ // -1: not available (the caller launches the batches one by one)
   GroupedPlan plan;
-  if (!grouped_plan(groups, ngroups, check_eligible, plan, !check_eligible) || plan.lds_max > 65536) return -1;
-  JitKernel* const kern = grouped_kernel(plan.key);
+  JitKernel* const kern = grouped_resolve(groups, ngroups, true, false, plan);
   if (nullptr == kern) return -1;
-  struct DevAddrH { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; };
-  struct GroupEntryH { DevAddrH ad; long long batch; unsigned block_begin, nblocks; int body, pad; };
   *name = (8 == groups[0].typesize) ? "smm_f64_jit_shape_runs_grouped" : "smm_f32_jit_shape_runs_grouped";
-  std::vector<GroupEntryH> tab(plan.entries.size());
-  unsigned total = 0;
-  for (size_t i = 0; i < plan.entries.size(); ++i) {
-    const SmmBatch& s = groups[plan.entries[i].group];
-    GroupEntryH& t = tab[i]; memset(&t, 0, sizeof(t));
-    t.ad.a = (const char*)s.a; t.ad.b = (const char*)s.b; t.ad.c = (char*)s.c; t.ad.ia = (const char*)s.ia; t.ad.ib = (const char*)s.ib; t.ad.ic = (const char*)s.ic;
-    t.ad.sa = s.sa; t.ad.sb = s.sb; t.ad.sc = s.sc; t.ad.index_base = s.index_base; t.ad.index_stride = s.index_stride; t.ad.mode = s.mode;
-    t.ad.flags = s.devflags;
-    t.batch = s.batch; t.block_begin = total; t.nblocks = (unsigned)plan.entries[i].blocks; t.body = plan.entries[i].body;
-    total += t.nblocks;
-  }
-  size_t lds_bytes = plan.lds_max;
-  if (plan.key.threads > 64) { // a work-group per chunk of 64 items, a wave per tile
-    const size_t per_wave = (plan.lds_max + 15) / 16 * 16;
-    total = tab[0].nblocks;
-    for (GroupEntryH& t : tab) { t.block_begin = 0; t.nblocks = total; t.pad = (int)per_wave; }
-    lds_bytes = per_wave * tab.size();
-  }
-  struct GroupTabH { GroupEntryH e[GROUPED_BYVAL]; };
-  static_assert(sizeof(GroupTabH) + 16 <= 4096, "kernel arguments of a launch");
-  int nentries = (int)tab.size();
-  if (tab.size() > (size_t)GROUPED_BYVAL) return -1; // (never: the callers fuse at most 32 batches per launch)
-  GroupTabH byval; // (a kernel argument: see gen_smm_grouped_source)
-  memcpy(&byval, tab.data(), tab.size() * sizeof(GroupEntryH));
-  void* args[] = { (void*)&byval, &nentries };
-  return jit_launch_dyn(kern, total, (unsigned)plan.key.threads, (unsigned)lds_bytes, args, stream);
-}
-
-// Matrix-core work-group kernels (32 < max(M, N) <= 64, K <= 64; independent items, or runs of a uniform length) with the
-// descriptor baked in. -1: not applicable / not ready (the pre-compiled kernel of the same plan serves: launch_smm_special).
-int launch_smm_jit_mfma(const SmmBatch& s, void* stream, const char** name)
-{
-  const char* const env_jit = getenv("LIBXSMM_AMD_JIT");
-  if (nullptr != env_jit && 0 == atoi(env_jit)) return -1;
-  static const int on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
-  if (0 == on || 0 == s.use_mfma || 0 != s.general || 0 != s.lowp) return -1;
-  static const int wave_min = []() { const char* e = getenv("XSMM_SMMJIT_WAVE_MIN"); return (nullptr != e && 0 != *e) ? atoi(e) : 32; }(); // developer knob: the wave form below 33
-  const bool transb = (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)); // (B^T in memory: served by the one-wave-per-item form only)
-  if (!((wave_min < s.m || wave_min < s.n) && s.m <= 64 && s.n <= 64 && 0 < s.k && s.k <= 64 && s.lda >= s.m && s.ldb >= (transb ? s.n : s.k) && s.ldc >= s.m)) return -1;
-  if (4 == s.typesize && 64 == s.m && 64 == s.n && 64 == s.k && 64 == s.lda && 64 == s.ldb && 64 == s.ldc && SYNC_NONE == s.sync) return -1; // the hand-tuned tight 64^3 kernel
-  long long units = 0; int runlen = 1;
-  if (SYNC_NONE == s.sync) units = s.batch;
-  else if (SYNC_RUNS == s.sync && 0 < s.uniform_run && 0 == s.batch % s.uniform_run) { units = s.batch / s.uniform_run; runlen = (int)s.uniform_run; }
-  if (units < 1) return -1;
-  const char* const env_min = getenv("LIBXSMM_AMD_JIT_MINBATCH");
-  if (s.batch < ((nullptr != env_min && 0 != *env_min) ? atoll(env_min) : 16LL) && 0 == s.jit_always) return -1;
-  const bool f64 = (8 == s.typesize);
-  { // one wave per item: independent items of a strided batch, tight and 16-byte aligned operands, at least four waves per CU
-    static const int wave_on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_WAVE"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
-    // 16-byte chunks for strided batches of suitably shaped and aligned items, else element by element (any shape, index and
-    // pointer batches: the kernel resolves the addresses like every other batch kernel)
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)
-                         | (uintptr_t)(s.sa * s.typesize) | (uintptr_t)(s.sb * s.typesize) | (uintptr_t)(s.sc * s.typesize);
-    const int chunk = 16 / s.typesize;
-    const int bdim = transb ? s.n : s.k, bcnt = transb ? s.k : s.n; // B in memory: bcnt columns of bdim elements at a distance of ldb
-    const bool tight_ld = (s.lda == s.m && s.ldb == bdim && s.ldc == s.m);
-    const bool wide = (tight_ld && ADDR_STRIDED == s.mode && 0 == (bits & 15) && 0 == s.m % chunk && 0 == s.k % 4 && (!transb || 0 == s.n % chunk));
-    const size_t wlds = smm_mfma_wave_lds(s.typesize, s.m, s.n, s.k, wide ? chunk : 1, transb);
-    // gaps in the leading dimensions: the element-wise build fetches the spans and drops the gaps (up to half as much again)
-    // -- where the spans are short: with more than ~80 elements per lane in flight the work-group form is the faster one
-    // (tools/bench_gaps.py: 43x9x27 ld 48/32/48 55.9 vs 51.4 %, 40x64x17 ld 40/17/44 48.6 vs 40.5 %, but 48^3 ld 56 28.8 vs 56.8 %)
-    const long long span_loads = ((long long)s.lda * (s.k - 1) + s.m + 63) / 64 + ((long long)s.ldb * (bcnt - 1) + bdim + 63) / 64 + ((long long)s.ldc * (s.n - 1) + s.m + 63) / 64;
-    const bool gaps_ok = tight_ld || (2 * s.lda <= 3 * s.m && 2 * s.ldb <= 3 * bdim && 2 * s.ldc <= 3 * s.m && span_loads <= 80);
-    if (0 != wave_on && 0 != wlds && 4 * wlds <= 160u * 1024u && SYNC_NONE == s.sync && gaps_ok)
-    {
-      const SmmKey wkey = { s.typesize, s.m, s.n, s.k, s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B), SMM_JIT_MFMA_WAVE | (wide ? 0 : SMM_JIT_SCALAR), s.lda, s.ldb, s.ldc };
-      JitKernel* const wk = smm_jit_get(wkey);
-      if (nullptr != wk) {
-        struct { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; } wad;
-        wad.a = (const char*)s.a; wad.b = (const char*)s.b; wad.c = (char*)s.c; wad.ia = (const char*)s.ia; wad.ib = (const char*)s.ib; wad.ic = (const char*)s.ic;
-        wad.sa = s.sa; wad.sb = s.sb; wad.sc = s.sc; wad.index_base = s.index_base; wad.index_stride = s.index_stride; wad.mode = s.mode; wad.flags = nullptr;
-        long long wbatch = s.batch; int one = 1;
-        int per_cu = (int)((160u * 1024u) / wlds);
-        const int by_regs = 4 * smm_mfma_wave_wpe(wlds, s.typesize, s.m, s.n, s.k, wide ? chunk : 1, s.lda, s.ldb, s.ldc);
-        if (per_cu > by_regs) per_cu = by_regs;
-        { // The memory system is at its best with ~100 KB of operands in flight per CU (the fp32 32^3 kernel: twelve waves of 12 KB); a wave
-          // here has a whole item of 19-55 KB in flight. Waves per CU, % of the HBM peak (tools/bench_dense.py, XSMM_SMMJIT_WAVE_PERCU sweep):
-          // f32 40^3 3: 71.8, 4: 73.8, 8: 67.9, 12: 67.5 | f64 40^3 3: 72.2, 4: 69.3, 8: 69.0 | f32 48^3 3: 72.9, 4: 70.3, 8: 68.3 |
-          // f64 48^3 3: 68.8, 8: 69.1, 12: 69.7 | f32 56^3 3: 69.8, 4: 68.6, 8: 67.6; five to seven waves (uneven over the four SIMDs) lose 3-15 points.
-          const size_t item_bytes = (size_t)s.typesize * ((size_t)s.lda * s.k + (size_t)s.ldb * bcnt + (size_t)s.ldc * s.n);
-          if (wide && item_bytes >= 16384) { const int fit = (int)(100u * 1024u / item_bytes); per_cu = (fit >= 4) ? 4 : 3; if (per_cu > by_regs) per_cu = by_regs; }
-          const char* const e = getenv("XSMM_SMMJIT_WAVE_PERCU"); if (nullptr != e && 0 < atoi(e)) per_cu = atoi(e); // developer knob
-        }
-        long long wblocks = 256LL * per_cu;
-        if (wblocks > s.batch) wblocks = s.batch;
-        void* wargs[] = { &wad, &wbatch, &one };
-        *name = f64 ? "smm_f64_mfma_wave_jit" : "smm_f32_mfma_wave_jit";
-        return jit_launch_dyn(wk, (unsigned)wblocks, 64u, (unsigned)wlds, wargs, stream);
-      }
-    }
-  }
-  if (transb) return -1; // (the forms below read B as stored column by column)
-  { // fp64 items too large for that: the two-halves form where it leaves room for four waves per CU (56^3: 66 % against 54-58 % on the
-    // work-group form; 64 x 64 x K stays on the work-group form, which is the faster one there -- tools/probe/mfma_wave.hip)
-    static const int wave_on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_WAVE"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-    const size_t wlds = f64 ? smm_mfma_wave2_lds(s.typesize, s.m, s.n, s.k) : 0;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)
-                         | (uintptr_t)(s.sa * s.typesize) | (uintptr_t)(s.sb * s.typesize) | (uintptr_t)(s.sc * s.typesize);
-    if (0 != wave_on && 0 != wlds && 4 * wlds <= 160u * 1024u && !(64 == s.m && 64 == s.n) && SYNC_NONE == s.sync && ADDR_STRIDED == s.mode && 0 == (bits & 15)
-      && s.lda == s.m && s.ldb == s.k && s.ldc == s.m)
-    {
-      const SmmKey wkey = { s.typesize, s.m, s.n, s.k, s.flags & LIBXSMM_GEMM_FLAG_BETA_0, SMM_JIT_MFMA_WAVE2, s.lda, s.ldb, s.ldc };
-      JitKernel* const wk = smm_jit_get(wkey);
-      if (nullptr != wk) {
-        struct { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; } wad;
-        wad.a = (const char*)s.a; wad.b = (const char*)s.b; wad.c = (char*)s.c; wad.ia = wad.ib = wad.ic = nullptr;
-        wad.sa = s.sa; wad.sb = s.sb; wad.sc = s.sc; wad.index_base = 0; wad.index_stride = 0; wad.mode = 0; wad.flags = nullptr;
-        long long wbatch = s.batch; int one = 1;
-        long long wblocks = 256LL * 4;
-        if (wblocks > s.batch) wblocks = s.batch;
-        void* wargs[] = { &wad, &wbatch, &one };
-        *name = "smm_f64_mfma_wave2_jit";
-        return jit_launch_dyn(wk, (unsigned)wblocks, 64u, (unsigned)wlds, wargs, stream);
-      }
-    }
-  }
-  if (!(32 < s.m || 32 < s.n)) return -1; // (the work-group forms below are for shapes beyond 32)
-  const bool tight = !f64 && s.lda == s.m && s.ldb == s.k && 0 == ((s.m * s.k) & 3) && 0 == ((s.k * s.n) & 3);
-  static const int tightc_on = []() { const char* e = getenv("XSMM_SMM64_TIGHTC"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-  const bool tightc = !f64 && s.ldc == s.m && 0 == ((s.m * s.n) & 3) && 0 != (s.m & 31) && 0 != tightc_on;
-  const int variant = SMM_JIT_MFMA | (tight ? SMM_JIT_MFMA_TIGHT : 0) | (tightc ? SMM_JIT_MFMA_TIGHTC : 0);
-  const SmmKey key = { s.typesize, s.m, s.n, s.k, s.flags & LIBXSMM_GEMM_FLAG_BETA_0, variant, s.lda, s.ldb, s.ldc };
-  JitKernel* const k = smm_jit_get(key);
-  if (nullptr == k) return -1;
-  struct { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; } ad;
-  ad.a = (const char*)s.a; ad.b = (const char*)s.b; ad.c = (char*)s.c; ad.ia = (const char*)s.ia; ad.ib = (const char*)s.ib; ad.ic = (const char*)s.ic;
-  ad.sa = s.sa; ad.sb = s.sb; ad.sc = s.sc; ad.index_base = s.index_base; ad.index_stride = s.index_stride; ad.mode = s.mode; ad.flags = nullptr;
-  long long batch = s.batch;
-  size_t lds = 0; int fit = (tightc ? 3 : 4); // (48 KiB of LDS with the C image: three work-groups per CU)
-  if (f64) { // (the sizes of the pre-compiled launch, kernels/smm_special.hip)
-    lds = (s.k > 32) ? (size_t)2 * 32 * 64 * sizeof(double) : (size_t)2 * (4 * ((s.k + 3) / 4)) * 64 * sizeof(double);
-    fit = (int)((160u * 1024u) / lds); if (fit > 3) fit = 3; if (fit < 1) fit = 1;
-  }
-  static const int bpc_env = []() { const char* e = getenv("XSMM_SMM64_BPC"); return (nullptr != e && 0 != *e) ? atoi(e) : 0; }();
-  long long blocks = units;
-  const long long resident = 256LL * (0 < bpc_env ? bpc_env : fit);
-  if (blocks > resident) blocks = resident;
-  void* args[] = { &ad, &batch, &runlen };
-  *name = f64 ? (1 == runlen ? "smm_f64_mfma_wg_jit" : "smm_f64_mfma_wg_runs_jit") : (1 == runlen ? "smm_f32_mfma_wg_jit" : "smm_f32_mfma_wg_runs_jit");
-  return jit_launch_dyn(k, (unsigned)blocks, 256u, (unsigned)lds, args, stream);
-}
-
-// 16-bit inputs (args.lowp 1: i16 -> i32, 3: bf16 -> f32): strided batches of tightly packed items with independent C go through
-// the streaming form of the specialised kernel (the inputs are widened on their way into LDS). -1: not applicable.
-int launch_smm_jit_lowp(const SmmBatch& s, void* stream, const char** name)
-{
-  const char* const env_jit = getenv("LIBXSMM_AMD_JIT");
-  if (nullptr != env_jit && 0 == atoi(env_jit)) return -1;
-  if ((1 != s.lowp && 3 != s.lowp && 4 != s.lowp) || 0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)) return -1;
-  if (4 == s.lowp && 0 != (s.m & 1)) return -1;
-  const bool strided = (ADDR_STRIDED == s.mode); // (index and pointer batches: the streaming form with element-wide -- one k pair -- accesses, below)
-  { // bf16 inputs beyond 32: the one-wave-per-item matrix-core kernel (fp32 instruction on the widened operands: the gold
-    // loop's product-then-add bit for bit)
-    static const int wave_on = []() { const char* e = getenv("XSMM_SMMJIT_MFMA_WAVE"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-    static const int wave_min = []() { const char* e = getenv("XSMM_SMMJIT_LOWP_WAVE_MIN"); return (nullptr != e && 0 != *e) ? atoi(e) : 31; }(); // developer knob (32^3: 73.8 vs 67.9 % for the fp32 result, 67.9 vs 49.5 % for bf16; 16^3 is better off on the streaming form)
-    const size_t wlds = smm_mfma_wave_lds(4, s.m, s.n, s.k);
-    const uintptr_t bits = strided ? (reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)
-                         | (uintptr_t)(s.sa * 2) | (uintptr_t)(s.sb * 2) | (uintptr_t)(s.sc * (4 == s.lowp ? 2 : 4))) : 0;
-    const char* const env_min = getenv("LIBXSMM_AMD_JIT_MINBATCH");
-    // (index and pointer batches as well: their items are whole numbers of 16-byte chunks long -- M % 4 == 0, K % 8 == 0 -- so callers
-    // that lay items out back to back keep the chunks aligned; an item that does not start on 16 bytes costs speed, not correctness)
-    if (0 != wave_on && 0 != s.use_mfma && (3 == s.lowp || 4 == s.lowp) && (wave_min < s.m || wave_min < s.n) && 0 != wlds && 4 * wlds <= 160u * 1024u
-      && 0 == (s.k & 7) && (3 == s.lowp || 0 == (s.m & 7)) && 0 == (bits & 15) && s.lda == s.m && s.ldb == s.k && s.ldc == s.m
-      && s.batch >= ((nullptr != env_min && 0 != *env_min) ? atoll(env_min) : 16LL))
-    {
-      const SmmKey wkey = { 4, s.m, s.n, s.k, s.flags & LIBXSMM_GEMM_FLAG_BETA_0, SMM_JIT_MFMA_WAVE | ((4 == s.lowp ? 2 : 3) << 11), s.lda, s.ldb, s.ldc };
-      JitKernel* const wk = smm_jit_get(wkey);
-      if (nullptr != wk) {
-        struct { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; } wad;
-        wad.a = (const char*)s.a; wad.b = (const char*)s.b; wad.c = (char*)s.c; wad.ia = (const char*)s.ia; wad.ib = (const char*)s.ib; wad.ic = (const char*)s.ic;
-        wad.sa = s.sa; wad.sb = s.sb; wad.sc = s.sc; // (in elements of the operands' types, as the kernel counts them)
-        wad.index_base = s.index_base; wad.index_stride = s.index_stride; wad.mode = s.mode; wad.flags = nullptr;
-        long long wbatch = s.batch; int one = 1;
-        int per_cu = (int)((160u * 1024u) / wlds);
-        const int by_regs = 4 * smm_mfma_wave_wpe(wlds);
-        if (per_cu > by_regs) per_cu = by_regs;
-        { // Eight waves per CU (tools/bench_dense.py lowp, XSMM_SMMJIT_WAVE_PERCU sweep, % of the HBM peak at 8 / as many as LDS and
-          // registers allow: bf16 -> f32 48^3 70.5 / 67.4, 64^3 74.4 / 67.7; bf16 -> bf16 32^3 73.5 / 67.6, 48^3 73.5 / 62.5, 64^3 60.3 / 54.7;
-          // three or four -- the optimum of the fp32 / fp64 wave kernels -- lose 5-30 points here: the widening and rounding work per item
-          // wants more waves to overlap with)
-          // (eight per CU also where the estimate above says fewer fit: whatever is not resident at once starts as the others finish)
-          per_cu = 8;
-          const char* const e = getenv("XSMM_SMMJIT_WAVE_PERCU"); if (nullptr != e && 0 < atoi(e)) per_cu = atoi(e); // developer knob
-        }
-        long long wblocks = 256LL * per_cu;
-        if (wblocks > s.batch) wblocks = s.batch;
-        void* wargs[] = { &wad, &wbatch, &one };
-        *name = (4 == s.lowp) ? "smm_bf16_mfma_wave_jit_lowp" : "smm_bf16f32_mfma_wave_jit_lowp";
-        return jit_launch_dyn(wk, (unsigned)wblocks, 64u, (unsigned)wlds, wargs, stream);
-      }
-    }
-  }
-  // (i16 -> i32 has no matrix-core form: beyond 32 the same streaming kernel with a larger tile per lane -- 48^3 18 -> 57 %,
-  // 64^3 16 -> 56 % of the HBM peak; XSMM_SMMJIT_LOWP_BIG=0: the pre-compiled kernel)
-  static const int big_i16 = []() { const char* e = getenv("XSMM_SMMJIT_LOWP_BIG"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-  const int lim = (0 != big_i16) ? 64 : 32; // (bf16 shapes the matrix-core form above does not take -- M or K not a multiple of 4 / 8 -- come here as well)
-  if (s.m > lim || s.n > lim || s.k > 64 || 0 != (s.k & 1) || s.lda != s.m || s.ldb != s.k || s.ldc != s.m) return -1;
-  // strided batches of items laid out back to back take 16-byte accesses; every other batch (other strides, index arrays -- in
-  // elements of 16 bits, as the reference's libxsmm_mmbatch_kernel counts them --, arrays of pointers) one k pair per access
-  const bool back_to_back = strided && s.sa == (long long)s.m * s.k && s.sb == (long long)s.k * s.n && s.sc == (long long)s.m * s.n;
-  const char* const env_min = getenv("LIBXSMM_AMD_JIT_MINBATCH");
-  if (s.batch < ((nullptr != env_min && 0 != *env_min) ? atoll(env_min) : 16LL)) return -1;
-  if (0 == smm_jit_waves(4, s.m, s.n, s.k, s.flags)) return -1;
-  SmmBatch j = s;
-  j.typesize = 4; j.lowp = 0; j.sync = SYNC_NONE; // (the kernel itself addresses A and B -- and a bf16 C -- in elements of 16 bits)
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c);
-  const int lowp_bits = ((4 == s.lowp ? 2 : s.lowp) << 11); // XLOWP: 1 i16 -> i32, 2 bf16 -> bf16, 3 bf16 -> f32
-  const bool wide = (back_to_back && 0 == (bits & 15));
-  const int variant = (wide ? 0 : SMM_JIT_SCALAR) | lowp_bits;
-  *name = (1 == s.lowp) ? "smm_i16i32_jit_shape_lowp" : (4 == s.lowp ? "smm_bf16_jit_shape_lowp" : "smm_bf16f32_jit_shape_lowp");
-  if (wide) { // small items laid out back to back: several per wave and pass, as the fp32 / fp64 streaming form takes them (a 16^3 item is
-    // 1.5-2 KB: one per wave leaves most lanes of every access idle and the kernel bound by its instruction count per item)
-    const char* const pack_e = getenv("XSMM_SMMJIT_LOWP_PACK"); // developer knob (re-read on every call: the tests sweep it)
-    const int pack_env = (nullptr != pack_e && 0 != *pack_e) ? atoi(pack_e) : 0;
-    const size_t item = 2 * ((size_t)s.m * s.k + (size_t)s.k * s.n) + (size_t)(4 == s.lowp ? 2 : 4) * s.m * s.n;
-    int pack = 1;
-    if (0 < pack_env) pack = pack_env;
-    else if (item < 6000) while (pack < 8 && 2 * pack * item <= 16384) pack *= 2;
-    while (0 != (pack & (pack - 1))) --pack;
-    while (1 < pack && ((size_t)pack * 4 * ((size_t)s.m * s.k + (size_t)s.k * s.n + (size_t)s.m * s.n) > 28672 || 0 == smm_jit_waves(4, s.m, s.n, s.k, s.flags, pack))) pack /= 2;
-    if (1 < pack && s.batch >= pack) {
-      const int e = smm_jit_launch_variant(j, variant | smm_jit_pack_bits(pack), stream);
-      if (0 == e) {
-        const long long done = (s.batch / pack) * pack;
-        if (done == s.batch) return 0;
-        SmmBatch rest = j; // (strides in elements of the operands: 16 bits, C of the result's width)
-        rest.a = (const char*)s.a + done * s.sa * 2; rest.b = (const char*)s.b + done * s.sb * 2;
-        rest.c = (char*)s.c + done * s.sc * (4 == s.lowp ? 2 : 4); rest.batch = s.batch - done;
-        return smm_jit_launch_variant(rest, variant, stream);
-      }
-      if (0 < e) return e; // (< 0: the packed flavour is not available -- one item per wave)
-    }
-  }
-  return smm_jit_launch_variant(j, variant, stream);
+  return grouped_launch(groups, plan, kern, stream);
 }
 
 // A batch of few runs whose C has several 16 x 16 tiles (one call per CP2K stack: 19 418 products of 32^3 are 172 runs -- 172 waves on
@@ -2553,11 +2391,9 @@ int launch_smm_jit_lowp(const SmmBatch& s, void* stream, const char** name)
 // Returns the number of tile batches written to out[<= 4] (0: not split).
 static int smm_tile_split(const SmmBatch& s, SmmBatch* out)
 {
-  const char* const on_env = getenv("XSMM_SMMJIT_TILESPLIT"); // developer knob (re-read on every call: the tests toggle it)
-  const int on = (nullptr != on_env && 0 != *on_env) ? atoi(on_env) : 1;
-  static const int max_waves = []() { const char* e = getenv("XSMM_SMMJIT_TILESPLIT_WAVES"); return (nullptr != e && 0 != *e) ? atoi(e) : 1280; }(); // developer knob
+  static const int max_waves = (int)knob("XSMM_SMMJIT_TILESPLIT_WAVES", 1280);
   const int mi = (s.m + 15) / 16, ni = (s.n + 15) / 16;
-  if (0 == on || mi * ni < 2 || mi * ni > 4 || SYNC_DEVICE != s.sync || (ADDR_STRIDED != s.mode && ADDR_INDEX != s.mode)) return 0;
+  if (0 == smm_tilesplit() || mi * ni < 2 || mi * ni > 4 || SYNC_DEVICE != s.sync || (ADDR_STRIDED != s.mode && ADDR_INDEX != s.mode)) return 0;
   // Every tile's wave fetches its rows of A and its columns of B: twice the requests of a wave per product. Measured (tools/bench_tile_split.py,
   // profiles/r3_tile_split.txt; fp64 32^3, ms split / not split): 2 000 items 0.08-0.16 / 0.12-0.31, 8 000 items 0.08-0.16 / 0.12-0.31, 16 000 items
   // equal for runs up to 32 and 0.17 / 0.31 for runs of 256, 30 000 items 0.20-0.28 / 0.13-0.27 for runs up to 32 (0.19 / 0.31 for runs of
@@ -2581,132 +2417,299 @@ static int smm_tile_split(const SmmBatch& s, SmmBatch* out)
   return n;
 }
 
-int launch_smm_jit(const SmmBatch& s, void* stream, const char** name)
-{ // returns -1 when no specialised kernel is available
-  const int width = smm_jit_width_variant(s);
+// ---- which generated kernels a batch gets ------------------------------------------------------------------------------
+// A plan is the list of alternatives the launchers try, in order. An alternative is one or two launch parts -- a generated kernel
+// over a slice of the batch, launched in order once the kernels of all parts are ready -- or the tiles of C as one grouped launch.
+// run_smm tries the matrix-core tier before the hand-written kernels, the specialised tier after them.
+namespace {
+enum { SLICE_ALL, SLICE_PACKED, SLICE_REST };  // the whole batch; its groups of `pack` consecutive items; the items after them
+enum { TIER_MFMA, TIER_JIT };
+struct SmmPart { SmmKey key; int slice; };
+struct SmmAlt { int tier; const char* name; int nparts; SmmPart part[2]; int ntiles; SmmBatch tiles[4]; };
+struct SmmPlan {
+  SmmBatch batch;         // as the generated kernels see it (16-bit inputs: typesize 4, strides in elements of the inputs)
+  int ab_bytes, c_bytes;  // bytes per element of A and B, of C (where the remainder starts)
+  int pack;               // items per wave pass of the SLICE_PACKED part
+  int nalts; SmmAlt alts[8];
+};
+
+SmmAlt& plan_alt(SmmPlan& p, int tier, const char* name)
+{
+  SmmAlt& a = p.alts[p.nalts++];
+  a.tier = tier; a.name = name; a.nparts = 0; a.ntiles = 0;
+  return a;
+}
+void plan_part(const SmmPlan& p, SmmAlt& a, int variant, int slice)
+{
+  const SmmBatch& s = p.batch;
+  a.part[a.nparts++] = SmmPart{ SmmKey{ s.typesize, s.m, s.n, s.k, s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B), variant, s.lda, s.ldb, s.ldc }, slice };
+}
+void plan_add(SmmPlan& p, int tier, const char* name, int variant) { plan_part(p, plan_alt(p, tier, name), variant, SLICE_ALL); }
+// groups of `pack` consecutive items per wave pass (kernel `variant`), then the few items that are left (kernel `rest`)
+void plan_packed(SmmPlan& p, const char* name, int variant, int pack, int rest)
+{
+  SmmAlt& a = plan_alt(p, TIER_JIT, name);
+  p.pack = pack;
+  if (p.batch.batch >= pack) plan_part(p, a, variant | smm_jit_pack_bits(pack), SLICE_PACKED);
+  if (0 != p.batch.batch % pack) plan_part(p, a, rest, SLICE_REST);
+}
+
+// the matrix-core tier (32 < max(M, N) <= 64, K <= 64; independent items, or runs of a uniform length): the descriptor baked in
+void plan_mfma(const SmmBatch& s, SmmPlan& p)
+{
+  static const int on = (int)knob("XSMM_SMMJIT_MFMA", 1);
+  static const int wave_min = (int)knob("XSMM_SMMJIT_WAVE_MIN", 32); // the wave form below 33
+  static const int wave_on = (int)knob("XSMM_SMMJIT_MFMA_WAVE", 1);
+  static const int tightc_on = (int)knob("XSMM_SMM64_TIGHTC", 1);
+  if (0 == on || 0 == s.use_mfma || 0 != s.general || 0 != s.lowp) return;
+  const bool transb = (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)); // (B^T in memory: served by the one-wave-per-item form only)
+  if (!((wave_min < s.m || wave_min < s.n) && s.m <= 64 && s.n <= 64 && 0 < s.k && s.k <= 64 && s.lda >= s.m && s.ldb >= (transb ? s.n : s.k) && s.ldc >= s.m)) return;
+  if (4 == s.typesize && 64 == s.m && 64 == s.n && 64 == s.k && 64 == s.lda && 64 == s.ldb && 64 == s.ldc && SYNC_NONE == s.sync) return; // the hand-tuned tight 64^3 kernel
+  const bool runs = (SYNC_RUNS == s.sync && 0 < s.uniform_run && 0 == s.batch % s.uniform_run);
+  if (!(SYNC_NONE == s.sync || runs) || (runs ? s.batch / s.uniform_run : s.batch) < 1) return;
+  if (s.batch < smm_jit_min_batch() && 0 == s.jit_always) return;
   const bool f64 = (8 == s.typesize);
-  if (s.m <= 32 && s.n <= 32 && s.k > 64 && smm_mfma_stream_ok(s)) { // long K, small M and N, every item its own C: K in chunks on the matrix cores
-    const int e = smm_jit_launch_variant(s, SMM_JIT_SCALAR | SMM_JIT_MFMA_RUNS, stream);
-    if (0 <= e) { *name = f64 ? "smm_f64_mfma_stream_jit" : "smm_f32_mfma_stream_jit"; return e; }
+  // 16-byte chunks for strided batches of suitably shaped and aligned items, else element by element (any shape, index and
+  // pointer batches: the kernel resolves the addresses like every other batch kernel)
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)
+                       | (uintptr_t)(s.sa * s.typesize) | (uintptr_t)(s.sb * s.typesize) | (uintptr_t)(s.sc * s.typesize);
+  { // one wave per item: independent items, at least four waves per CU
+    const int chunk = 16 / s.typesize;
+    const int bdim = transb ? s.n : s.k, bcnt = transb ? s.k : s.n; // B in memory: bcnt columns of bdim elements at a distance of ldb
+    const bool tight_ld = (s.lda == s.m && s.ldb == bdim && s.ldc == s.m);
+    const bool wide = (tight_ld && ADDR_STRIDED == s.mode && 0 == (bits & 15) && 0 == s.m % chunk && 0 == s.k % 4 && (!transb || 0 == s.n % chunk));
+    const size_t wlds = smm_mfma_wave_lds(s.typesize, s.m, s.n, s.k, wide ? chunk : 1, transb);
+    // gaps in the leading dimensions: the element-wise build fetches the spans and drops the gaps (up to half as much again)
+    // -- where the spans are short: with more than ~80 elements per lane in flight the work-group form is the faster one
+    // (tools/bench_gaps.py: 43x9x27 ld 48/32/48 55.9 vs 51.4 %, 40x64x17 ld 40/17/44 48.6 vs 40.5 %, but 48^3 ld 56 28.8 vs 56.8 %)
+    const long long span_loads = ((long long)s.lda * (s.k - 1) + s.m + 63) / 64 + ((long long)s.ldb * (bcnt - 1) + bdim + 63) / 64 + ((long long)s.ldc * (s.n - 1) + s.m + 63) / 64;
+    const bool gaps_ok = tight_ld || (2 * s.lda <= 3 * s.m && 2 * s.ldb <= 3 * bdim && 2 * s.ldc <= 3 * s.m && span_loads <= 80);
+    if (0 != wave_on && 0 != wlds && 4 * wlds <= 160u * 1024u && SYNC_NONE == s.sync && gaps_ok)
+      plan_add(p, TIER_MFMA, f64 ? "smm_f64_mfma_wave_jit" : "smm_f32_mfma_wave_jit", SMM_JIT_MFMA_WAVE | (wide ? 0 : SMM_JIT_SCALAR));
   }
+  if (transb) return; // (the forms below read B as stored column by column)
+  // fp64 items too large for that: the two-halves form where it leaves room for four waves per CU (56^3: 66 % against 54-58 % on the
+  // work-group form; 64 x 64 x K stays on the work-group form, which is the faster one there -- tools/probe/mfma_wave.hip)
+  const size_t w2lds = f64 ? smm_mfma_wave2_lds(s.typesize, s.m, s.n, s.k) : 0;
+  if (0 != wave_on && 0 != w2lds && 4 * w2lds <= 160u * 1024u && !(64 == s.m && 64 == s.n) && SYNC_NONE == s.sync && ADDR_STRIDED == s.mode && 0 == (bits & 15)
+    && s.lda == s.m && s.ldb == s.k && s.ldc == s.m) plan_add(p, TIER_MFMA, "smm_f64_mfma_wave2_jit", SMM_JIT_MFMA_WAVE2);
+  if (!(32 < s.m || 32 < s.n)) return; // (the work-group forms below are for shapes beyond 32)
+  const bool tight = !f64 && s.lda == s.m && s.ldb == s.k && 0 == ((s.m * s.k) & 3) && 0 == ((s.k * s.n) & 3);
+  const bool tightc = !f64 && s.ldc == s.m && 0 == ((s.m * s.n) & 3) && 0 != (s.m & 31) && 0 != tightc_on;
+  plan_add(p, TIER_MFMA, f64 ? (runs ? "smm_f64_mfma_wg_runs_jit" : "smm_f64_mfma_wg_jit") : (runs ? "smm_f32_mfma_wg_runs_jit" : "smm_f32_mfma_wg_jit"),
+           SMM_JIT_MFMA | (tight ? SMM_JIT_MFMA_TIGHT : 0) | (tightc ? SMM_JIT_MFMA_TIGHTC : 0));
+}
+
+// 16-bit inputs (lowp 1: i16 -> i32, 3: bf16 -> f32, 4: bf16 -> bf16): tight items with independent C
+void plan_lowp(const SmmBatch& s, SmmPlan& p)
+{
+  static const int wave_on = (int)knob("XSMM_SMMJIT_MFMA_WAVE", 1);
+  static const int wave_min = (int)knob("XSMM_SMMJIT_LOWP_WAVE_MIN", 31); // (32^3: 73.8 vs 67.9 % for the fp32 result, 67.9 vs 49.5 % for bf16; 16^3 is better off on the streaming form)
+  static const int big_i16 = (int)knob("XSMM_SMMJIT_LOWP_BIG", 1);
+  if ((1 != s.lowp && 3 != s.lowp && 4 != s.lowp) || 0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) || (4 == s.lowp && 0 != (s.m & 1))) return;
+  p.batch.typesize = 4; p.batch.lowp = 0; p.batch.sync = SYNC_NONE; // (the kernel itself addresses A and B -- and a bf16 C -- in elements of 16 bits)
+  p.ab_bytes = 2; p.c_bytes = (4 == s.lowp ? 2 : 4);
+  const int lowp_bits = ((4 == s.lowp ? 2 : s.lowp) << 11); // XLOWP: 1 i16 -> i32, 2 bf16 -> bf16, 3 bf16 -> f32
+  const bool strided = (ADDR_STRIDED == s.mode); // (index and pointer batches: the streaming form with element-wide -- one k pair -- accesses)
+  const bool tight = (s.lda == s.m && s.ldb == s.k && s.ldc == s.m);
+  { // bf16 inputs beyond 32: the one-wave-per-item matrix-core kernel (fp32 instruction on the widened operands: the gold loop's
+    // product-then-add bit for bit). Index and pointer batches as well: their items are whole numbers of 16-byte chunks long -- M % 4 == 0,
+    // K % 8 == 0 -- so callers that lay items out back to back keep the chunks aligned; an item that does not start on 16 bytes costs speed
+    const size_t wlds = smm_mfma_wave_lds(4, s.m, s.n, s.k);
+    const uintptr_t bits = strided ? (reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)
+                         | (uintptr_t)(s.sa * 2) | (uintptr_t)(s.sb * 2) | (uintptr_t)(s.sc * p.c_bytes)) : 0;
+    if (0 != wave_on && 0 != s.use_mfma && 1 != s.lowp && (wave_min < s.m || wave_min < s.n) && 0 != wlds && 4 * wlds <= 160u * 1024u
+      && 0 == (s.k & 7) && (3 == s.lowp || 0 == (s.m & 7)) && 0 == (bits & 15) && tight && s.batch >= smm_jit_min_batch())
+      plan_add(p, TIER_JIT, (4 == s.lowp) ? "smm_bf16_mfma_wave_jit_lowp" : "smm_bf16f32_mfma_wave_jit_lowp", SMM_JIT_MFMA_WAVE | lowp_bits);
+  }
+  // (i16 -> i32 has no matrix-core form: beyond 32 the same streaming kernel with a larger tile per lane -- 48^3 18 -> 57 %,
+  // 64^3 16 -> 56 % of the HBM peak; XSMM_SMMJIT_LOWP_BIG=0: the pre-compiled kernel)
+  const int lim = (0 != big_i16) ? 64 : 32; // (bf16 shapes the matrix-core form above does not take -- M or K not a multiple of 4 / 8 -- come here as well)
+  if (s.m > lim || s.n > lim || s.k > 64 || 0 != (s.k & 1) || !tight || s.batch < smm_jit_min_batch() || 0 == smm_jit_waves(4, s.m, s.n, s.k, s.flags)) return;
+  // strided batches of items laid out back to back take 16-byte accesses; every other batch (other strides, index arrays -- in
+  // elements of 16 bits, as the reference's libxsmm_mmbatch_kernel counts them --, arrays of pointers) one k pair per access
+  const bool back_to_back = strided && s.sa == (long long)s.m * s.k && s.sb == (long long)s.k * s.n && s.sc == (long long)s.m * s.n;
+  const bool wide = (back_to_back && 0 == ((reinterpret_cast<uintptr_t>(s.a) | reinterpret_cast<uintptr_t>(s.b) | reinterpret_cast<uintptr_t>(s.c)) & 15));
+  const int variant = (wide ? 0 : SMM_JIT_SCALAR) | lowp_bits;
+  const char* const name = (1 == s.lowp) ? "smm_i16i32_jit_shape_lowp" : (4 == s.lowp ? "smm_bf16_jit_shape_lowp" : "smm_bf16f32_jit_shape_lowp");
+  if (wide) { // small items laid out back to back: several per wave and pass, as the fp32 / fp64 streaming form takes them (a 16^3 item is
+    // 1.5-2 KB: one per wave leaves most lanes of every access idle and the kernel bound by its instruction count per item)
+    const int pack_env = (int)knob("XSMM_SMMJIT_LOWP_PACK", 0); // (read on every call: the tests sweep it)
+    const size_t item = 2 * ((size_t)s.m * s.k + (size_t)s.k * s.n) + (size_t)p.c_bytes * s.m * s.n;
+    int pack = 1;
+    if (0 < pack_env) pack = pack_env;
+    else if (item < 6000) while (pack < 8 && 2 * pack * item <= 16384) pack *= 2;
+    while (0 != (pack & (pack - 1))) --pack;
+    while (1 < pack && ((size_t)pack * 4 * ((size_t)s.m * s.k + (size_t)s.k * s.n + (size_t)s.m * s.n) > 28672 || 0 == smm_jit_waves(4, s.m, s.n, s.k, s.flags, pack))) pack /= 2;
+    if (1 < pack && s.batch >= pack) plan_packed(p, name, variant, pack, variant);
+  }
+  plan_add(p, TIER_JIT, name, variant);
+}
+
+// the specialised tier (the batch has passed smm_jit_eligible)
+void plan_jit(const SmmBatch& s, SmmPlan& p)
+{
+  static const int wg_env = (int)knob("XSMM_SMMJIT_WG", 1);
+  const bool f64 = (8 == s.typesize);
+  const int width = smm_jit_width_variant(s);
+  if (s.m <= 32 && s.n <= 32 && s.k > 64 && smm_mfma_runs_ok(s, true)) // long K, small M and N, every item its own C: K in chunks on the matrix cores
+    plan_add(p, TIER_JIT, f64 ? "smm_f64_mfma_stream_jit" : "smm_f32_mfma_stream_jit", SMM_JIT_SCALAR | SMM_JIT_MFMA_RUNS);
   if (s.m > 32 || s.n > 32 || s.k > 64) { // (eligibility made sure of SYNC_NONE, or of runs of a uniform length)
-    if (0 == smm_jit_big_kc(s.typesize, s.m, s.n, s.k, s.flags) || (SYNC_NONE != s.sync && !(0 < s.uniform_run && 0 == s.batch % s.uniform_run))) return -1;
-    *name = f64 ? "smm_f64_jit_shape_wg" : "smm_f32_jit_shape_wg";
-    return smm_jit_launch_variant(s, SMM_JIT_BIG, stream);
+    if (0 != smm_jit_big_kc(s.typesize, s.m, s.n, s.k) && (SYNC_NONE == s.sync || (0 < s.uniform_run && 0 == s.batch % s.uniform_run)))
+      plan_add(p, TIER_JIT, f64 ? "smm_f64_jit_shape_wg" : "smm_f32_jit_shape_wg", SMM_JIT_BIG);
+    return;
   }
   if (SYNC_NONE == s.sync) { // every item owns its C
-    { // leading dimensions with gaps: the matrix-core run form addresses A's fragments and C through their leading dimensions (no
-      // gap element is requested) -- every item is a run of its own there
-      const char* const gaps_env = getenv("XSMM_SMMJIT_GAPS_MFMA"); // developer knob (re-read on every call: tests and tools toggle it): 0 off, 1 gaps only, 2 tight items too
-      // (tools/bench_generic.py, fraction of the HBM peak in algorithmic bytes, register-tiled streaming form -> this one: fp64 23^3 ld 24
-      // 54.1 -> 59.2 %, fp32 32^3 ld 40 42.3 -> 50.5 %, fp64 13^3 ld 16 44.1 -> 51.6 %; tight fp64 23^3 64.5 -> 61.5 %: tight items stay)
-      const int gaps_mfma = (nullptr != gaps_env && 0 != *gaps_env) ? atoi(gaps_env) : 1;
-      const bool tight_ld = (s.lda == s.m && s.ldc == s.m && s.ldb == s.k);
-      if (0 != gaps_mfma && (!tight_ld || 2 == gaps_mfma) && smm_mfma_runs_ok(s)) {
-        const int e = smm_jit_launch_variant(s, SMM_JIT_SCALAR | SMM_JIT_MFMA_RUNS, stream);
-        if (0 <= e) { *name = f64 ? "smm_f64_mfma_stream_jit" : "smm_f32_mfma_stream_jit"; return e; }
-      }
-    }
-    *name = f64 ? "smm_f64_jit_shape" : "smm_f32_jit_shape";
+    // leading dimensions with gaps: the matrix-core run form addresses A's fragments and C through their leading dimensions (no
+    // gap element is requested) -- every item is a run of its own there. XSMM_SMMJIT_GAPS_MFMA (read on every call: tests and tools
+    // toggle it): 0 off, 1 gaps only, 2 tight items too. (tools/bench_generic.py, fraction of the HBM peak in algorithmic bytes,
+    // register-tiled streaming form -> this one: fp64 23^3 ld 24 54.1 -> 59.2 %, fp32 32^3 ld 40 42.3 -> 50.5 %, fp64 13^3 ld 16
+    // 44.1 -> 51.6 %; tight fp64 23^3 64.5 -> 61.5 %: tight items stay)
+    const int gaps_mfma = (int)knob("XSMM_SMMJIT_GAPS_MFMA", 1);
+    const bool tight_ld = (s.lda == s.m && s.ldc == s.m && s.ldb == s.k);
+    if (0 != gaps_mfma && (!tight_ld || 2 == gaps_mfma) && smm_mfma_runs_ok(s))
+      plan_add(p, TIER_JIT, f64 ? "smm_f64_mfma_stream_jit" : "smm_f32_mfma_stream_jit", SMM_JIT_SCALAR | SMM_JIT_MFMA_RUNS);
+    const char* const name = f64 ? "smm_f64_jit_shape" : "smm_f32_jit_shape";
     const int pack = smm_jit_pack(s, width);
-    if (1 < pack) { // groups of `pack` consecutive items per wave, then the few items that are left
-      const int e = smm_jit_launch_variant(s, width | smm_jit_pack_bits(pack), stream);
-      if (0 == e) {
-        const long long done = (s.batch / pack) * pack;
-        if (done == s.batch) return 0;
-        SmmBatch rest = s;
-        rest.a = (const char*)s.a + done * s.sa * s.typesize; rest.b = (const char*)s.b + done * s.sb * s.typesize;
-        rest.c = (char*)s.c + done * s.sc * s.typesize; rest.batch = s.batch - done;
-        return smm_jit_launch_variant(rest, SMM_JIT_SCALAR, stream);
-      }
-      if (0 < e) return e; // (< 0: the packed flavour did not compile -- one item per wave)
-    }
-    return smm_jit_launch_variant(s, width, stream);
+    if (1 < pack) plan_packed(p, name, width, pack, SMM_JIT_SCALAR);
+    plan_add(p, TIER_JIT, name, width);
+    return;
   }
+  const char* const runs_name = f64 ? "smm_f64_jit_shape_runs" : "smm_f32_jit_shape_runs";
   if (smm_mfma_runs_ok(s)) { // shared C on the matrix cores: a wave per run (batch order; segments + atomics if the verdict or a relaxed order say so)
-    { SmmBatch tiles[4];
-      const int nt = smm_tile_split(s, tiles); // (at most four entries: the table is a kernel argument -- nothing staged, fine inside a stream capture)
-      if (1 < nt) {
-        const int e = launch_smm_jit_grouped_checked(tiles, nt, false, stream, name);
-        if (0 <= e) { *name = f64 ? "smm_f64_mfma_runs_tiles_jit" : "smm_f32_mfma_runs_tiles_jit"; return e; }
-      }
+    SmmBatch tiles[4];
+    const int nt = smm_tile_split(s, tiles); // (at most four entries: the table is a kernel argument -- nothing staged, fine inside a stream capture)
+    if (1 < nt) {
+      SmmAlt& a = plan_alt(p, TIER_JIT, f64 ? "smm_f64_mfma_runs_tiles_jit" : "smm_f32_mfma_runs_tiles_jit");
+      a.ntiles = nt; std::copy(tiles, tiles + nt, a.tiles);
     }
-    const int e = smm_jit_launch_variant(s, SMM_JIT_SCALAR | (0 != s.relaxed ? SMM_JIT_SPLIT : 0) | SMM_JIT_RUNS | SMM_JIT_MFMA_RUNS, stream);
-    if (0 <= e) { *name = f64 ? "smm_f64_mfma_runs_jit" : "smm_f32_mfma_runs_jit"; return e; }
+    plan_add(p, TIER_JIT, f64 ? "smm_f64_mfma_runs_jit" : "smm_f32_mfma_runs_jit", smm_run_variant(s, false));
   }
-  static const int wg_env = []() { const char* e = getenv("XSMM_SMMJIT_WG"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }(); // developer knob
   // the work-group form pays off once a product's operands are large (measured on CP2K stacks: 32^3 f64 yes, 23^3 no)
   const bool tight = (s.lda == s.m && s.ldc == s.m && (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (s.ldb == s.n) : (s.ldb == s.k)));
   const bool wg_fits = (tight && 0 != wg_env && smm_jit_wg_buf(s.typesize, s.m, s.n, s.k, s.flags) <= 65536
                      && (2 == wg_env || (size_t)s.typesize * ((size_t)s.m * s.k + (size_t)s.k * s.n) >= 12288));
   if (SYNC_RUNS == s.sync) { // the host knows that C repeats in runs (one C for the whole batch, batch-reduce): long runs
-    if (wg_fits) {
-      const int e = smm_jit_launch_variant(s, width | SMM_JIT_WGRUNS, stream);
-      if (0 <= e) { *name = f64 ? "smm_f64_jit_shape_wgruns" : "smm_f32_jit_shape_wgruns"; return e; }
-    }
-    *name = f64 ? "smm_f64_jit_shape_runs" : "smm_f32_jit_shape_runs";
-    return smm_jit_launch_variant(s, width | SMM_JIT_RUNS, stream);
+    if (wg_fits) plan_add(p, TIER_JIT, f64 ? "smm_f64_jit_shape_wgruns" : "smm_f32_jit_shape_wgruns", width | SMM_JIT_WGRUNS);
+    plan_add(p, TIER_JIT, runs_name, width | SMM_JIT_RUNS);
+    return;
   }
-  // SYNC_DEVICE: both run forms are launched; each reads the device-side verdict (average run length) and one of them works
-  *name = f64 ? "smm_f64_jit_shape_runs" : "smm_f32_jit_shape_runs";
-  const int split = (0 != s.relaxed ? SMM_JIT_SPLIT : 0); // the caller's reference path is unordered as well
-  // (both kernels are resolved before anything is launched: a wave form that leaves long runs to a companion that then
-  // fails to compile would have to be followed by a second wave-form launch -- which would add the short runs twice)
-  auto available = [&](int variant) {
-    const SmmKey key = { s.typesize, s.m, s.n, s.k, s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B), variant, s.lda, s.ldb, s.ldc };
-    return nullptr != smm_jit_get(key);
-  };
-  const bool pair = wg_fits && available(width | split | SMM_JIT_WGRUNS) && available(width | split | SMM_JIT_RUNS | SMM_JIT_HASWG);
-  if (!pair) return smm_jit_launch_variant(s, width | split | SMM_JIT_RUNS, stream); // the wave form alone takes long runs as well
-  int e = smm_jit_launch_variant(s, width | split | SMM_JIT_RUNS | SMM_JIT_HASWG, stream);
-  if (0 == e) e = smm_jit_launch_variant(s, width | split | SMM_JIT_WGRUNS, stream);
-  return e;
+  // SYNC_DEVICE: both run forms are launched; each reads the device-side verdict (average run length) and one of them works.
+  // (a wave form that leaves long runs to a companion that then fails to compile would have to be followed by a second wave-form
+  // launch -- which would add the short runs twice: the executor launches nothing before the kernels of all parts are ready)
+  const int split = (0 != s.relaxed ? SMM_JIT_SPLIT : 0);
+  if (wg_fits) {
+    SmmAlt& a = plan_alt(p, TIER_JIT, runs_name);
+    plan_part(p, a, width | split | SMM_JIT_RUNS | SMM_JIT_HASWG, SLICE_ALL);
+    plan_part(p, a, width | split | SMM_JIT_WGRUNS, SLICE_ALL);
+  }
+  plan_add(p, TIER_JIT, runs_name, width | split | SMM_JIT_RUNS); // the wave form alone takes long runs as well
+}
+} // namespace
+
+// The alternatives of both tiers for batch s, in the order the launchers try them. Pure: no device, no kernel looked up.
+static void smm_jit_plan(const SmmBatch& s, SmmPlan& p)
+{
+  p.batch = s; p.ab_bytes = p.c_bytes = s.typesize; p.pack = 1; p.nalts = 0;
+  if (!smm_jit_enabled()) return;
+  if (0 != s.lowp) { plan_lowp(s, p); return; }
+  plan_mfma(s, p);
+  if (smm_jit_eligible(s)) plan_jit(s, p);
 }
 
-// Code objects ahead of time (no device needed): for every shape the flavours a batch call may ask for -- strided batches
-// (wide accesses, several items per wave where that is chosen), index / pointer batches (element-wide accesses: streaming,
-// run forms and their relaxed-order twins) -- and, if `grouped`, the fused kernel of all shapes for index batches. Returns
-// the number of code objects that could not be built.
+// the part of the batch a launch part covers
+static SmmBatch smm_slice(const SmmPlan& p, int slice)
+{
+  SmmBatch s = p.batch;
+  const long long done = (s.batch / p.pack) * p.pack;
+  if (SLICE_PACKED == slice) { s.sa *= p.pack; s.sb *= p.pack; s.sc *= p.pack; s.batch /= p.pack; } // the kernel takes `pack` items as one
+  else if (SLICE_REST == slice) {
+    s.a = (const char*)s.a + done * s.sa * p.ab_bytes; s.b = (const char*)s.b + done * s.sb * p.ab_bytes;
+    s.c = (char*)s.c + done * s.sc * p.c_bytes; s.batch -= done;
+  }
+  return s;
+}
+
+// Launches the first alternative of the tier whose kernels are all ready (every kernel of an alternative is asked for, so that
+// the compiler thread builds them all). -1: none is (the caller's next tier serves, with the same bits).
+static int smm_jit_execute(const SmmPlan& p, int tier, void* stream, const char** name)
+{
+  for (int i = 0; i < p.nalts; ++i) {
+    const SmmAlt& a = p.alts[i];
+    if (tier != a.tier) continue;
+    if (0 < a.ntiles) {
+      GroupedPlan gp;
+      JitKernel* const kern = grouped_resolve(a.tiles, a.ntiles, false, true, gp);
+      if (nullptr == kern) continue;
+      *name = a.name;
+      return grouped_launch(a.tiles, gp, kern, stream);
+    }
+    JitKernel* kern[2] = { nullptr, nullptr };
+    bool ready = true;
+    for (int j = 0; j < a.nparts; ++j) ready = (nullptr != (kern[j] = smm_jit_get(a.part[j].key))) && ready;
+    if (!ready) continue;
+    *name = a.name;
+    int e = 0;
+    for (int j = 0; j < a.nparts && 0 == e; ++j) e = smm_jit_launch(smm_slice(p, a.part[j].slice), a.part[j].key.variant, kern[j], stream);
+    return e;
+  }
+  return -1;
+}
+
+int launch_smm_jit_mfma(const SmmBatch& s, void* stream, const char** name)
+{
+  SmmPlan p;
+  smm_jit_plan(s, p);
+  return smm_jit_execute(p, TIER_MFMA, stream, name);
+}
+
+int launch_smm_jit(const SmmBatch& s, void* stream, const char** name)
+{
+  SmmPlan p;
+  smm_jit_plan(s, p);
+  return smm_jit_execute(p, TIER_JIT, stream, name);
+}
+
+// Code objects ahead of time (no device needed): every kernel the plans of a fixed set of batches per shape name -- strided
+// batches (wide and element-wide accesses), index batches (independent items, runs, the verdict on the device in batch order
+// and relaxed, a batch of few runs split into tiles) -- and, if `grouped`, the fused kernel of all shapes for index batches.
+// Returns the number of code objects that could not be built.
 int smm_jit_prebuild(const SmmBatch* shapes, int nshapes, int grouped, int* built)
 {
   int failed = 0, done = 0;
-  static const int wg_env = []() { const char* e = getenv("XSMM_SMMJIT_WG"); return (nullptr != e && 0 != *e) ? atoi(e) : 1; }();
-  auto build = [&](const std::string& src) { std::string log; if (src.empty()) return; if (0 == jit_build_offline(src, &log)) ++done; else { ++failed; if (0 != verbosity()) fprintf(stderr, "LIBXSMM-AMD: prebuild: %s\n", log.c_str()); } };
+  std::unordered_set<std::string> seen;
+  auto build = [&](const std::string& src) {
+    std::string log;
+    if (src.empty() || !seen.insert(src).second) return;
+    if (0 == jit_build_offline(src, &log)) ++done; else { ++failed; if (0 != verbosity()) fprintf(stderr, "LIBXSMM-AMD: prebuild: %s\n", log.c_str()); }
+  };
+  auto sample = [](const SmmBatch& shape, int mode, int sync, int relaxed) {
+    SmmBatch s = shape;
+    s.mode = mode; s.sync = sync; s.relaxed = relaxed; s.batch = 1 << 20; s.jit_always = 1; s.c_atomics = 1;
+    s.use_mfma = 1; // (the default policy; a process that switches the matrix cores off compiles its own)
+    s.a = s.b = s.c = nullptr; s.ia = s.ib = s.ic = nullptr; s.devflags = nullptr; s.uniform_run = 0;
+    s.sa = (long long)s.m * s.k; s.sb = (long long)s.k * s.n; s.sc = (long long)s.m * s.n;
+    return s;
+  };
   for (int i = 0; i < nshapes; ++i) {
-    SmmBatch s = shapes[i];
-    s.batch = 1 << 20; s.jit_always = 1; s.sync = SYNC_NONE;
-    if (!smm_jit_eligible(s)) continue;
-    const int flags = s.flags & (LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_TRANS_B);
-    auto one = [&](int variant) { build(gen_smm_source(s.typesize, s.m, s.n, s.k, flags, variant, s.lda, s.ldb, s.ldc)); };
-    if (s.m > 32 || s.n > 32 || s.k > 64) {
-      one(SMM_JIT_BIG);
-      if (s.m <= 64 && s.n <= 64 && s.k <= 64 && 0 == (flags & LIBXSMM_GEMM_FLAG_TRANS_B)) { // the matrix-core forms launch_smm_jit_mfma would pick
-        const size_t wlds = smm_mfma_wave_lds(s.typesize, s.m, s.n, s.k);
-        const bool f64 = (8 == s.typesize);
-        const size_t w2lds = f64 ? smm_mfma_wave2_lds(s.typesize, s.m, s.n, s.k) : 0;
-        if (0 != wlds && 4 * wlds <= 160u * 1024u && s.lda == s.m && s.ldb == s.k && s.ldc == s.m) { one(SMM_JIT_MFMA_WAVE); one(SMM_JIT_MFMA_WAVE | SMM_JIT_SCALAR); }
-        else if (0 != w2lds && 4 * w2lds <= 160u * 1024u && !(64 == s.m && 64 == s.n) && s.lda == s.m && s.ldb == s.k && s.ldc == s.m) one(SMM_JIT_MFMA_WAVE2);
-        else if (!(!f64 && 64 == s.m && 64 == s.n && 64 == s.k && 64 == s.lda && 64 == s.ldb && 64 == s.ldc)) {
-          const bool tight = !f64 && s.lda == s.m && s.ldb == s.k && 0 == ((s.m * s.k) & 3) && 0 == ((s.k * s.n) & 3);
-          const bool tightc = !f64 && s.ldc == s.m && 0 == ((s.m * s.n) & 3) && 0 != (s.m & 31);
-          one(SMM_JIT_MFMA | (tight ? SMM_JIT_MFMA_TIGHT : 0) | (tightc ? SMM_JIT_MFMA_TIGHTC : 0));
+    SmmBatch kinds[8];
+    kinds[0] = sample(shapes[i], ADDR_STRIDED, SYNC_NONE, 0); // tight, 16-byte aligned items back to back: wide accesses
+    kinds[1] = kinds[0]; kinds[1].sa += 1;                      // element-wide accesses
+    kinds[2] = sample(shapes[i], ADDR_INDEX, SYNC_NONE, 0);
+    kinds[3] = sample(shapes[i], ADDR_INDEX, SYNC_RUNS, 0);
+    kinds[4] = sample(shapes[i], ADDR_INDEX, SYNC_DEVICE, 0);
+    kinds[5] = sample(shapes[i], ADDR_INDEX, SYNC_DEVICE, 1);
+    kinds[6] = kinds[4]; kinds[6].batch = 64;                   // few runs: the tiles of C as groups (smm_tile_split)
+    for (int j = 0; j < 7; ++j) {
+      SmmPlan p;
+      smm_jit_plan(kinds[j], p);
+      for (int a = 0; a < p.nalts; ++a) {
+        const SmmAlt& alt = p.alts[a];
+        if (0 < alt.ntiles) build(gen_smm_grouped_source_for(alt.tiles, alt.ntiles, true));
+        for (int q = 0; q < alt.nparts; ++q) {
+          const SmmKey& k = alt.part[q].key;
+          build(gen_smm_source(k.typesize, k.m, k.n, k.k, k.flags, k.variant, k.lda, k.ldb, k.ldc));
         }
-      }
-      continue;
-    }
-    // strided batches: the wide flavour with the pack the launcher would choose, and the element-wide flavour for the remainder
-    SmmBatch t = s; t.mode = ADDR_STRIDED; t.sa = (long long)s.m * s.k; t.sb = (long long)s.k * s.n; t.sc = (long long)s.m * s.n;
-    const int pack = smm_jit_pack(t, 0);
-    one(0); if (1 < pack) one(smm_jit_pack_bits(pack));
-    one(SMM_JIT_SCALAR);
-    if (0 == (flags & LIBXSMM_GEMM_FLAG_BETA_0)) { // shared C only matters with beta == 1
-      const bool tight = (s.lda == s.m && s.ldc == s.m && (0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (s.ldb == s.n) : (s.ldb == s.k)));
-      const bool wg_fits = (tight && 0 != wg_env && smm_jit_wg_buf(s.typesize, s.m, s.n, s.k, flags) <= 65536
-                         && (2 == wg_env || (size_t)s.typesize * ((size_t)s.m * s.k + (size_t)s.k * s.n) >= 12288));
-      for (int split = 0; split <= SMM_JIT_SPLIT; split += SMM_JIT_SPLIT) {
-        { SmmBatch r = s; r.use_mfma = 1; if (smm_mfma_runs_ok(r)) one(SMM_JIT_SCALAR | split | SMM_JIT_RUNS | SMM_JIT_MFMA_RUNS); }
-        one(SMM_JIT_SCALAR | split | SMM_JIT_RUNS);
-        if (wg_fits) { one(SMM_JIT_SCALAR | split | SMM_JIT_RUNS | SMM_JIT_HASWG); one(SMM_JIT_SCALAR | split | SMM_JIT_WGRUNS); }
       }
     }
   }
@@ -2714,18 +2717,10 @@ int smm_jit_prebuild(const SmmBatch* shapes, int nshapes, int grouped, int* buil
     for (int relaxed = 0; relaxed < 2; ++relaxed) {
       std::vector<SmmBatch> g;
       for (int i = 0; i < nshapes; ++i) {
-        SmmBatch s = shapes[i]; s.mode = ADDR_INDEX; s.batch = 1 << 20; s.sync = SYNC_DEVICE; s.relaxed = relaxed; s.jit_always = 1; s.c_atomics = 1;
-        s.use_mfma = 1; // (the default policy; a process that switches the matrix cores off compiles its own)
+        const SmmBatch s = sample(shapes[i], ADDR_INDEX, SYNC_DEVICE, relaxed);
         if (smm_jit_grouped_eligible(s) && s.typesize == shapes[0].typesize) g.push_back(s);
       }
       if (1 < g.size()) build(gen_smm_grouped_source_for(g.data(), (int)g.size()));
-    }
-    // one call per shape with few runs: the tiles of C as groups (smm_tile_split)
-    for (int i = 0; i < nshapes; ++i) {
-      SmmBatch s = shapes[i]; s.mode = ADDR_INDEX; s.batch = 64; s.sync = SYNC_DEVICE; s.relaxed = 0; s.jit_always = 1; s.c_atomics = 1; s.use_mfma = 1;
-      SmmBatch tiles[4];
-      const int nt = (0 == (s.flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? smm_tile_split(s, tiles) : 0;
-      if (1 < nt) build(gen_smm_grouped_source_for(tiles, nt, true));
     }
   }
   if (nullptr != built) *built = done;

@@ -612,6 +612,53 @@ print("RESULT", blocked, first, second, gblocked, gfirst, gsecond)
 
 
 @pytest.mark.gpu
+def test_packed_batch_with_remainder_adds_every_item_once(xs, orc, torch_gpu, tmp_path):
+    """Asynchronous compile, cold cache: a strided batch of 13^3 doubles whose packed kernel (four items per wave pass) is ready but
+    whose remainder kernel has not been asked for yet must not launch the packed part and then fall back to the generic kernel over
+    the whole batch (beta = 1: the packed items would be added twice). Run in a child process: environment and caches stay as they are."""
+    import subprocess
+    import sys
+    script = r"""
+import importlib, os, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import torch
+import oracle_binding as orc
+xs = importlib.import_module("libxsmm-1_amd")
+L = xs.lib()
+torch.cuda.set_device(0)
+L.libxsmm_amd_set_mfma(0)
+rng = np.random.default_rng(3)
+m = n = k = 13
+blob, desc = xs.descriptor(xs.F64, m, n, k, m, k, m, 1.0, 1.0)
+def call(batch):
+    a = rng.uniform(-1, 1, batch * m * k); b = rng.uniform(-1, 1, batch * k * n); c = rng.uniform(-1, 1, batch * m * n)
+    ref = c.copy(); orc.gemm_batch_strided(orc.FMA, 0, m, n, k, m, k, m, a, b, ref, m * k, k * n, m * n, batch, 4)
+    da, db, dc = (torch.from_numpy(x).cuda() for x in (a, b, c))
+    assert 0 == L.libxsmm_amd_gemm_batch_strided(desc, xs.dptr(da), xs.dptr(db), xs.dptr(dc), m * k, k * n, m * n, batch)
+    torch.cuda.synchronize()
+    assert np.array_equal(dc.cpu().numpy(), ref), (batch, xs.last_kernel())
+    return xs.last_kernel()
+first = call(1000)        # queues the packed kernel (and the unpacked one it falls back to)
+L.libxsmm_amd_jit_wait()
+second = call(1001)       # packed kernel ready, remainder kernel never asked for
+L.libxsmm_amd_jit_wait()
+third = call(1001)
+print("RESULT", first, second, third)
+"""
+    env = dict(os.environ)
+    env.pop("LIBXSMM_AMD_JIT_ASYNC", None)
+    env.pop("LIBXSMM_AMD_JIT_MINBATCH", None)
+    env["XSMM_SMMJIT_PACK"] = "4"
+    env["LIBXSMM_AMD_CACHE"] = str(tmp_path / "cold_cache")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, "-c", script, root], capture_output=True, text=True, env=env, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    line = [l for l in res.stdout.splitlines() if l.startswith("RESULT")][-1].split()
+    assert line[3] == "smm_f64_jit_shape", line
+
+
+@pytest.mark.gpu
 def test_process_may_exit_while_the_compiler_thread_is_busy(xs, torch_gpu, tmp_path):
     """A short-lived process that has just handed a kernel to the compiler thread exits cleanly (the helper thread is not left
     inside hiprtc / the HIP runtime while their static objects are torn down), and the code object it was building is on disk."""
