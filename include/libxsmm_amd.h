@@ -42,11 +42,43 @@ LIBXSMM_API void* libxsmm_amd_get_stream(void);
  *  as well: consecutive calls of one kind on one handle with the same operands merge into rectangles of blocks, launched
  *  -- one kernel per rectangle, one for a full sweep -- by whatever ends the record (a call of another kind or with other
  *  operands, libxsmm_amd_flush / libxsmm_amd_defer_end, any other entry point of the library on the thread). They run at
- *  the stream position of THAT moment; every block still touches only its own slices / C tile. */
+ *  the stream position of THAT moment; every block still touches only its own slices / C tile.
+ *  Inside a bracket (again not with the environment variable alone) batch calls are recorded too: libxsmm_gemm_batch,
+ *  libxsmm_gemm_batch_omp, libxsmm_mmbatch[_kernel] with one task and the group loops of libxsmm_?gemm_batch[_omp] -- the
+ *  caller's loop with one call per shape (samples/cp2k/cp2k.cpp:328-360). RECORDED is a call in the SMM domain (alpha 1,
+ *  beta 0 or 1, no TRANS_A; f32 / f64) with index arrays or arrays of pointers, whose matrices the GPU reaches and whose C
+ *  the CPU does not address, on a stream that is not being captured. Index / pointer arrays the CPU addresses are copied
+ *  when the call is made: the caller may overwrite them as soon as the call returns. The MATRICES fall under the bracket's
+ *  contract above (libxsmm_amd_flush() before the caller's own work on the stream touches them), and arrays in device
+ *  memory are read at the flush, so they belong to the operands in this respect. The recorded calls RUN AT THE STREAM
+ *  POSITION OF THE FLUSH: libxsmm_amd_flush, the outermost libxsmm_amd_defer_end (an inner one leaves the record open), a
+ *  call that cannot be recorded (it runs behind the recorded ones), a change of precision, any other entry point of the
+ *  library on the thread (libxsmm_amd_synchronize included), or a 65th call (a record holds at most 64 calls; the next one flushes it first). At the flush the calls are cut, in
+ *  call order, into segments of consecutive calls that are independent of each other (libxsmm_amd_merge_segments); every
+ *  segment is one fused launch like libxsmm_amd_gemm_batch_groups (one C-ordering check, one multiplication where the
+ *  shape-specialised run kernels apply), segment after segment: calls that depend on each other keep the call order, and the
+ *  sums per C block are formed as outside the bracket. Independence is judged by the address ranges the operands of a call
+ *  span. For arrays the CPU addresses these were noted at the call; for arrays in device memory a small kernel computes them
+ *  at the flush and the host reads its table back (48 bytes per call): THE ONE WAIT FOR THE STREAM this path adds, at most
+ *  once per flush and only when a recorded call had its arrays in device memory. Do not begin a stream capture with a record
+ *  open (flush first): calls recorded before the capture would become part of the graph, and since nothing may be waited for
+ *  inside a capture, calls with arrays in device memory then run one after the other. A thread ends its brackets before it ends. */
 LIBXSMM_API void libxsmm_amd_defer_begin(void);
 LIBXSMM_API void libxsmm_amd_defer_end(void);
 LIBXSMM_API int libxsmm_amd_defer_active(void);
 LIBXSMM_API void libxsmm_amd_flush(void);
+/** The segments recorded batch calls leave in (see above), as a pure function: n calls in call order, hulls[6 * i ...] =
+ *  {a_lo, a_hi, b_lo, b_hi, c_lo, c_hi} of call i -- the byte addresses its A, B and C operands span, half-open ranges
+ *  [lo, hi). Two ranges meet if they share a byte (ranges that only touch, hi == lo, do not). Call i joins the open segment
+ *  unless its C meets the A, B or C of a member or its A or B meets the C of a member; then it opens a new segment.
+ *  segment_of[i] receives the segment of call i (0, 1, ...); returns the number of segments (0 for n == 0), -1 for bad arguments. */
+LIBXSMM_API int libxsmm_amd_merge_segments(int n, const unsigned long long hulls[], int segment_of[]);
+/** DIAGNOSTIC, not a stable part of the interface (it may change or go without notice; the tests use it to see which path a
+ *  flush took). What the calling thread's last flush of recorded batch calls did: the number of calls, of segments, of
+ *  calls whose hulls the device computed (-1: the hulls could not be had and the calls ran one after the other), and -- for
+ *  the first `capacity` calls -- the hulls (6 per call) and segments as for libxsmm_amd_merge_segments. Any pointer may be
+ *  NULL. Returns the number of calls written. */
+LIBXSMM_API int libxsmm_amd_merge_last_plan(int* ncalls, int* nsegments, int* ndevice_hulls, unsigned long long hulls[], int segment_of[], int capacity);
 /** Block until all work enqueued by this library on its stream has completed. Returns EXIT_SUCCESS/FAILURE. */
 LIBXSMM_API int libxsmm_amd_synchronize(void);
 /** Device memory (hipMalloc/hipFree) -- what libxsmm_malloc returns when a device is present is host-pinned

@@ -237,6 +237,9 @@ def _declare(L):
     sig("libxsmm_amd_defer_begin", None)
     sig("libxsmm_amd_defer_end", None)
     sig("libxsmm_amd_defer_active", i)
+    ull_p = C.POINTER(C.c_ulonglong)
+    sig("libxsmm_amd_merge_segments", i, i, ull_p, c_int_p)
+    sig("libxsmm_amd_merge_last_plan", i, c_int_p, c_int_p, c_int_p, ull_p, c_int_p, i)
     sig("libxsmm_amd_is_device_pointer", i, vp)
     sig("libxsmm_amd_gemm_batch_strided", i, vp, vp, vp, vp, ll, ll, ll, ll)
     sig("libxsmm_amd_stream_probe", i, vp, vp, vp, ll)
@@ -347,6 +350,41 @@ def gemm_batch_groups(prec, shapes, a, b, c, stride_a, stride_b, stride_c, sizes
     return lib().libxsmm_amd_gemm_batch_groups(prec, prec, n, chars(transa), chars(transb), ints(s[0] for s in shapes), ints(s[1] for s in shapes),
                                                ints(s[2] for s in shapes), lds(lda), lds(ldb), lds(ldc), None, C.byref(be), ptrs(a), ptrs(b), ptrs(c),
                                                index_base, index_stride, ptrs(stride_a), ptrs(stride_b), ptrs(stride_c), ints(sizes), 1 if relaxed else 0)
+
+
+def defer_begin():
+    """libxsmm_amd_defer_begin: per-product kernel calls, spmdm block calls and batch calls of this thread are recorded (brackets nest)"""
+    lib().libxsmm_amd_defer_begin()
+
+
+def defer_end():
+    """libxsmm_amd_defer_end: the outermost one launches what was recorded"""
+    lib().libxsmm_amd_defer_end()
+
+
+def flush():
+    """libxsmm_amd_flush: launches what was recorded, the bracket stays open"""
+    lib().libxsmm_amd_flush()
+
+
+def merge_segments(hulls):
+    """libxsmm_amd_merge_segments: hulls = per call (a_lo, a_hi, b_lo, b_hi, c_lo, c_hi), half-open byte ranges -> (number of segments,
+    [segment of call i])"""
+    n = len(hulls)
+    flat = (C.c_ulonglong * max(1, 6 * n))(*[int(v) for h in hulls for v in h])
+    seg = (C.c_int * max(1, n))()
+    count = lib().libxsmm_amd_merge_segments(n, flat, seg)
+    return count, [seg[j] for j in range(n)]
+
+
+def merge_last_plan(capacity=64):
+    """libxsmm_amd_merge_last_plan -> dict(calls, segments, device_hulls, hulls=[6-tuples], segment_of=[...]) of this thread's last flush"""
+    nc, ns, nd = C.c_int(0), C.c_int(0), C.c_int(0)
+    flat = (C.c_ulonglong * (6 * capacity))()
+    seg = (C.c_int * capacity)()
+    m = lib().libxsmm_amd_merge_last_plan(C.byref(nc), C.byref(ns), C.byref(nd), flat, seg, capacity)
+    return dict(calls=nc.value, segments=ns.value, device_hulls=nd.value, hulls=[tuple(flat[6 * j + o] for o in range(6)) for j in range(m)],
+                segment_of=[seg[j] for j in range(m)])
 
 
 def call_kernel(fn_ptr, a, b, c, x3=None):

@@ -247,9 +247,32 @@ bool open_burst(Ring& r, Kernel* k)
 } // namespace
 
 bool defer_bracket_open() { return 0 < tl_defer_bracket; }
+bool defer_capturing(void* stream) { return capturing_now(stream); }
+
+// Recorded batch calls (xsmm_gemm.cpp) leave in segments: consecutive calls that may run side by side. The rule is the one the
+// grouped pointer batches follow (xsmm_gemm.cpp: try_grouped_pointer_batches): a call's C must not meet another member's A, B
+// or C. A call that conflicts with a member of the open segment opens a new one -- it then runs behind all of them, in call order.
+int merge_segments(int n, const unsigned long long* hulls, int* segment_of)
+{
+  auto meet = [](const unsigned long long* x, const unsigned long long* y) { return x[0] < y[1] && y[0] < x[1]; }; // half-open ranges
+  int first = 0, segment = 0;
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long* const hi = hulls + 6 * (size_t)i;
+    for (int j = first; j < i; ++j) {
+      const unsigned long long* const hj = hulls + 6 * (size_t)j;
+      if (meet(hi + 4, hj + 0) || meet(hi + 4, hj + 2) || meet(hi + 4, hj + 4) || meet(hj + 4, hi + 0) || meet(hj + 4, hi + 2)) {
+        first = i; ++segment;
+        break;
+      }
+    }
+    segment_of[i] = segment;
+  }
+  return 0 < n ? segment + 1 : 0;
+}
 
 void defer_flush()
 {
+  if (tl_batch_open) batch_flush_record();
   if (tl_spmdm_open) spmdm_flush_record();
   if (!tl_defer_open || nullptr == tl_ring.ring) { tl_defer_open = false; return; }
   close_burst(*tl_ring.ring);
@@ -257,7 +280,8 @@ void defer_flush()
 
 bool defer_call(Kernel* k, const void* a, const void* b, void* c)
 {
-  if (tl_spmdm_open) spmdm_flush_record(); // (recorded spmdm block calls come first: a burst runs at the stream position of its first call)
+  if (tl_batch_open) batch_flush_record(); // (recorded batch calls and spmdm block calls come first: a burst runs at the stream position of its first call)
+  if (tl_spmdm_open) spmdm_flush_record();
   if (!defer_enabled() || nullptr == k || KC_DENSE != k->kclass) return false;
   // small products only (the reference's own JIT domain, LIBXSMM_MAX_MNK = 64^3): a large product is a launch -- or a library
   // GEMM -- of its own that spreads over the chip
@@ -326,6 +350,7 @@ bool defer_call(Kernel* k, const void* a, const void* b, void* c)
 // from device memory), the following calls only count up as long as they continue the walk along the rows.
 bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, int typesize, int M, int N, int K, long long ldb, long long ldc, int vec)
 {
+  if (tl_batch_open) batch_flush_record();
   if (tl_spmdm_open) spmdm_flush_record();
   if (!defer_enabled() || nullptr == handle || nullptr == jit || nullptr == B || nullptr == C) return false;
   Ring* const rp = my_ring();
@@ -401,6 +426,15 @@ LIBXSMM_API void libxsmm_amd_defer_begin(void) { ++tl_defer_bracket; }
 LIBXSMM_API void libxsmm_amd_defer_end(void)
 {
   if (0 < tl_defer_bracket) --tl_defer_bracket;
+  // Recorded batch calls wait for the outermost end: a routine that brackets its own calls does not cut its caller's record.
+  // (Nothing else is open beside a batch record: a burst or spmdm block calls are flushed before a batch call is recorded.)
+  if (0 < tl_defer_bracket && tl_batch_open) return;
   defer_flush(); // whatever was recorded is complete now: the caller may queue its own work behind it
+}
+
+LIBXSMM_API int libxsmm_amd_merge_segments(int n, const unsigned long long hulls[], int segment_of[])
+{ // see include/libxsmm_amd.h
+  if (n < 0 || (0 < n && (nullptr == hulls || nullptr == segment_of))) return -1;
+  return merge_segments(n, hulls, segment_of);
 }
 LIBXSMM_API int libxsmm_amd_defer_active(void) { return defer_enabled() ? 1 : 0; }

@@ -26,9 +26,10 @@ thread_local Scratch tl_scratch[8];
 // The engine's current stream is a per-thread setting (every entry point may be called from any thread, as in the
 // reference; a thread that never calls libxsmm_amd_set_stream launches on the default stream).
 // (Whoever asks for the stream is about to queue work or to wait for it: a burst of deferred per-call kernels that is still
-// open on this thread is sealed first, so that everything stays in the order of the calls -- xsmm_defer.cpp)
+// open on this thread is sealed first, and recorded spmdm block calls and batch calls are launched, so that everything stays
+// in the order of the calls -- xsmm_defer.cpp)
 Device& device_raw() { thread_local Device tl_device; tl_device.count = g_device.count; return tl_device; }
-Device& device() { if (tl_defer_open || tl_spmdm_open) defer_flush(); return device_raw(); }
+Device& device() { if (tl_defer_open || tl_spmdm_open || tl_batch_open) defer_flush(); return device_raw(); }
 
 bool device_ready()
 {
@@ -259,7 +260,7 @@ int flag_slot_set(int* slot, int equal_pairs, int decreasing_pairs)
 // reused INDEX_RING calls later; by then the launch that read it (event recorded by index_upload_commit) is normally long done.
 namespace {
 struct IndexStage { void* host = nullptr; void* dev = nullptr; size_t size = 0; int commit = -1; void* stream = nullptr; int state = 0; /* 1: filled, 2: committed */ };
-constexpr int INDEX_RING = 256; // (a grouped call stages three arrays per group plus its table)
+constexpr int INDEX_RING = INDEX_UPLOAD_RING;
 thread_local IndexStage tl_index_ring[INDEX_RING];
 thread_local unsigned tl_index_next = 0;
 // (one event per commit, shared by the entries a call has filled: see the flag ring above)
@@ -269,6 +270,10 @@ thread_local unsigned tl_index_next_commit = 0;
 
 void* index_upload(const void* src, size_t bytes)
 {
+  // An entry that was filled but not committed is waited for and taken over when the ring comes round to it: whoever holds
+  // commits back -- the record of batch calls inside a bracket (xsmm_gemm.cpp: MERGE_MAX_UPLOADS), until its flush has queued
+  // the launches -- must keep its entries plus whatever is staged during that flush below INDEX_UPLOAD_RING (run_groups
+  // stages nothing today: its tables travel as kernel arguments).
   IndexStage& e = tl_index_ring[tl_index_next++ % INDEX_RING];
   if (2 == e.state && 0 <= e.commit) (void)hipEventSynchronize(tl_index_commits[e.commit]);
   else if (1 == e.state) (void)hipStreamSynchronize((hipStream_t)e.stream); // filled but never committed (an error path)

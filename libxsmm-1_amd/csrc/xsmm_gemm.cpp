@@ -454,9 +454,195 @@ bool try_record(const libxsmm_gemm_descriptor& d, const void* a, const void* b, 
   return true;
 }
 
+// ---- batch calls inside a libxsmm_amd_defer_begin/end bracket ---------------------------------------------------------
+// A caller's loop of libxsmm_gemm_batch calls, one per shape (samples/cp2k/cp2k.cpp:328-360), launches shape after shape:
+// the chains of one shape do not fill the chip and launches on one stream do not overlap. Inside a bracket the calls are
+// recorded -- each as the fully resolved batch libxsmm_amd_gemm_batch_groups would build for it -- and leave together at
+// the flush (batch_flush_record). Index and pointer arrays the CPU addresses are copied at the call (the caller may reuse
+// its buffers as soon as the call returns, as with the reference's synchronous calls); the staged copies stay uncommitted
+// until the flush has queued the launches that read them.
+constexpr int MERGE_MAX_CALLS = 64;                         // calls a record holds (two check launches' worth): the 65th flushes it first
+constexpr int MERGE_MAX_UPLOADS = INDEX_UPLOAD_RING - 16;  // staged arrays a record may hold (three per call at most)
+
+struct MergeRecord {
+  std::vector<SmmBatch> calls;
+  std::vector<unsigned long long> hulls;  // six per call: {a_lo, a_hi, b_lo, b_hi, c_lo, c_hi}; filled at the call where the host can read the arrays
+  std::vector<char> on_device;            // != 0: the call's arrays live in device memory, its hulls come from the hull kernel
+  int uploads = 0;
+  std::vector<unsigned long long> table;  // the hull kernel's tables, copied back (the device side lives in the thread's scratch)
+  // what the last flush did (libxsmm_amd_merge_last_plan)
+  std::vector<unsigned long long> plan_hulls; std::vector<int> plan_segment; int plan_device = 0;
+};
+thread_local MergeRecord tl_merge;
+
+bool host_readable(int kind) { return 0 == kind || 0 != (kind & 2); } // plain host memory, or pinned / managed memory
+
+void hull_of_indexes(unsigned long long* out, const void* base, const int* idx, int index_stride, int index_base, long long n, int typesize, size_t span)
+{ // (a NULL index array: every item uses the base itself, see resolve() in kernels/smm_common.cuh)
+  const IndexRange r = index_range(idx, index_stride, index_base, n);
+  const unsigned long long p = reinterpret_cast<uintptr_t>(base);
+  out[0] = p + (unsigned long long)(r.lo * typesize);
+  out[1] = p + (unsigned long long)(r.hi * typesize) + (unsigned long long)span * typesize;
+}
+
+void hull_of_pointers(unsigned long long* out, const void* const* ptrs, size_t n, int typesize, size_t span)
+{
+  unsigned long long lo = reinterpret_cast<uintptr_t>(ptrs[0]), hi = lo;
+  for (size_t i = 1; i < n; ++i) { const unsigned long long q = reinterpret_cast<uintptr_t>(ptrs[i]); if (q < lo) lo = q; if (q > hi) hi = q; }
+  out[0] = lo; out[1] = hi + (unsigned long long)span * typesize;
+}
+
+// true: the call was recorded and runs at the next flush. false: nothing was done, the call takes the ordinary path (which
+// flushes the record on its way: it asks for the stream).
+bool record_batch_call(const Kernel* k, libxsmm_blasint index_base, libxsmm_blasint index_stride,
+  const libxsmm_blasint* stride_a, const libxsmm_blasint* stride_b, const libxsmm_blasint* stride_c,
+  const void* a, const void* b, void* c, libxsmm_blasint batchsize, int ntasks)
+{
+  if (!defer_bracket_open() || nullptr == k || KC_DENSE != k->kclass || 1 != ntasks || 0 == batchsize || !device_ready()) return false;
+  const long long size = (batchsize < 0 ? -(long long)batchsize : batchsize);
+  void* const stream = device_raw().stream;
+  if (defer_capturing(stream)) return false;
+  SmmBatch s = from_descriptor(k->desc);
+  const int ts = s.typesize;
+  const int ka = pointer_kind(a), kb = pointer_kind(b), kc = pointer_kind(c);
+  std::vector<const void*> ta, tb, tc; // host pointer arrays, gathered
+  const int* host_idx[3] = { nullptr, nullptr, nullptr };
+  bool on_device = false;
+  if (0 != index_stride) { // index arrays: a, b, c are the matrices
+    if (0 == (ka & kb & kc & 1) || 0 != (kc & 2)) return false; // host matrices (staged), or a C the CPU reads on return
+    s.mode = ADDR_INDEX; s.index_base = index_base; s.index_stride = index_stride; s.a = a; s.b = b; s.c = c;
+    const int* const idx[3] = { reinterpret_cast<const int*>(stride_a), reinterpret_cast<const int*>(stride_b), reinterpret_cast<const int*>(stride_c) };
+    for (int o = 0; o < 3; ++o) {
+      if (nullptr == idx[o]) continue;
+      if (host_readable(pointer_kind(idx[o]))) host_idx[o] = idx[o]; else on_device = true;
+    }
+    s.ia = idx[0]; s.ib = idx[1]; s.ic = idx[2]; // (host arrays: replaced by their staged copies below)
+  }
+  else { // arrays of pointers: a, b, c are the arrays (byte distances as in batch_execute)
+    s.mode = ADDR_POINTER;
+    s.sa = (nullptr != stride_a ? ((long long)*stride_a - (long long)index_base * (long long)sizeof(void*)) : 0);
+    s.sb = (nullptr != stride_b ? ((long long)*stride_b - (long long)index_base * (long long)sizeof(void*)) : 0);
+    s.sc = (nullptr != stride_c ? ((long long)*stride_c - (long long)index_base * (long long)sizeof(void*)) : 0);
+    if (1 == ka && 1 == kb && 1 == kc) { s.a = a; s.b = b; s.c = c; on_device = true; } // device arrays: the matrices live on the device as well
+    else if (host_readable(ka) && host_readable(kb) && host_readable(kc)) {
+      const size_t na = (0 != s.sa ? (size_t)size : 1), nb = (0 != s.sb ? (size_t)size : 1), nc = (0 != s.sc ? (size_t)size : 1);
+      ta.resize(na); tb.resize(nb); tc.resize(nc);
+      for (size_t i = 0; i < na; ++i) ta[i] = *reinterpret_cast<const void* const*>(static_cast<const char*>(a) + s.sa * (long long)i);
+      for (size_t i = 0; i < nb; ++i) tb[i] = *reinterpret_cast<const void* const*>(static_cast<const char*>(b) + s.sb * (long long)i);
+      for (size_t i = 0; i < nc; ++i) tc[i] = *reinterpret_cast<const void* const*>(static_cast<const char*>(c) + s.sc * (long long)i);
+      const int k0 = pointer_kind(tc[0]); // (the first operand of each tells where the matrices live, as in batch_execute)
+      if (0 == (pointer_kind(ta[0]) & pointer_kind(tb[0]) & k0 & 1) || 0 != (k0 & 2)) return false;
+    }
+    else return false;
+  }
+  s.batch = size; s.tasks = 1; s.c_atomics = 1;
+  s.relaxed = relaxed_order(ntasks, index_stride, c) ? 1 : 0;
+  s.sync = (0 != (s.flags & LIBXSMM_GEMM_FLAG_BETA_0) || batchsize < 0 || size < 2) ? SYNC_NONE : SYNC_DEVICE; // (one C for the whole batch is found out on the device as well)
+  MergeRecord& r = tl_merge;
+  if (tl_defer_open || tl_spmdm_open) defer_flush(); // a burst of per-call kernels, recorded spmdm blocks: they come first
+  if (tl_batch_open) { // one fused launch takes one precision, one policy, one order of the sums; the staging ring must hold the record
+    const SmmBatch& f = r.calls.front();
+    // (a change of stream needs no test here: libxsmm_amd_set_stream asks for the stream, which flushes)
+    if (f.typesize != ts || f.use_mfma != s.use_mfma || f.relaxed != s.relaxed
+      || MERGE_MAX_CALLS <= (int)r.calls.size() || MERGE_MAX_UPLOADS < r.uploads + 3) batch_flush_record();
+  }
+  unsigned long long hull[6] = { 0, 0, 0, 0, 0, 0 };
+  const size_t span[3] = { span_a(s), span_b(s), span_c(s) };
+  const bool was_open = tl_batch_open;
+  tl_batch_open = false; // (index_upload asks for the stream, which launches what is open)
+  bool ok = true; int uploads = 0;
+  if (ADDR_INDEX == s.mode) {
+    const int** const dst[3] = { &s.ia, &s.ib, &s.ic };
+    for (int o = 0; o < 3 && ok; ++o) {
+      if (nullptr == host_idx[o]) continue;
+      void* const d = index_upload(host_idx[o], (size_t)(size - 1) * index_stride + sizeof(int));
+      ++uploads; ok = (nullptr != d);
+      *dst[o] = static_cast<const int*>(d);
+    }
+    if (ok && !on_device) {
+      hull_of_indexes(hull + 0, a, host_idx[0], index_stride, index_base, size, ts, span[0]);
+      hull_of_indexes(hull + 2, b, host_idx[1], index_stride, index_base, size, ts, span[1]);
+      hull_of_indexes(hull + 4, c, host_idx[2], index_stride, index_base, size, ts, span[2]);
+    }
+  }
+  else if (!on_device) {
+    s.a = index_upload(ta.data(), ta.size() * sizeof(void*)); s.b = index_upload(tb.data(), tb.size() * sizeof(void*));
+    s.c = index_upload(tc.data(), tc.size() * sizeof(void*));
+    uploads = 3; ok = (nullptr != s.a && nullptr != s.b && nullptr != s.c);
+    s.sa = (0 != s.sa ? (long long)sizeof(void*) : 0); s.sb = (0 != s.sb ? (long long)sizeof(void*) : 0); s.sc = (0 != s.sc ? (long long)sizeof(void*) : 0);
+    hull_of_pointers(hull + 0, ta.data(), ta.size(), ts, span[0]);
+    hull_of_pointers(hull + 2, tb.data(), tb.size(), ts, span[1]);
+    hull_of_pointers(hull + 4, tc.data(), tc.size(), ts, span[2]);
+  }
+  tl_batch_open = was_open;
+  if (!ok) return false; // (entries a failed upload has filled: the ordinary path's commit releases them)
+  if (!tl_batch_open) { r.calls.clear(); r.hulls.clear(); r.on_device.clear(); r.uploads = 0; tl_batch_open = true; }
+  r.uploads += uploads;
+  r.calls.push_back(s); r.hulls.insert(r.hulls.end(), hull, hull + 6); r.on_device.push_back(on_device ? 1 : 0);
+  return true;
+}
+
 } // namespace
 
 namespace xsmm {
+
+// Launches the batch calls recorded on this thread. The hulls of calls whose arrays live in device memory come from the hull
+// kernel and one small copy back -- the only wait for the device this path knows, once per flush and only then. The calls are
+// cut into segments of independent calls (merge_segments); every segment is one run_groups, segment after segment on the stream:
+// dependent calls keep the call order, a segment of one call is the launch it would have been on its own.
+thread_local bool tl_batch_open = false;
+void batch_flush_record()
+{
+  if (!tl_batch_open) return;
+  tl_batch_open = false; // (first: the launches below ask for the stream, which flushes what is open)
+  MergeRecord& r = tl_merge;
+  const int n = (int)r.calls.size();
+  void* const stream = device().stream;
+  bool hulls_ok = true;
+  std::vector<int> dev; // the calls the hull kernel looks at
+  for (int i = 0; i < n; ++i) if (0 != r.on_device[(size_t)i]) dev.push_back(i);
+  if (!dev.empty()) {
+    constexpr size_t TABLE = 2 * 3 * BATCH_HULL_CALLS, TABLES = (MERGE_MAX_CALLS + BATCH_HULL_CALLS - 1) / BATCH_HULL_CALLS;
+    // (a capture that began with the record open: nothing may be waited for -- the calls run one after the other)
+    unsigned long long* const d_hulls = defer_capturing(stream) ? nullptr : static_cast<unsigned long long*>(scratch(7, TABLES * TABLE * sizeof(unsigned long long)));
+    r.table.resize(TABLES * TABLE);
+    hulls_ok = (nullptr != d_hulls);
+    size_t tables = 0;
+    for (size_t first = 0; first < dev.size() && hulls_ok; first += BATCH_HULL_CALLS, ++tables) {
+      const int m = (int)((dev.size() - first < (size_t)BATCH_HULL_CALLS) ? (dev.size() - first) : (size_t)BATCH_HULL_CALLS);
+      SmmBatch chunk[BATCH_HULL_CALLS]; unsigned long long spans[3 * BATCH_HULL_CALLS];
+      for (int j = 0; j < m; ++j) {
+        const SmmBatch& s = r.calls[(size_t)dev[first + (size_t)j]];
+        chunk[j] = s;
+        spans[3 * j + 0] = (unsigned long long)span_a(s) * s.typesize; spans[3 * j + 1] = (unsigned long long)span_b(s) * s.typesize;
+        spans[3 * j + 2] = (unsigned long long)span_c(s) * s.typesize;
+      }
+      hulls_ok = (0 == launch_batch_hulls(chunk, spans, m, d_hulls + tables * TABLE, stream));
+    }
+    if (hulls_ok) hulls_ok = (0 == d2h(r.table.data(), d_hulls, tables * TABLE * sizeof(unsigned long long))); // (waits for the stream)
+    for (size_t j = 0; j < dev.size() && hulls_ok; ++j) {
+      const unsigned long long* const t = r.table.data() + (j / BATCH_HULL_CALLS) * TABLE;
+      const size_t e = 3 * (j % BATCH_HULL_CALLS);
+      unsigned long long* const h = r.hulls.data() + 6 * (size_t)dev[j];
+      for (int o = 0; o < 3; ++o) { h[2 * o] = t[e + (size_t)o]; h[2 * o + 1] = t[3 * BATCH_HULL_CALLS + e + (size_t)o]; }
+    }
+  }
+  std::vector<int> segment((size_t)n, 0);
+  if (hulls_ok) (void)merge_segments(n, r.hulls.data(), segment.data());
+  else for (int i = 0; i < n; ++i) segment[(size_t)i] = i; // no verdict: call after call, which is always right
+  bool ok = true;
+  for (int first = 0; first < n;) {
+    int last = first + 1;
+    while (last < n && segment[(size_t)last] == segment[(size_t)first]) ++last;
+    std::vector<SmmBatch> groups(r.calls.begin() + first, r.calls.begin() + last);
+    if (0 != run_groups(groups)) ok = false;
+    first = last;
+  }
+  index_upload_commit(); // the launches that read the staged arrays are queued
+  if (!ok) { static int error_once = 0; if (0 != libxsmm_verbosity && once(&error_once)) fprintf(stderr, "LIBXSMM ERROR: recorded libxsmm_gemm_batch calls failed!\n"); }
+  r.plan_hulls.swap(r.hulls); r.plan_segment.swap(segment); r.plan_device = (hulls_ok ? (int)dev.size() : -1);
+  r.calls.clear(); r.hulls.clear(); r.on_device.clear(); r.uploads = 0;
+}
 
 // What a kernel thunk does when user code calls the bare function pointer.
 // One product of a low-precision kernel, or a batch of them with independent C operands (device-reachable operands).
@@ -644,6 +830,9 @@ LIBXSMM_API int libxsmm_mmbatch_kernel(libxsmm_xmmfunction kernel, libxsmm_blasi
     else (void)stream_sync();
     return EXIT_SUCCESS;
   }
+  // inside a libxsmm_amd_defer_begin/end bracket: recorded, leaves with its neighbours at the flush
+  if (record_batch_call(k, index_base, index_stride, stride_a, stride_b, stride_c, a, b, c, batchsize, ntasks)) return EXIT_SUCCESS;
+  if (tl_batch_open) batch_flush_record(); // a call that is not recorded runs behind the recorded ones
   SmmBatch s = from_descriptor(k->desc);
   s.relaxed = relaxed_order(ntasks, index_stride, c) ? 1 : 0;
   s.shared_across_calls = (1 < ntasks && 0 <= batchsize) ? 1 : 0; // (a negative batchsize is the caller's promise that nothing is shared)
@@ -945,6 +1134,21 @@ LIBXSMM_API int libxsmm_amd_gemm_batch_groups(libxsmm_gemm_precision iprec, libx
   if (0 != e) return EXIT_FAILURE;
   if (host_visible) (void)stream_sync(); // operands the CPU addresses directly are done with when the call returns
   return EXIT_SUCCESS;
+}
+
+LIBXSMM_API int libxsmm_amd_merge_last_plan(int* ncalls, int* nsegments, int* ndevice_hulls, unsigned long long hulls[], int segment_of[], int capacity)
+{ // see include/libxsmm_amd.h
+  const MergeRecord& r = tl_merge;
+  const int n = (int)r.plan_segment.size();
+  if (nullptr != ncalls) *ncalls = n;
+  if (nullptr != nsegments) *nsegments = (0 < n ? r.plan_segment.back() + 1 : 0);
+  if (nullptr != ndevice_hulls) *ndevice_hulls = r.plan_device;
+  const int m = (n < capacity ? n : capacity);
+  for (int i = 0; i < m; ++i) {
+    if (nullptr != segment_of) segment_of[i] = r.plan_segment[(size_t)i];
+    if (nullptr != hulls) memcpy(hulls + 6 * (size_t)i, r.plan_hulls.data() + 6 * (size_t)i, 6 * sizeof(unsigned long long));
+  }
+  return 0 < m ? m : 0;
 }
 
 // ---- BLAS-like single GEMM (reference LIBXSMM_XGEMM, include/libxsmm_frontend.h:371-411) ---------------------------

@@ -93,6 +93,18 @@ extern thread_local bool tl_defer_open;
 extern thread_local bool tl_spmdm_open;   // spmdm block calls recorded inside a bracket (xsmm_sparse.cpp)
 void spmdm_flush_record();                // launches them
 bool defer_bracket_open();                // the calling thread is inside libxsmm_amd_defer_begin/end
+bool defer_capturing(void* stream);       // the stream is being captured (or cannot be asked): nothing is recorded for later
+extern thread_local bool tl_batch_open;   // batch calls recorded inside a bracket (xsmm_gemm.cpp)
+void batch_flush_record();                // launches them: segments of independent calls, each a fused launch
+// Cuts n calls, in call order, into maximal consecutive segments whose members are independent of each other: no call's C range
+// meets another member's A, B or C range. hulls: {a_lo, a_hi, b_lo, b_hi, c_lo, c_hi} per call, byte addresses, half-open.
+// segment_of[i] receives the segment of call i (0, 1, ...; non-decreasing); returns the number of segments.
+int merge_segments(int n, const unsigned long long* hulls, int* segment_of);
+constexpr int BATCH_HULL_CALLS = 32;      // calls per hull launch (as many as a C-ordering check launch takes)
+// Address hulls of up to BATCH_HULL_CALLS index / pointer batches whose arrays live in device memory (kernels/batch_hull.hip).
+// span_bytes: 3 per call (A, B, C); d_out: device unsigned long long [2][3 * BATCH_HULL_CALLS], initialised here on the stream:
+// the lowest address of operand o of call c in d_out[3 * c + o], the highest (span included) in d_out[3 * BATCH_HULL_CALLS + 3 * c + o].
+int launch_batch_hulls(const SmmBatch* calls, const unsigned long long* span_bytes, int ncalls, unsigned long long* d_out, void* stream);
 
 // CSR "register" kernel family (fsspmdm sparse path, libxsmm_create_?csr_reg): row-major
 // C[m*ldc+n] = (beta? C:0) + sum_p val[p]*B[col[p]*ldb+n], rows without nnz untouched.
@@ -176,6 +188,7 @@ int pointer_kind(const void* p);         // bit 0: the GPU reaches it; bit 1: pi
 bool is_host_visible(const void* p);      // pinned host or managed memory (processed in place, but the CPU reads it directly)
 void settle(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr); // wait for the stream if an operand is host-visible
 int flag_slot_set(int* slot, int equal_pairs, int decreasing_pairs); // the verdict without a check kernel (0: ok)
+constexpr int INDEX_UPLOAD_RING = 256;   // staged arrays a thread may hold before index_upload_commit (a grouped call stages three arrays per group plus its table)
 void* index_upload(const void* host_array, size_t bytes); // async copy of a host index array to the device (nullptr: failed)
 void index_upload_commit();                                // after the launches that read uploaded arrays were queued
 int library_gemm(int typesize, int transa, int transb, int m, int n, int k, double alpha, const void* a, int lda,

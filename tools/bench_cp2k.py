@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 5 on one GPU: CP2K-style stacks -- fp64 products of all 27 shapes (M,N,K) in {13,23,32}^3, grouped by
 shape, every u consecutive products of a group accumulating into one C block (samples/cp2k/cp2k.cpp:155,328-360).
-One libxsmm_gemm_batch call (index arrays) per shape group, all on the engine's stream.
+One libxsmm_gemm_batch call (index arrays) per shape group, all on the engine's stream (call_per_shape), the same loop inside
+libxsmm_amd_defer_begin/end (call_per_shape_bracket), and the one-call form libxsmm_amd_gemm_batch_groups.
 
 usage: python3 tools/bench_cp2k.py [products=524288] [reps=7] [omp=0] [host_idx=0]   (omp=1: libxsmm_gemm_batch_omp, order of the sums relaxed)
 Algorithmic bytes (the reference's bwsize, cp2k.cpp:156): sum over products 8*(M*K+K*N) + sum over C blocks 2*8*M*N."""
@@ -75,39 +76,66 @@ def one_pass(streams):
 
 
 # ONE call for all groups: libxsmm_amd_gemm_batch_groups (one check launch + one multiplication launch, all chains resident)
-if not HOST_IDX:
-    shapes_ = [(g_[0], g_[1], g_[2]) for g_ in groups]
+shapes_ = [(g_[0], g_[1], g_[2]) for g_ in groups]
 
-    def one_call():
-        assert 0 == xs.gemm_batch_groups(xs.F64, shapes_, [g_[4] for g_ in groups], [g_[5] for g_ in groups], [g_[6] for g_ in groups],
-                                         [g_[7] for g_ in groups], [g_[8] for g_ in groups], [g_[9] for g_ in groups], [g_[3] for g_ in groups], relaxed=OMP)
-    import time as _time
-    t0 = _time.perf_counter(); one_call(); torch.cuda.synchronize()
-    print("first grouped call (hiprtc unless the code object is cached on disk): %.2f s" % (_time.perf_counter() - t0))
-    times = []
-    for it in range(reps + 2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); one_call(); e1.record(); torch.cuda.synchronize()
-        if it >= 2:
-            times.append(e0.elapsed_time(e1))
-    t = sorted(times)[len(times) // 2]
-    print("cp2k stacks%s, ONE grouped call: kernel %s  median %.3f ms (min %.3f)  %.0f GB/s (%.1f%% of 8 TB/s)  %.0f GFLOP/s"
-          % (" (relaxed)" if OMP else "", xs.last_kernel(), t, min(times), tot_bytes / t / 1e6, tot_bytes / t / 1e6 / 80.0, tot_flops / t / 1e6))
-    # the same call queued back to back (what bench.py times: the GPU never waits for the host as long as a call costs the host less
-    # than the GPU) and the host's own time per call
-    nq = max(4, reps)
-    torch.cuda.synchronize()
+
+def one_call():
+    assert 0 == xs.gemm_batch_groups(xs.F64, shapes_, [g_[4] for g_ in groups], [g_[5] for g_ in groups], [g_[6] for g_ in groups],
+                                     [g_[7] for g_ in groups], [g_[8] for g_ in groups], [g_[9] for g_ in groups], [g_[3] for g_ in groups], relaxed=OMP)
+
+
+import time as _time  # noqa: E402
+t0 = _time.perf_counter(); one_call(); torch.cuda.synchronize()
+print("first grouped call (hiprtc unless the code object is cached on disk): %.2f s" % (_time.perf_counter() - t0))
+times = []
+for it in range(reps + 2):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    h0 = _time.perf_counter(); e0.record()
-    for it in range(nq):
-        one_call()
-    e1.record(); h1 = _time.perf_counter(); torch.cuda.synchronize()
-    tq = e0.elapsed_time(e1) / nq
-    print("cp2k stacks%s, %d grouped calls queued back to back: %.3f ms per call on the GPU  %.0f GB/s (%.1f%% of 8 TB/s); host time per call %.3f ms"
-          % (" (relaxed)" if OMP else "", nq, tq, tot_bytes / tq / 1e6, tot_bytes / tq / 1e6 / 80.0, (h1 - h0) / nq * 1e3))
+    e0.record(); one_call(); e1.record(); torch.cuda.synchronize()
+    if it >= 2:
+        times.append(e0.elapsed_time(e1))
+t = sorted(times)[len(times) // 2]
+print("cp2k stacks%s, ONE grouped call: kernel %s  median %.3f ms (min %.3f)  %.0f GB/s (%.1f%% of 8 TB/s)  %.0f GFLOP/s"
+      % (" (relaxed)" if OMP else "", xs.last_kernel(), t, min(times), tot_bytes / t / 1e6, tot_bytes / t / 1e6 / 80.0, tot_flops / t / 1e6))
+# the same call queued back to back (what bench.py times: the GPU never waits for the host as long as a call costs the host less
+# than the GPU) and the host's own time per call
+nq = max(4, reps)
+torch.cuda.synchronize()
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+h0 = _time.perf_counter(); e0.record()
+for it in range(nq):
+    one_call()
+e1.record(); h1 = _time.perf_counter(); torch.cuda.synchronize()
+tq = e0.elapsed_time(e1) / nq
+print("cp2k stacks%s, %d grouped calls queued back to back: %.3f ms per call on the GPU  %.0f GB/s (%.1f%% of 8 TB/s); host time per call %.3f ms"
+      % (" (relaxed)" if OMP else "", nq, tq, tot_bytes / tq / 1e6, tot_bytes / tq / 1e6 / 80.0, (h1 - h0) / nq * 1e3))
 
 if ONLY_GROUPED:
     sys.exit(0)
+
+
+def bracketed_pass():
+    """the caller's loop, unchanged, between the two bracket lines: the 27 calls are recorded and leave as one fused launch"""
+    L.libxsmm_amd_defer_begin()
+    one_pass([])
+    L.libxsmm_amd_defer_end()
+
+
+bracketed_pass(); torch.cuda.synchronize()
+times = []
+for it in range(reps + 2):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); bracketed_pass(); e1.record(); torch.cuda.synchronize()
+    if it >= 2:
+        times.append(e0.elapsed_time(e1))
+t = sorted(times)[len(times) // 2]
+
+h0 = _time.perf_counter()
+for it in range(max(4, reps)):
+    bracketed_pass()
+h1 = _time.perf_counter(); torch.cuda.synchronize()
+print("cp2k stacks%s, call_per_shape_bracket (%s index arrays): kernel %s  median %.3f ms (min %.3f)  %.0f GB/s (%.1f%% of 8 TB/s)  %.0f GFLOP/s; host time per bracket %.3f ms"
+      % (" (omp entry)" if OMP else "", "host" if HOST_IDX else "device", xs.last_kernel(), t, min(times), tot_bytes / t / 1e6, tot_bytes / t / 1e6 / 80.0, tot_flops / t / 1e6,
+         (h1 - h0) / max(4, reps) * 1e3))
 for nstreams in (0, 4, 8, 27):
     streams = [torch.cuda.Stream() for _ in range(nstreams)]
     times = []
