@@ -385,6 +385,57 @@ LIBXSMM_API libxsmm_xmmfunction libxsmm_create_rm_ac_soa(const libxsmm_gemm_desc
 LIBXSMM_API libxsmm_xmmfunction libxsmm_create_rm_bc_soa(const libxsmm_gemm_descriptor* descriptor);
 LIBXSMM_API void libxsmm_release_kernel(const void* jit_kernel);   /* src/template/libxsmm.h:325 */
 
+/* ---------------------------------------------------------------------------------------------
+ * packed ("compact") kernels: pgemm, getrf, trmm, trsm over packs of VLEN interleaved matrices
+ * (src/template/libxsmm.h:265-275, include/libxsmm_generator.h:102-119, src/libxsmm_generator.c:383-505).
+ * Element (i,j) of matrix v of a pack: layout 102 (column major) X[(i + j*ldx)*VLEN + v], layout 101 (row major)
+ * X[(j + i*ldx)*VLEN + v]. VLEN is the engine's pack width, libxsmm_amd_packed_width(typesize): 8 (fp64), 16 (fp32) --
+ * the reference's AVX-512 values, whatever the host CPU is. Per matrix of a pack:
+ *   pgemm kernel(A, B, C):       C += alpha * op(A) * op(B), alpha in {1, -1}; op(A) m x k, op(B) k x n, C m x n
+ *   trmm  kernel(A, B, scratch): B := alpha * op(A) * B (side 'L') or alpha * B * op(A) (side 'R'); B m x n
+ *   trsm  kernel(A, B, scratch): op(A) * X = alpha * B (side 'L') or X * op(A) = alpha * B (side 'R'); X overwrites B
+ *   getrf kernel(A, A, NULL):    A = L * U in place, no pivoting: unit-lower L below the diagonal, U on and above it (m x n)
+ * A of trmm / trsm is triangular of order m ('L') or n ('R'), uplo 'L'/'U', diag 'N'/'U'; the strict other triangle, and
+ * the diagonal for diag 'U', are never read. The third argument of trmm / trsm is scratch space of the reference's CPU
+ * kernels: it is neither needed nor touched here (NULL or any pointer). Non-unit trsm and getrf multiply by the rounded
+ * reciprocal of the pivot, as the reference's kernels do. Operands in device memory: one asynchronous launch on the
+ * calling thread's stream; operands the CPU addresses: staged, complete on return (the rules of the dispatched SMM
+ * kernels). A loop over packs costs a launch per pack: use libxsmm_amd_packed_execute_batch (libxsmm_amd.h), or put the
+ * loop between libxsmm_amd_defer_begin/end.
+ * Descriptors: the reference's packed structs (src/libxsmm_main.h:193-226), with two differences in the initialisers:
+ * dimensions are stored in full (the reference's initialisers narrow them through unsigned char, i.e. modulo 256), and
+ * libxsmm_pgemm_descriptor_init returns NULL for an alpha other than 1 or -1 (the reference prints a warning and exits
+ * the process); a NULL alpha means 1. Supported by dispatch: typesize 4 or 8, layout 101 or 102, every dimension from 1
+ * to 32, leading dimensions from the extent they step over up to 4096, trans 'N'/'T', side 'L'/'R', uplo 'L'/'U', diag
+ * 'N'/'U' (either case). For anything else, dimensions beyond 32 included, dispatch returns NULL.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct libxsmm_pgemm_descriptor libxsmm_pgemm_descriptor; /* opaque; src/libxsmm_main.h:193-199 */
+typedef struct libxsmm_getrf_descriptor libxsmm_getrf_descriptor; /* src/libxsmm_main.h:202-206 */
+typedef struct libxsmm_trmm_descriptor libxsmm_trmm_descriptor;   /* src/libxsmm_main.h:209-216 */
+typedef struct libxsmm_trsm_descriptor libxsmm_trsm_descriptor;   /* src/libxsmm_main.h:219-226 */
+/* include/libxsmm_typedefs.h:580-594 */
+typedef void (*libxsmm_pgemm_xfunction)(const void* a, const void* b, void* c);
+typedef void (*libxsmm_getrf_xfunction)(const void* a, const void* b, void* c);
+typedef void (*libxsmm_trmm_xfunction)(const void* a, const void* b, void* c);
+typedef void (*libxsmm_trsm_xfunction)(const void* a, const void* b, void* c);
+/* include/libxsmm_generator.h:102-119 */
+LIBXSMM_API libxsmm_trsm_descriptor* libxsmm_trsm_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint lda, libxsmm_blasint ldb,
+  const void* alpha, char transa, char diag, char side, char uplo, int layout);
+LIBXSMM_API libxsmm_trmm_descriptor* libxsmm_trmm_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint lda, libxsmm_blasint ldb,
+  const void* alpha, char transa, char diag, char side, char uplo, int layout);
+LIBXSMM_API libxsmm_pgemm_descriptor* libxsmm_pgemm_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint k, libxsmm_blasint lda, libxsmm_blasint ldb,
+  libxsmm_blasint ldc, const void* alpha, char transa, char transb, int layout);
+LIBXSMM_API libxsmm_getrf_descriptor* libxsmm_getrf_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint lda, int layout);
+/* src/template/libxsmm.h:265-275; registered kernels (libxsmm_release_kernel leaves them in the registry) */
+LIBXSMM_API libxsmm_pgemm_xfunction libxsmm_dispatch_pgemm(const libxsmm_pgemm_descriptor* descriptor);
+LIBXSMM_API libxsmm_getrf_xfunction libxsmm_dispatch_getrf(const libxsmm_getrf_descriptor* descriptor);
+LIBXSMM_API libxsmm_trmm_xfunction libxsmm_dispatch_trmm(const libxsmm_trmm_descriptor* descriptor);
+LIBXSMM_API libxsmm_trsm_xfunction libxsmm_dispatch_trsm(const libxsmm_trsm_descriptor* descriptor);
+
 /* introspection (src/template/libxsmm.h:107-121) */
 LIBXSMM_API int libxsmm_get_kernel_kind(const void* kernel, libxsmm_kernel_kind* kind);
 LIBXSMM_API int libxsmm_get_mmkernel_info(libxsmm_xmmfunction kernel, libxsmm_mmkernel_info* info, size_t* code_size);

@@ -251,4 +251,21 @@ LIBXSMM_API int libxsmm_amd_soa_width(libxsmm_gemm_precision precision);
 LIBXSMM_API int libxsmm_amd_kernel_execute_batch(const void* kernel, const void* a, const void* b, void* c,
   long long stride_dense, long long stride_c, long long batch);
 
+/* ---- packed kernels (libxsmm_dispatch_pgemm / getrf / trmm / trsm, see libxsmm.h) ----------------------- */
+/** Pack width VLEN of the packed kernels for an element size in bytes: 8 for 8 (fp64), 16 for 4 (fp32), 0 otherwise. */
+LIBXSMM_API int libxsmm_amd_packed_width(unsigned int typesize);
+/** `npacks` packs in one launch: pack p of an operand starts p * ld * lines * VLEN elements behind the first one, where
+ *  lines is the number of columns (layout 102) or rows (layout 101) of the operand as it is stored (A of pgemm with
+ *  transa 'T' is stored k x m, B with transb 'T' n x k; A of trmm / trsm has the order of the triangle) -- the operands
+ *  of consecutive packs lie back to back, which is what a caller's loop `for each pack: kernel(Ap, Bp, Cp)` walks.
+ *  a, b, c as in the kernel call (getrf: b is ignored; trmm / trsm: c is ignored). Device operands: asynchronous on the
+ *  calling thread's stream; operands the CPU addresses are staged and complete on return. The results equal those of
+ *  the per-pack calls bit for bit. Returns EXIT_SUCCESS/EXIT_FAILURE. */
+LIBXSMM_API int libxsmm_amd_packed_execute_batch(const void* kernel, const void* a, const void* b, void* c, long long npacks);
+/** The HIP text a packed descriptor is specialised to (kind: LIBXSMM_KERNEL_KIND_PGEMM / GETRF / TRMM / TRSM selects the
+ *  descriptor type). Buffer/compile/return conventions of libxsmm_amd_csr_kernel_source. The form follows
+ *  LIBXSMM_AMD_PACKED_FORM as a launch does (unset or 0: chosen by shape; 1: packs staged through LDS; 2: every lane
+ *  works on its matrix in global memory). */
+LIBXSMM_API int libxsmm_amd_packed_kernel_source(const void* descriptor, int kind, char* buffer, size_t buffer_size, int compile);
+
 #endif /* LIBXSMM_AMD_H */

@@ -273,6 +273,16 @@ def _declare(L):
     sig("libxsmm_amd_jit_prebuild", i, C.POINTER(vp), i, i)
     sig("libxsmm_amd_jit_wait", None)
     sig("libxsmm_amd_jit_drain", None)
+    u = C.c_uint
+    for nm in ("trsm", "trmm"):
+        sig("libxsmm_%s_descriptor_init" % nm, vp, C.POINTER(DescriptorBlob), u, i, i, i, i, vp, C.c_char, C.c_char, C.c_char, C.c_char, i)
+    sig("libxsmm_pgemm_descriptor_init", vp, C.POINTER(DescriptorBlob), u, i, i, i, i, i, i, vp, C.c_char, C.c_char, i)
+    sig("libxsmm_getrf_descriptor_init", vp, C.POINTER(DescriptorBlob), u, i, i, i, i)
+    for nm in ("pgemm", "getrf", "trmm", "trsm"):
+        sig("libxsmm_dispatch_" + nm, vp, vp)
+    sig("libxsmm_amd_packed_width", i, u)
+    sig("libxsmm_amd_packed_execute_batch", i, vp, vp, vp, vp, ll)
+    sig("libxsmm_amd_packed_kernel_source", i, vp, i, vp, C.c_size_t, i)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -385,6 +395,89 @@ def merge_last_plan(capacity=64):
     m = lib().libxsmm_amd_merge_last_plan(C.byref(nc), C.byref(ns), C.byref(nd), flat, seg, capacity)
     return dict(calls=nc.value, segments=ns.value, device_hulls=nd.value, hulls=[tuple(flat[6 * j + o] for o in range(6)) for j in range(m)],
                 segment_of=[seg[j] for j in range(m)])
+
+
+# ---- packed kernels (libxsmm_dispatch_pgemm / getrf / trmm / trsm) ------------------------------------------------------
+KIND_PGEMM, KIND_GETRF, KIND_TRMM, KIND_TRSM = 3, 4, 5, 6  # libxsmm_kernel_kind
+COL_MAJOR, ROW_MAJOR = 102, 101
+
+
+def packed_width(typesize):
+    """libxsmm_amd_packed_width: matrices per pack (8 for fp64, 16 for fp32)"""
+    return lib().libxsmm_amd_packed_width(typesize)
+
+
+def packed_descriptor(kind, typesize, m, n, k=0, lda=None, ldb=None, ldc=None, alpha=1.0, transa="N", transb="N", side="L", uplo="L",
+                      diag="N", layout=COL_MAJOR):
+    """libxsmm_{pgemm,getrf,trmm,trsm}_descriptor_init -> (blob, pointer); leading dimensions default to the tight ones"""
+    blob = DescriptorBlob()
+    ct = C.c_double if typesize == 8 else C.c_float
+    al = C.byref(ct(alpha)) if alpha is not None else None
+    lead = lambda rows, cols: rows if layout == COL_MAJOR else cols
+    ch = lambda c: c.encode()
+    L = lib()
+    if kind == KIND_PGEMM:
+        ar, ac = (k, m) if transa in "Tt" else (m, k)
+        br, bc = (n, k) if transb in "Tt" else (k, n)
+        p = L.libxsmm_pgemm_descriptor_init(C.byref(blob), typesize, m, n, k, lead(ar, ac) if lda is None else lda,
+                                            lead(br, bc) if ldb is None else ldb, lead(m, n) if ldc is None else ldc, al, ch(transa), ch(transb), layout)
+    elif kind == KIND_GETRF:
+        p = L.libxsmm_getrf_descriptor_init(C.byref(blob), typesize, m, n, lead(m, n) if lda is None else lda, layout)
+    else:
+        nt = n if side in "Rr" else m
+        init = L.libxsmm_trmm_descriptor_init if kind == KIND_TRMM else L.libxsmm_trsm_descriptor_init
+        p = init(C.byref(blob), typesize, m, n, nt if lda is None else lda, lead(m, n) if ldb is None else ldb, al, ch(transa), ch(diag), ch(side),
+                 ch(uplo), layout)
+    return blob, p
+
+
+def packed_dispatch(kind, desc):
+    """libxsmm_dispatch_{pgemm,getrf,trmm,trsm}: the kernel's function pointer, None outside the supported domain"""
+    L = lib()
+    return {KIND_PGEMM: L.libxsmm_dispatch_pgemm, KIND_GETRF: L.libxsmm_dispatch_getrf, KIND_TRMM: L.libxsmm_dispatch_trmm,
+            KIND_TRSM: L.libxsmm_dispatch_trsm}[kind](desc)
+
+
+def packed_execute_batch(fn_ptr, a, b, c, npacks):
+    """libxsmm_amd_packed_execute_batch: npacks packs back to back, one launch"""
+    return lib().libxsmm_amd_packed_execute_batch(fn_ptr, dptr(a), dptr(b), dptr(c), npacks)
+
+
+def packed_kernel_source(kind, desc, compile=0, capacity=1 << 16):
+    """libxsmm_amd_packed_kernel_source -> (return code, text)"""
+    buf = C.create_string_buffer(capacity)
+    rc = lib().libxsmm_amd_packed_kernel_source(desc, kind, buf, capacity, compile)
+    return rc, buf.value.decode()
+
+
+def pack(mats, ld, layout=COL_MAJOR, vlen=None, fill=0):
+    """(nmat, rows, cols) array -> packed layout: element (i, j) of matrix v of pack p at [p][line][i or j][v] with `ld` elements per line
+    (layout 102: a line is a column); nmat is rounded up to whole packs (the added matrices and the padding hold `fill`)"""
+    import numpy as np
+    mats = np.asarray(mats)
+    nmat, rows, cols = mats.shape
+    vlen = packed_width(mats.dtype.itemsize) if vlen is None else vlen
+    npacks = (nmat + vlen - 1) // vlen
+    nl, cd = (cols, rows) if layout == COL_MAJOR else (rows, cols)
+    assert ld >= cd
+    out = np.full((npacks, nl, ld, vlen), fill, dtype=mats.dtype)
+    full = np.full((npacks * vlen, rows, cols), fill, dtype=mats.dtype)
+    full[:nmat] = mats
+    lines = full.transpose(0, 2, 1) if layout == COL_MAJOR else full  # (matrix, line, position in the line)
+    out[:, :, :cd, :] = lines.reshape(npacks, vlen, nl, cd).transpose(0, 2, 3, 1)
+    return out.reshape(-1)
+
+
+def unpack(packed, nmat, rows, cols, ld, layout=COL_MAJOR, vlen=None):
+    """the inverse of pack: -> (nmat, rows, cols)"""
+    import numpy as np
+    packed = np.asarray(packed)
+    vlen = packed_width(packed.dtype.itemsize) if vlen is None else vlen
+    npacks = (nmat + vlen - 1) // vlen
+    nl, cd = (cols, rows) if layout == COL_MAJOR else (rows, cols)
+    lines = packed.reshape(npacks, nl, ld, vlen)[:, :, :cd, :].transpose(0, 3, 1, 2).reshape(npacks * vlen, nl, cd)
+    mats = lines.transpose(0, 2, 1) if layout == COL_MAJOR else lines
+    return np.ascontiguousarray(mats[:nmat])
 
 
 def call_kernel(fn_ptr, a, b, c, x3=None):

@@ -202,6 +202,21 @@ void close_burst(Ring& r)
   r.mine = -1; r.kernel = nullptr; r.ncalls = 0; r.last_c = nullptr; r.panel_handle = nullptr;
 }
 
+// gate and batch kernel of a new burst are queued: the bookkeeping of the open burst
+bool burst_opened(Ring& r, Slot& sl, int s, Kernel* k, void* stream)
+{
+  if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)stream)) sl.pending = true; else (void)hipGetLastError();
+  sl.stream = stream;
+  r.cur = (s + 1) % DEFER_SLOTS;
+  r.kernel = k; r.stream = stream; r.ncalls = 0; r.last_c = nullptr; r.mine = s;
+  r.c_lo = r.a_lo = r.b_lo = ~(uintptr_t)0; r.c_hi = r.a_hi = r.b_hi = 0;
+  r.last_ns.store(now_ns(), std::memory_order_relaxed);
+  r.open_slot.store(s, std::memory_order_release);
+  tl_defer_open = true;
+  if (0 == g_open_bursts.fetch_add(1, std::memory_order_acq_rel)) { std::lock_guard<std::mutex> guard(g_rings_lock); g_helper_wake.notify_one(); }
+  return true;
+}
+
 // queue gate + batch kernel of a new burst on the caller's stream
 bool open_burst(Ring& r, Kernel* k)
 {
@@ -213,6 +228,18 @@ bool open_burst(Ring& r, Kernel* k)
   Slot& sl = r.slot[s];
   if (sl.pending) { (void)hipEventSynchronize(sl.done); sl.pending = false; } // the slot's previous burst (DEFER_SLOTS bursts ago)
   sl.word->store(0, std::memory_order_release);
+  if (KC_PACKED == k->kclass) { // packed kernels: the same gate, the descriptor's own batch kernel behind it (pack p from entry p of the ring)
+    if (0 != launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream)) return false;
+    const char* pname = "";
+    const int pe = packed_launch_burst(k, sl.entries, sl.count, DEFER_CAP, dev.stream, &pname);
+    if (0 != pe) { // (the gate is queued already: let it through with nothing recorded)
+      sl.word->store(SEALED, std::memory_order_release);
+      fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", pname, pe);
+      return false;
+    }
+    note_launch(pname);
+    return burst_opened(r, sl, s, k, dev.stream);
+  }
   SmmBatch b; memset(&b, 0, sizeof(b));
   const libxsmm_gemm_descriptor& d = k->desc;
   b.typesize = (LIBXSMM_GEMM_PRECISION_F64 == LIBXSMM_GETENUM_INP(d.datatype)) ? 8 : 4;
@@ -232,16 +259,7 @@ bool open_burst(Ring& r, Kernel* k)
     return false;
   }
   note_launch("smm_deferred_calls");
-  if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)dev.stream)) sl.pending = true; else (void)hipGetLastError();
-  sl.stream = dev.stream;
-  r.cur = (s + 1) % DEFER_SLOTS;
-  r.kernel = k; r.stream = dev.stream; r.ncalls = 0; r.last_c = nullptr; r.mine = s;
-  r.c_lo = r.a_lo = r.b_lo = ~(uintptr_t)0; r.c_hi = r.a_hi = r.b_hi = 0;
-  r.last_ns.store(now_ns(), std::memory_order_relaxed);
-  r.open_slot.store(s, std::memory_order_release);
-  tl_defer_open = true;
-  if (0 == g_open_bursts.fetch_add(1, std::memory_order_acq_rel)) { std::lock_guard<std::mutex> guard(g_rings_lock); g_helper_wake.notify_one(); }
-  return true;
+  return burst_opened(r, sl, s, k, dev.stream);
 }
 
 } // namespace
@@ -278,22 +296,37 @@ void defer_flush()
   close_burst(*tl_ring.ring);
 }
 
+static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t bytes_a, const void* b, size_t bytes_b, void* c, size_t bytes_c, bool runs);
+
 bool defer_call(Kernel* k, const void* a, const void* b, void* c)
 {
   if (tl_batch_open) batch_flush_record(); // (recorded batch calls and spmdm block calls come first: a burst runs at the stream position of its first call)
   if (tl_spmdm_open) spmdm_flush_record();
-  if (!defer_enabled() || nullptr == k || KC_DENSE != k->kclass) return false;
+  if (!defer_enabled() || nullptr == k || (KC_DENSE != k->kclass && KC_PACKED != k->kclass)) return false;
+  if (KC_PACKED == k->kclass) { // kernel(a, b, c) over one pack: the ring keeps the arguments as they were passed, the overlap rules see
+    PackedOps ops;             // the operand that is written in the place of C and what is only read in the places of A and B
+    if (!packed_operands(k, a, b, c, &ops)) return false;
+    return defer_record(k, Entry{ a, b, c }, ops.rd[0], ops.rd_bytes[0], ops.rd[1], ops.rd_bytes[1], ops.wr, ops.wr_bytes, false);
+  }
   // small products only (the reference's own JIT domain, LIBXSMM_MAX_MNK = 64^3): a large product is a launch -- or a library
   // GEMM -- of its own that spreads over the chip
   if ((long long)k->desc.m * k->desc.n * k->desc.k > 64LL * 64 * 64 || k->desc.m > 128 || k->desc.n > 128) return false;
-  Ring* const rp = my_ring();
-  if (nullptr == rp) return false;
-  Ring& r = *rp;
   const libxsmm_gemm_descriptor& d = k->desc;
   const size_t ts = (LIBXSMM_GEMM_PRECISION_F64 == LIBXSMM_GETENUM_INP(d.datatype)) ? 8 : 4;
   const bool tb = 0 != (d.flags & LIBXSMM_GEMM_FLAG_TRANS_B);
   const size_t bytes_a = ((size_t)(d.k - 1) * d.lda + d.m) * ts, bytes_b = (tb ? ((size_t)(d.k - 1) * d.ldb + d.n) : ((size_t)(d.n - 1) * d.ldb + d.k)) * ts,
                bytes_c = ((size_t)(d.n - 1) * d.ldc + d.m) * ts;
+  return defer_record(k, Entry{ a, b, c }, a, bytes_a, b, bytes_b, c, bytes_c, 0 == (d.flags & LIBXSMM_GEMM_FLAG_BETA_0));
+}
+
+// Appends one call to the calling thread's open burst of kernel k, or opens a new burst for it. entry: what the batch kernel gets;
+// a, b: the operands the call only reads (bytes 0: none -- pass c), c: the one it writes; runs: consecutive calls with one C are
+// a run that one unit of the batch kernel works off in call order (false: a C that repeats seals the burst).
+static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t bytes_a, const void* b, size_t bytes_b, void* c, size_t bytes_c, bool runs)
+{
+  Ring* const rp = my_ring();
+  if (nullptr == rp) return false;
+  Ring& r = *rp;
   const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), pc = reinterpret_cast<uintptr_t>(c);
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (tl_defer_open) {
@@ -305,12 +338,12 @@ bool defer_call(Kernel* k, const void* a, const void* b, void* c)
       // except a C equal to the previous call's C, which continues its run. (Hulls of the addresses: a loop that walks its
       // arrays in one direction never touches them, anything else starts a new burst.)
       // (a kernel that overwrites C has no runs: the later call alone must remain)
-      if (fits && (c != r.last_c || 0 != (d.flags & LIBXSMM_GEMM_FLAG_BETA_0))) fits = !(pc < r.c_hi && r.c_lo < pc + bytes_c);
+      if (fits && (c != r.last_c || !runs)) fits = !(pc < r.c_hi && r.c_lo < pc + bytes_c);
       fits = fits && !(pa < pc + bytes_c && pc < pa + bytes_a) && !(pb < pc + bytes_c && pc < pb + bytes_b);
       fits = fits && !(pa < r.c_hi && r.c_lo < pa + bytes_a) && !(pb < r.c_hi && r.c_lo < pb + bytes_b) && !(pc < r.a_hi && r.a_lo < pc + bytes_c) && !(pc < r.b_hi && r.b_lo < pc + bytes_c);
       if (fits) {
         Slot& sl = r.slot[r.mine];
-        sl.entries[r.ncalls] = Entry{ a, b, c };
+        sl.entries[r.ncalls] = entry;
         unsigned long long expect = (unsigned long long)r.ncalls;
         if (sl.word->compare_exchange_strong(expect, expect + 1, std::memory_order_release, std::memory_order_relaxed)) {
           ++r.ncalls;

@@ -206,7 +206,8 @@ void note_launch(const char* name);
 void* scratch(int slot, size_t bytes);
 
 enum KernelClass : int { KC_DENSE = 0, KC_REDUCE = 1, KC_CSR_REG = 2, KC_TEXT = 3 /* pattern kernel compiled from generated text (SOA family) */,
-  KC_LOWP = 4 /* i16 / bf16 inputs (kernels/smm_lowp.hip) */ };
+  KC_LOWP = 4 /* i16 / bf16 inputs (kernels/smm_lowp.hip) */,
+  KC_PACKED = 5 /* pgemm / getrf / trmm / trsm over packs of interleaved matrices (xsmm_packed.cpp) */ };
 
 struct Kernel {                 // what a dispatched function pointer stands for
   libxsmm_gemm_descriptor desc;
@@ -218,6 +219,8 @@ struct Kernel {                 // what a dispatched function pointer stands for
   unsigned* d_rowptr = nullptr; unsigned* d_colidx = nullptr; void* d_values = nullptr;
   // KC_TEXT payload: libxsmm_amd_spgemm* (xsmm_generator.cpp)
   void* text = nullptr;
+  // KC_PACKED payload (xsmm_packed.cpp); desc is not used
+  void* packed = nullptr;
 };
 
 Kernel* kernel_from_pointer(const void* fn);           // NULL if fn is not one of ours
@@ -227,6 +230,19 @@ void text_kernel_destroy(void* text);
 void* make_thunk(Kernel* k);                           // executable stub carrying k
 void free_thunk(void* thunk);
 void call_kernel(Kernel* k, const void* a, const void* b, void* c, const void* x3, const void* x6); // what a thunk does (x3, x6: the 4th and 7th argument of the call)
+
+// packed kernels (xsmm_packed.cpp)
+// Registered kernels whose key is not a GEMM descriptor: the kernel for these descriptor bytes (tag: kept apart from the GEMM keys),
+// made by make(desc) if the registry does not hold it yet (nullptr: not supported). Returns the kernel's function pointer.
+void* registry_dispatch(const void* desc, size_t size, int tag, Kernel* (*make)(const void* desc));
+void packed_destroy(void* packed);                     // the payload of a packed kernel (Kernel::packed)
+int packed_kind(const Kernel* k);                      // LIBXSMM_KERNEL_KIND_PGEMM ... TRSM
+void packed_call(Kernel* k, const void* a, const void* b, void* c); // what the thunk of a packed kernel does
+// the operands of one call as a burst sees them: rd[2] what is only read (bytes 0: none), wr what is written (and read)
+struct PackedOps { const void* rd[2]; size_t rd_bytes[2]; void* wr; size_t wr_bytes; };
+bool packed_operands(const Kernel* k, const void* a, const void* b, void* c, PackedOps* ops); // false: not fit for a burst (alignment)
+// the batch kernel of a burst: pack p takes its operands from ring[3 * p ...], the number of packs from *count (at most capacity)
+int packed_launch_burst(Kernel* k, const void* ring, const unsigned long long* count, int capacity, void* stream, const char** name);
 
 int verbosity();
 bool once(int* flag);   // true the first time

@@ -581,6 +581,35 @@ void* adopt_kernel(Kernel* k)
 }
 }
 
+namespace xsmm {
+void* registry_dispatch(const void* desc, size_t size, int tag, Kernel* (*make)(const void* desc))
+{
+  if (nullptr == desc || 0 == size || size + 1 > LIBXSMM_DESCRIPTOR_MAXSIZE || nullptr == make) return nullptr;
+  libxsmm_init();
+  if (LIBXSMM_TARGET_ARCH_GENERIC == g_target_archid.load()) return nullptr; // LIBXSMM_TARGET=generic: JIT disabled
+  Key key; memset(&key, 0, sizeof(key));
+  memcpy(key.bytes, desc, size);
+  key.bytes[LIBXSMM_DESCRIPTOR_MAXSIZE - 1] = (unsigned char)(0x80 | tag); // (GEMM keys end in zeros)
+  Registry& r = registry();
+  {
+    std::shared_lock<std::shared_mutex> guard(r.lock);
+    auto it = r.by_desc.find(key);
+    if (it != r.by_desc.end()) return it->second->thunk;
+  }
+  Kernel* const k = make(desc);
+  if (nullptr == k) return nullptr;
+  std::unique_lock<std::shared_mutex> guard(r.lock);
+  auto it = r.by_desc.find(key);
+  if (it != r.by_desc.end()) { packed_destroy(k->packed); delete k; return it->second->thunk; } // (another thread was faster; its payload is the same)
+  k->registered = true;
+  k->thunk = make_thunk(k);
+  if (nullptr == k->thunk) { packed_destroy(k->packed); delete k; return nullptr; }
+  r.by_desc.emplace(key, k);
+  r.by_thunk.emplace(k->thunk, k);
+  return k->thunk;
+}
+}
+
 LIBXSMM_API libxsmm_dmmfunction libxsmm_create_dcsr_reg(const libxsmm_gemm_descriptor* descriptor,
   const unsigned int* row_ptr, const unsigned int* column_idx, const double* values)
 {
@@ -624,6 +653,7 @@ LIBXSMM_API void libxsmm_release_kernel(const void* jit_kernel)
   if (device_ready()) (void)stream_sync();
   dev_free(k->d_rowptr); dev_free(k->d_colidx); dev_free(k->d_values);
   if (nullptr != k->text) text_kernel_destroy(k->text);
+  if (nullptr != k->packed) packed_destroy(k->packed);
   free_thunk(k->thunk);
   delete k;
 }
@@ -633,14 +663,14 @@ LIBXSMM_API int libxsmm_get_kernel_kind(const void* kernel, libxsmm_kernel_kind*
 {
   if (nullptr == kernel || nullptr == kind) return EXIT_FAILURE;
   const Kernel* const k = kernel_from_pointer(kernel);
-  *kind = (nullptr != k ? LIBXSMM_KERNEL_KIND_MATMUL : LIBXSMM_KERNEL_KIND_INVALID);
+  *kind = (nullptr == k ? LIBXSMM_KERNEL_KIND_INVALID : (KC_PACKED == k->kclass ? (libxsmm_kernel_kind)packed_kind(k) : LIBXSMM_KERNEL_KIND_MATMUL));
   return nullptr != k ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 LIBXSMM_API int libxsmm_get_mmkernel_info(libxsmm_xmmfunction kernel, libxsmm_mmkernel_info* info, size_t* code_size)
 {
   const Kernel* const k = kernel_from_pointer(reinterpret_cast<const void*>(kernel.xmm));
-  if (nullptr == k || (nullptr == info && nullptr == code_size)) {
+  if (nullptr == k || KC_PACKED == k->kclass || (nullptr == info && nullptr == code_size)) { // (a packed kernel is no matrix multiplication kernel)
     static int error_once = 0;
     if (0 != libxsmm_verbosity && once(&error_once)) fprintf(stderr, "LIBXSMM ERROR: invalid argument!\n");
     return EXIT_FAILURE;
