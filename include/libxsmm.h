@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <assert.h> /* (the reference pulls it in through libxsmm_macros.h; samples/transpose relies on that) */
 
 /* ---------------------------------------------------------------------------------------------
  * configuration (reference: generated include/libxsmm_config.h; defaults per SURVEY.md Appendix C)
@@ -435,6 +436,69 @@ LIBXSMM_API libxsmm_pgemm_xfunction libxsmm_dispatch_pgemm(const libxsmm_pgemm_d
 LIBXSMM_API libxsmm_getrf_xfunction libxsmm_dispatch_getrf(const libxsmm_getrf_descriptor* descriptor);
 LIBXSMM_API libxsmm_trmm_xfunction libxsmm_dispatch_trmm(const libxsmm_trmm_descriptor* descriptor);
 LIBXSMM_API libxsmm_trsm_xfunction libxsmm_dispatch_trsm(const libxsmm_trsm_descriptor* descriptor);
+
+/* ---------------------------------------------------------------------------------------------
+ * matrix copy and transposition (src/template/libxsmm.h:259-263,333-363; src/libxsmm_xcopy.c). Column major:
+ *   matcopy  out[j*ldo+i] = in[j*ldi+i] for i < m, j < n; in == NULL zeroes the destination; the elements between m and
+ *            ldo are never written; prefetch is accepted and ignored
+ *   otrans   out[i*ldo+j] = in[j*ldi+i]; out == in with ldi == ldo is the in-place transposition (libxsmm_itrans)
+ *   itrans   in place, m == n only (src/libxsmm_xcopy.c:381-423)
+ * Any typesize from 1 to 255; elements move as integers (NaN payloads, -0 and denormals keep their bits). Argument checks
+ * are the reference's (src/libxsmm_xcopy.c:174-177,295-298,386-421): on a violation nothing is written and one line goes
+ * to stderr, once per process and entry point, if the verbosity is not zero. The work runs on the GPU: operands in device
+ * memory are processed in place, asynchronously on the calling thread's stream; memory the CPU addresses as well
+ * (libxsmm_malloc) is processed in place and complete on return; pageable host memory is staged (complete on return, the
+ * padding of a pitched destination keeps its bytes). Task tid of nthreads (_thread forms) moves its share: a range of the
+ * n columns (matcopy) or of the m rows of the input (otrans); the shares are disjoint and cover the matrix, calls from
+ * concurrent threads are safe. The _omp forms do the whole matrix in one call. Inside libxsmm_amd_defer_begin/end these
+ * calls are not recorded: they seal the open burst first, so everything runs in call order.
+ * Dispatched kernels: kernel(in, &ldi, out, &ldo). A transposition kernel takes ldi from the call and m, n, ldo and the
+ * typesize from its descriptor; a matcopy kernel takes everything from its descriptor (normalised to typesize 4 as in
+ * src/libxsmm_generator.c:356-381, which libxsmm_get_mcopykernel_info reports), ignores `in` with
+ * LIBXSMM_MATCOPY_FLAG_ZERO_SOURCE and tolerates a fifth (prefetch) argument.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct libxsmm_mcopy_descriptor libxsmm_mcopy_descriptor; /* opaque; src/libxsmm_main.h:171-182 */
+typedef struct libxsmm_trans_descriptor libxsmm_trans_descriptor; /* src/libxsmm_main.h:185-190 */
+typedef enum libxsmm_matcopy_flags { LIBXSMM_MATCOPY_FLAG_ZERO_SOURCE = 1 } libxsmm_matcopy_flags; /* include/libxsmm_typedefs.h:265-268 */
+/* include/libxsmm_typedefs.h:572-577 */
+typedef void (*libxsmm_xmcopyfunction)(const void* in, const unsigned int* ldi, void* out, const unsigned int* ldo, ...);
+typedef void (*libxsmm_xtransfunction)(const void* in, const unsigned int* ldi, void* out, const unsigned int* ldo);
+typedef struct libxsmm_transkernel_info { /* include/libxsmm_typedefs.h:610-615 */
+  unsigned int ldo, m, n;
+  unsigned int typesize;
+} libxsmm_transkernel_info;
+typedef struct libxsmm_mcopykernel_info { /* include/libxsmm_typedefs.h:618-627 */
+  unsigned int ldi, ldo, m, n;
+  unsigned int typesize;
+  int prefetch;
+  int flags;
+} libxsmm_mcopykernel_info;
+/* include/libxsmm_generator.h:94-100; mcopy: NULL unless typesize is a multiple of 4; unroll: NULL or <= 0 selects 2, at most 64 */
+LIBXSMM_API libxsmm_trans_descriptor* libxsmm_trans_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, unsigned int m, unsigned int n, unsigned int ldo);
+LIBXSMM_API libxsmm_mcopy_descriptor* libxsmm_mcopy_descriptor_init(libxsmm_descriptor_blob* blob,
+  unsigned int typesize, unsigned int m, unsigned int n, unsigned int ldo,
+  unsigned int ldi, int flags, int prefetch, const int* unroll);
+/* src/template/libxsmm.h:259-263; registered kernels: NULL for a NULL descriptor or one no call could satisfy (an extent of zero, ldo too small) */
+LIBXSMM_API libxsmm_xmcopyfunction libxsmm_dispatch_mcopy(const libxsmm_mcopy_descriptor* descriptor);
+LIBXSMM_API libxsmm_xtransfunction libxsmm_dispatch_trans(const libxsmm_trans_descriptor* descriptor);
+/* src/template/libxsmm.h:113-117 */
+LIBXSMM_API int libxsmm_get_transkernel_info(libxsmm_xtransfunction kernel, libxsmm_transkernel_info* info, size_t* code_size);
+LIBXSMM_API int libxsmm_get_mcopykernel_info(libxsmm_xmcopyfunction kernel, libxsmm_mcopykernel_info* info, size_t* code_size);
+/* src/template/libxsmm.h:333-363 */
+LIBXSMM_API void libxsmm_matcopy(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, const int* prefetch);
+LIBXSMM_API void libxsmm_matcopy_thread(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, const int* prefetch, int tid, int nthreads);
+LIBXSMM_APIEXT void libxsmm_matcopy_omp(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, const int* prefetch);
+LIBXSMM_API void libxsmm_otrans(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo);
+LIBXSMM_API void libxsmm_otrans_thread(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, int tid, int nthreads);
+LIBXSMM_APIEXT void libxsmm_otrans_omp(void* out, const void* in, unsigned int typesize,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo);
+LIBXSMM_API void libxsmm_itrans(void* inout, unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ld);
 
 /* introspection (src/template/libxsmm.h:107-121) */
 LIBXSMM_API int libxsmm_get_kernel_kind(const void* kernel, libxsmm_kernel_kind* kind);

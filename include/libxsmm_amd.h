@@ -268,4 +268,26 @@ LIBXSMM_API int libxsmm_amd_packed_execute_batch(const void* kernel, const void*
  *  works on its matrix in global memory). */
 LIBXSMM_API int libxsmm_amd_packed_kernel_source(const void* descriptor, int kind, char* buffer, size_t buffer_size, int compile);
 
+/* ---- stacks of small matrices: copy and transposition (libxsmm_matcopy / libxsmm_otrans, see libxsmm.h) ---------- */
+/** `batch` items of m x n elements of typesize bytes (1 ... 255), one launch. Item g of the strided forms starts
+ *  g * stride_in (stride_out) elements behind `in` (`out`); the pointer forms take one pointer per item, the arrays in host
+ *  or in device memory, the items in memory the GPU reaches, aligned to the largest power of two (up to 16) that divides
+ *  typesize. matcopy: out_g[j*ldo+i] = in_g[j*ldi+i], m <= ldi and m <= ldo, `in` == NULL zeroes the items; otrans:
+ *  out_g[i*ldo+j] = in_g[j*ldi+i], m <= ldi and n <= ldo. The items of `out` must not overlap each other (strided forms:
+ *  stride_out is checked against the extent of an item) or any item of `in`, with one exception: otrans with out == in
+ *  (pointer form: the same array), equal strides, ldi == ldo and m == n transposes every item in place. What lies between the
+ *  items, and between the columns of an item, keeps its bytes. Device operands: asynchronous on the calling thread's stream;
+ *  strided operands in pageable host memory are staged and complete on return. batch == 0 (or m == 0, or n == 0) succeeds
+ *  and does nothing; a negative batch, a leading dimension or stride that is too small, or a NULL operand fails before
+ *  anything is written. Inside libxsmm_amd_defer_begin/end the calls are not recorded: they seal the open burst and run in
+ *  call order. Returns EXIT_SUCCESS/EXIT_FAILURE. */
+LIBXSMM_API int libxsmm_amd_matcopy_batch(void* out, const void* in, unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n,
+  libxsmm_blasint ldi, libxsmm_blasint ldo, long long stride_in, long long stride_out, long long batch);
+LIBXSMM_API int libxsmm_amd_otrans_batch(void* out, const void* in, unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n,
+  libxsmm_blasint ldi, libxsmm_blasint ldo, long long stride_in, long long stride_out, long long batch);
+LIBXSMM_API int libxsmm_amd_matcopy_batch_ptr(void* const out[], const void* const in[], unsigned int typesize, libxsmm_blasint m,
+  libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, long long batch);
+LIBXSMM_API int libxsmm_amd_otrans_batch_ptr(void* const out[], const void* const in[], unsigned int typesize, libxsmm_blasint m,
+  libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, long long batch);
+
 #endif /* LIBXSMM_AMD_H */

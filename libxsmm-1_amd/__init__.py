@@ -33,6 +33,15 @@ class MMKernelInfo(C.Structure):  # libxsmm_mmkernel_info
                 ("m", C.c_uint), ("n", C.c_uint), ("k", C.c_uint), ("flags", C.c_int)]
 
 
+class TransKernelInfo(C.Structure):  # libxsmm_transkernel_info
+    _fields_ = [("ldo", C.c_uint), ("m", C.c_uint), ("n", C.c_uint), ("typesize", C.c_uint)]
+
+
+class McopyKernelInfo(C.Structure):  # libxsmm_mcopykernel_info
+    _fields_ = [("ldi", C.c_uint), ("ldo", C.c_uint), ("m", C.c_uint), ("n", C.c_uint), ("typesize", C.c_uint),
+                ("prefetch", C.c_int), ("flags", C.c_int)]
+
+
 class RegistryInfo(C.Structure):
     _fields_ = [("capacity", C.c_size_t), ("size", C.c_size_t), ("nbytes", C.c_size_t),
                 ("nstatic", C.c_size_t), ("ncache", C.c_size_t)]
@@ -283,6 +292,23 @@ def _declare(L):
     sig("libxsmm_amd_packed_width", i, u)
     sig("libxsmm_amd_packed_execute_batch", i, vp, vp, vp, vp, ll)
     sig("libxsmm_amd_packed_kernel_source", i, vp, i, vp, C.c_size_t, i)
+    sig("libxsmm_trans_descriptor_init", vp, C.POINTER(DescriptorBlob), u, u, u, u)
+    sig("libxsmm_mcopy_descriptor_init", vp, C.POINTER(DescriptorBlob), u, u, u, u, u, i, i, c_int_p)
+    sig("libxsmm_dispatch_mcopy", vp, vp)
+    sig("libxsmm_dispatch_trans", vp, vp)
+    sig("libxsmm_get_transkernel_info", i, vp, C.POINTER(TransKernelInfo), C.POINTER(C.c_size_t))
+    sig("libxsmm_get_mcopykernel_info", i, vp, C.POINTER(McopyKernelInfo), C.POINTER(C.c_size_t))
+    for nm in ("libxsmm_matcopy", "libxsmm_matcopy_omp"):
+        sig(nm, None, vp, vp, u, i, i, i, i, c_int_p)
+    sig("libxsmm_matcopy_thread", None, vp, vp, u, i, i, i, i, c_int_p, i, i)
+    for nm in ("libxsmm_otrans", "libxsmm_otrans_omp"):
+        sig(nm, None, vp, vp, u, i, i, i, i)
+    sig("libxsmm_otrans_thread", None, vp, vp, u, i, i, i, i, i, i)
+    sig("libxsmm_itrans", None, vp, u, i, i, i)
+    for nm in ("libxsmm_amd_matcopy_batch", "libxsmm_amd_otrans_batch"):
+        sig(nm, i, vp, vp, u, i, i, i, i, ll, ll, ll)
+    for nm in ("libxsmm_amd_matcopy_batch_ptr", "libxsmm_amd_otrans_batch_ptr"):
+        sig(nm, i, vp, vp, u, i, i, i, i, ll)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -478,6 +504,85 @@ def unpack(packed, nmat, rows, cols, ld, layout=COL_MAJOR, vlen=None):
     lines = packed.reshape(npacks, nl, ld, vlen)[:, :, :cd, :].transpose(0, 3, 1, 2).reshape(npacks * vlen, nl, cd)
     mats = lines.transpose(0, 2, 1) if layout == COL_MAJOR else lines
     return np.ascontiguousarray(mats[:nmat])
+
+
+# ---- matrix copy and transposition (libxsmm_matcopy / otrans / itrans, libxsmm_dispatch_mcopy / _trans, stack forms) ------
+KIND_MCOPY, KIND_TRANS = 1, 2  # libxsmm_kernel_kind
+MATCOPY_FLAG_ZERO_SOURCE = 1
+
+
+def matcopy(out, inp, typesize, m, n, ldi, ldo, prefetch=None, tid=None, nthreads=None, omp=False):
+    """libxsmm_matcopy[_thread|_omp]: out[j*ldo+i] = in[j*ldi+i]; inp None zeroes the destination (tid given: the _thread form)"""
+    L = lib()
+    if tid is not None:
+        L.libxsmm_matcopy_thread(dptr(out), dptr(inp), typesize, m, n, ldi, ldo, iptr(prefetch), tid, nthreads)
+    else:
+        (L.libxsmm_matcopy_omp if omp else L.libxsmm_matcopy)(dptr(out), dptr(inp), typesize, m, n, ldi, ldo, iptr(prefetch))
+
+
+def otrans(out, inp, typesize, m, n, ldi, ldo, tid=None, nthreads=None, omp=False):
+    """libxsmm_otrans[_thread|_omp]: out[i*ldo+j] = in[j*ldi+i] (tid given: the _thread form)"""
+    L = lib()
+    if tid is not None:
+        L.libxsmm_otrans_thread(dptr(out), dptr(inp), typesize, m, n, ldi, ldo, tid, nthreads)
+    else:
+        (L.libxsmm_otrans_omp if omp else L.libxsmm_otrans)(dptr(out), dptr(inp), typesize, m, n, ldi, ldo)
+
+
+def itrans(inout, typesize, m, n, ld):
+    """libxsmm_itrans: in place, m == n"""
+    lib().libxsmm_itrans(dptr(inout), typesize, m, n, ld)
+
+
+def trans_descriptor(typesize, m, n, ldo):
+    """libxsmm_trans_descriptor_init -> (blob, pointer)"""
+    blob = DescriptorBlob()
+    return blob, lib().libxsmm_trans_descriptor_init(C.byref(blob), typesize, m, n, ldo)
+
+
+def mcopy_descriptor(typesize, m, n, ldo, ldi, flags=0, prefetch=0, unroll=None):
+    """libxsmm_mcopy_descriptor_init -> (blob, pointer); pointer is None unless typesize is a multiple of 4"""
+    blob = DescriptorBlob()
+    return blob, lib().libxsmm_mcopy_descriptor_init(C.byref(blob), typesize, m, n, ldo, ldi, flags, prefetch, iptr(unroll))
+
+
+def trans_dispatch(desc):
+    """libxsmm_dispatch_trans: kernel(in, &ldi, out, &ldo), None for a NULL or unusable descriptor"""
+    return lib().libxsmm_dispatch_trans(desc)
+
+
+def mcopy_dispatch(desc):
+    """libxsmm_dispatch_mcopy: kernel(in, &ldi, out, &ldo[, prefetch])"""
+    return lib().libxsmm_dispatch_mcopy(desc)
+
+
+def call_xcopy_kernel(fn_ptr, inp, ldi, out, ldo, prefetch=False):
+    """Call a dispatched mcopy / trans kernel through its bare pointer (prefetch: pass a fifth argument, as matcopy callers may)."""
+    li, lo = C.c_uint(ldi), C.c_uint(ldo)
+    if prefetch:
+        C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)(fn_ptr)(dptr(inp), C.addressof(li), dptr(out), C.addressof(lo), dptr(inp))
+    else:
+        C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)(fn_ptr)(dptr(inp), C.addressof(li), dptr(out), C.addressof(lo))
+
+
+def matcopy_batch(out, inp, typesize, m, n, ldi, ldo, stride_in, stride_out, batch):
+    """libxsmm_amd_matcopy_batch: `batch` items, strides in elements, one launch; inp None zeroes the items"""
+    return lib().libxsmm_amd_matcopy_batch(dptr(out), dptr(inp), typesize, m, n, ldi, ldo, stride_in, stride_out, batch)
+
+
+def otrans_batch(out, inp, typesize, m, n, ldi, ldo, stride_in, stride_out, batch):
+    """libxsmm_amd_otrans_batch (out == inp with equal strides, ldi == ldo and m == n: every item in place)"""
+    return lib().libxsmm_amd_otrans_batch(dptr(out), dptr(inp), typesize, m, n, ldi, ldo, stride_in, stride_out, batch)
+
+
+def matcopy_batch_ptr(out_ptrs, in_ptrs, typesize, m, n, ldi, ldo, batch):
+    """libxsmm_amd_matcopy_batch_ptr: arrays of item pointers (int64 numpy arrays or device tensors); in_ptrs None zeroes the items"""
+    return lib().libxsmm_amd_matcopy_batch_ptr(dptr(out_ptrs), dptr(in_ptrs), typesize, m, n, ldi, ldo, batch)
+
+
+def otrans_batch_ptr(out_ptrs, in_ptrs, typesize, m, n, ldi, ldo, batch):
+    """libxsmm_amd_otrans_batch_ptr"""
+    return lib().libxsmm_amd_otrans_batch_ptr(dptr(out_ptrs), dptr(in_ptrs), typesize, m, n, ldi, ldo, batch)
 
 
 def call_kernel(fn_ptr, a, b, c, x3=None):

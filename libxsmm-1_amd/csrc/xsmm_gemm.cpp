@@ -692,6 +692,7 @@ void call_kernel(Kernel* k, const void* a, const void* b, void* c, const void* x
 {
   if (nullptr == k) return;
   if (KC_PACKED == k->kclass) { packed_call(k, a, b, c); return; } // kernel(a, b, c) over one pack (xsmm_packed.cpp)
+  if (KC_XCOPY == k->kclass) { xcopy_call(k, a, b, c, x3); return; } // kernel(in, &ldi, out, &ldo) (xsmm_xcopy.cpp)
   if (KC_LOWP == k->kclass && 0 != (k->desc.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE)) { // kernel(a[], b[], c, &count): bf16 batch-reduce
     if (nullptr == x3 || nullptr == a || nullptr == b || nullptr == c) return;
     const unsigned long long count = *static_cast<const unsigned long long*>(x3);
@@ -795,7 +796,7 @@ LIBXSMM_API int libxsmm_mmbatch_kernel(libxsmm_xmmfunction kernel, libxsmm_blasi
 { // reference src/libxsmm_gemm.c:1315-1324: task `tid` of `ntasks` owns the slice [tid*tasksize, min(...))
   (void)itypesize; (void)otypesize; (void)flags;
   Kernel* const k = kernel_from_pointer(reinterpret_cast<const void*>(kernel.xmm));
-  if (nullptr == k || KC_CSR_REG == k->kclass || KC_TEXT == k->kclass || KC_PACKED == k->kclass || nullptr == a || nullptr == b || nullptr == c || ntasks < 1 || tid < 0 || tid >= ntasks) return EXIT_FAILURE;
+  if (nullptr == k || KC_CSR_REG == k->kclass || KC_TEXT == k->kclass || KC_PACKED == k->kclass || KC_XCOPY == k->kclass || nullptr == a || nullptr == b || nullptr == c || ntasks < 1 || tid < 0 || tid >= ntasks) return EXIT_FAILURE;
   const long long size = (batchsize < 0 ? -(long long)batchsize : batchsize);
   const long long tasksize = (size + ntasks - 1) / ntasks;
   const long long begin = (long long)tid * tasksize, span = begin + tasksize, end = (span < size ? span : size);

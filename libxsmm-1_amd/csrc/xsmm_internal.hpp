@@ -207,7 +207,8 @@ void* scratch(int slot, size_t bytes);
 
 enum KernelClass : int { KC_DENSE = 0, KC_REDUCE = 1, KC_CSR_REG = 2, KC_TEXT = 3 /* pattern kernel compiled from generated text (SOA family) */,
   KC_LOWP = 4 /* i16 / bf16 inputs (kernels/smm_lowp.hip) */,
-  KC_PACKED = 5 /* pgemm / getrf / trmm / trsm over packs of interleaved matrices (xsmm_packed.cpp) */ };
+  KC_PACKED = 5 /* pgemm / getrf / trmm / trsm over packs of interleaved matrices (xsmm_packed.cpp) */,
+  KC_XCOPY = 6 /* matrix copy / transposition kernels (libxsmm_dispatch_mcopy / _trans, xsmm_xcopy.cpp) */ };
 
 struct Kernel {                 // what a dispatched function pointer stands for
   libxsmm_gemm_descriptor desc;
@@ -221,6 +222,9 @@ struct Kernel {                 // what a dispatched function pointer stands for
   void* text = nullptr;
   // KC_PACKED payload (xsmm_packed.cpp); desc is not used
   void* packed = nullptr;
+  // KC_XCOPY payload: the descriptor's fields (mcopy: normalised to typesize 4 as the reference does); desc is not used
+  int xkind = 0;                // LIBXSMM_KERNEL_KIND_MCOPY or _TRANS
+  unsigned xm = 0, xn = 0, xldi = 0, xldo = 0, xtypesize = 0, xflags = 0, xprefetch = 0;
 };
 
 Kernel* kernel_from_pointer(const void* fn);           // NULL if fn is not one of ours
@@ -243,6 +247,26 @@ struct PackedOps { const void* rd[2]; size_t rd_bytes[2]; void* wr; size_t wr_by
 bool packed_operands(const Kernel* k, const void* a, const void* b, void* c, PackedOps* ops); // false: not fit for a burst (alignment)
 // the batch kernel of a burst: pack p takes its operands from ring[3 * p ...], the number of packs from *count (at most capacity)
 int packed_launch_burst(Kernel* k, const void* ring, const unsigned long long* count, int capacity, void* stream, const char** name);
+
+// matrix copy / transposition (xsmm_xcopy.cpp, kernels/xcopy.hip)
+void xcopy_call(Kernel* k, const void* in, const void* ldi, void* out, const void* ldo); // what the thunk of an mcopy / trans kernel does
+// A stack of items for the kernels of kernels/xcopy.hip, every length in units of `unit` bytes (an element is P units).
+struct StackMove {
+  const void* in; void* out;    // first items, or arrays of item pointers (ptrs != 0)
+  long long sin, sout;          // units from one item to the next (ptrs == 0)
+  long long ldi, ldo;           // units from one column to the next
+  int m, n, P;                  // rows, columns (of the input; copy: of both), units per element
+  int mp, G;                    // through LDS: units per column of an item's image, items per chunk (0: not through LDS)
+  long long batch;
+  int ptrs;
+  int s1[3], s2[4]; long long sg; // filled in by the launcher: the steps of the kernels' running indexes
+};
+enum { XCOPY_STACK_TRANS = 0, XCOPY_STACK_COPY = 1, XCOPY_STACK_SWAP = 2 };
+// all return hipError_t as int; unit: 1, 2, 4, 8 or 16 bytes, every address and pitch a multiple of it
+int launch_xcopy_trans(int unit, const void* in, void* out, int m, int n, long long ldi, long long ldo, bool vec_in, bool vec_out, void* stream); // element = unit; vec_*: that side's base and pitch are multiples of 16 bytes
+int launch_xcopy_itrans(int unit, void* inout, int n, long long ld, bool vec, void* stream);
+int launch_xcopy_copy(int unit, const void* in, void* out, long long rowbytes, long long ncols, long long pitch_in, long long pitch_out, void* stream); // pitches in bytes; in == nullptr: zeros
+int launch_xcopy_stack(int unit, const StackMove& args, int op, void* stream, const char** name);
 
 int verbosity();
 bool once(int* flag);   // true the first time

@@ -663,14 +663,15 @@ LIBXSMM_API int libxsmm_get_kernel_kind(const void* kernel, libxsmm_kernel_kind*
 {
   if (nullptr == kernel || nullptr == kind) return EXIT_FAILURE;
   const Kernel* const k = kernel_from_pointer(kernel);
-  *kind = (nullptr == k ? LIBXSMM_KERNEL_KIND_INVALID : (KC_PACKED == k->kclass ? (libxsmm_kernel_kind)packed_kind(k) : LIBXSMM_KERNEL_KIND_MATMUL));
+  *kind = (nullptr == k ? LIBXSMM_KERNEL_KIND_INVALID : (KC_PACKED == k->kclass ? (libxsmm_kernel_kind)packed_kind(k) :
+    (KC_XCOPY == k->kclass ? (libxsmm_kernel_kind)k->xkind : LIBXSMM_KERNEL_KIND_MATMUL)));
   return nullptr != k ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 LIBXSMM_API int libxsmm_get_mmkernel_info(libxsmm_xmmfunction kernel, libxsmm_mmkernel_info* info, size_t* code_size)
 {
   const Kernel* const k = kernel_from_pointer(reinterpret_cast<const void*>(kernel.xmm));
-  if (nullptr == k || KC_PACKED == k->kclass || (nullptr == info && nullptr == code_size)) { // (a packed kernel is no matrix multiplication kernel)
+  if (nullptr == k || KC_PACKED == k->kclass || KC_XCOPY == k->kclass || (nullptr == info && nullptr == code_size)) { // (packed, copy and transposition kernels are no matrix multiplication kernels)
     static int error_once = 0;
     if (0 != libxsmm_verbosity && once(&error_once)) fprintf(stderr, "LIBXSMM ERROR: invalid argument!\n");
     return EXIT_FAILURE;
@@ -684,6 +685,43 @@ LIBXSMM_API int libxsmm_get_mmkernel_info(libxsmm_xmmfunction kernel, libxsmm_mm
     info->m = k->desc.m; info->n = k->desc.n; info->k = k->desc.k;
   }
   if (nullptr != code_size) *code_size = THUNK_SIZE;
+  return EXIT_SUCCESS;
+}
+
+namespace {
+const Kernel* xcopy_kernel_info(const void* fn, int kind, bool has_out, size_t* code_size)
+{ // src/libxsmm_main.c:2013-2087
+  static int error_once = 0;
+  if (!has_out) {
+    if (0 != libxsmm_verbosity && once(&error_once)) fprintf(stderr, "LIBXSMM ERROR: invalid argument!\n");
+    return nullptr;
+  }
+  const Kernel* const k = kernel_from_pointer(fn);
+  if (nullptr == k || KC_XCOPY != k->kclass || kind != k->xkind) {
+    if (0 != libxsmm_verbosity && once(&error_once)) fprintf(stderr, "LIBXSMM ERROR: invalid kernel cannot be inspected!\n");
+    return nullptr;
+  }
+  if (nullptr != code_size) *code_size = THUNK_SIZE;
+  return k;
+}
+}
+
+LIBXSMM_API int libxsmm_get_transkernel_info(libxsmm_xtransfunction kernel, libxsmm_transkernel_info* info, size_t* code_size)
+{
+  const Kernel* const k = xcopy_kernel_info(reinterpret_cast<const void*>(kernel), LIBXSMM_KERNEL_KIND_TRANS, nullptr != info || nullptr != code_size, code_size);
+  if (nullptr == k) return EXIT_FAILURE;
+  if (nullptr != info) { info->typesize = k->xtypesize; info->ldo = k->xldo; info->m = k->xm; info->n = k->xn; }
+  return EXIT_SUCCESS;
+}
+
+LIBXSMM_API int libxsmm_get_mcopykernel_info(libxsmm_xmcopyfunction kernel, libxsmm_mcopykernel_info* info, size_t* code_size)
+{
+  const Kernel* const k = xcopy_kernel_info(reinterpret_cast<const void*>(kernel), LIBXSMM_KERNEL_KIND_MCOPY, nullptr != info || nullptr != code_size, code_size);
+  if (nullptr == k) return EXIT_FAILURE;
+  if (nullptr != info) {
+    info->typesize = k->xtypesize; info->prefetch = (int)k->xprefetch; info->flags = (int)k->xflags;
+    info->ldi = k->xldi; info->ldo = k->xldo; info->m = k->xm; info->n = k->xn;
+  }
   return EXIT_SUCCESS;
 }
 
