@@ -43,9 +43,14 @@
 
 namespace xsmm {
 
-thread_local bool tl_defer_open = false;
-
 namespace {
+
+// WHAT IS OPEN ON THIS THREAD. Calls are recorded in three forms -- a burst (this file), a record of batch calls (xsmm_gemm.cpp),
+// a record of spmdm block calls (xsmm_sparse.cpp) -- and everything recorded has to reach the stream in call order. So at most
+// one kind is open at a time: record_begin(kind) launches whatever else is open before kind opens, and whoever asks for the
+// stream (device()) launches what is open. record_flush() takes the kind off BEFORE it runs the kind's flush function: the
+// launches of a flush ask for the stream themselves and must find nothing open. This is the only file that assigns tl_open.
+thread_local OpenKind tl_open = OPEN_NONE;
 
 constexpr unsigned long long SEALED = 1ULL << 63;
 constexpr int DEFER_CAP = 8192;    // calls per burst
@@ -86,6 +91,16 @@ bool g_helper_started = false;
 
 long long now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// the burst in slot s of r takes no more calls (the helper when the calls have stopped coming, the owner at its flush)
+void seal(Ring& r, int s)
+{
+  std::atomic<unsigned long long>& w = *r.slot[s].word;
+  unsigned long long v = w.load(std::memory_order_relaxed);
+  while (0 == (v & SEALED) && !w.compare_exchange_weak(v, v | SEALED, std::memory_order_release, std::memory_order_relaxed)) {}
+  int expect = s; // (whoever takes the burst off the helper's list lowers the count)
+  if (r.open_slot.compare_exchange_strong(expect, -1, std::memory_order_acq_rel)) g_open_bursts.fetch_sub(1, std::memory_order_acq_rel);
+}
+
 void helper_loop()
 {
   // (sleeps of a few microseconds: the default timer slack of a thread, 50 us, would add that much to the latency of a caller who
@@ -103,13 +118,7 @@ void helper_loop()
         std::lock_guard<std::mutex> guard(g_rings_lock);
         for (Ring* r : g_rings) {
           const int s = r->open_slot.load(std::memory_order_acquire);
-          if (0 <= s && t - r->last_ns.load(std::memory_order_relaxed) > IDLE_NS) {
-            std::atomic<unsigned long long>& w = *r->slot[s].word;
-            unsigned long long v = w.load(std::memory_order_relaxed);
-            while (0 == (v & SEALED) && !w.compare_exchange_weak(v, v | SEALED, std::memory_order_release, std::memory_order_relaxed)) {}
-            int expect = s; // (the owner finds the bit at its next call, or in defer_flush)
-            if (r->open_slot.compare_exchange_strong(expect, -1, std::memory_order_acq_rel)) g_open_bursts.fetch_sub(1, std::memory_order_acq_rel);
-          }
+          if (0 <= s && t - r->last_ns.load(std::memory_order_relaxed) > IDLE_NS) seal(*r, s); // (the owner finds the bit at its next call, or at its flush)
         }
       }
       std::this_thread::sleep_for(std::chrono::microseconds(2));
@@ -121,7 +130,7 @@ struct RingHolder {
   Ring* ring = nullptr;
   ~RingHolder() {
     if (nullptr == ring) return;
-    if (tl_defer_open) defer_flush();
+    if (OPEN_BURST == tl_open) record_flush(); // (a batch or spmdm record that is still open is dropped: DESIGN.md, section 1)
     std::lock_guard<std::mutex> guard(g_rings_lock);
     g_rings_idle.push_back(ring);
   }
@@ -191,117 +200,92 @@ Range device_range(const void* p)
 
 void close_burst(Ring& r)
 { // caller side: the burst takes no more calls
-  if (0 <= r.mine) {
-    std::atomic<unsigned long long>& w = *r.slot[r.mine].word;
-    unsigned long long v = w.load(std::memory_order_relaxed);
-    while (0 == (v & SEALED) && !w.compare_exchange_weak(v, v | SEALED, std::memory_order_release, std::memory_order_relaxed)) {}
-    int expect = r.mine; // (whoever takes the burst off the helper's list lowers the count)
-    if (r.open_slot.compare_exchange_strong(expect, -1, std::memory_order_acq_rel)) g_open_bursts.fetch_sub(1, std::memory_order_acq_rel);
-  }
-  tl_defer_open = false;
+  if (0 <= r.mine) seal(r, r.mine);
   r.mine = -1; r.kernel = nullptr; r.ncalls = 0; r.last_c = nullptr; r.panel_handle = nullptr;
 }
 
-// gate and batch kernel of a new burst are queued: the bookkeeping of the open burst
-bool burst_opened(Ring& r, Slot& sl, int s, Kernel* k, void* stream)
+// Opens a burst that holds `first` calls already: queues the gate on the caller's stream and, through launch(slot, stream, &name),
+// the batch kernel behind it. launch returns the hip error and leaves in *name what the error message calls the kernel or, when
+// it succeeded, what the launch counts as. Whatever else is open on the thread is launched first (record_begin). What the burst
+// is made of (kernel or operator, the ranges of its operands) is the caller's to fill in afterwards.
+template<typename Launch> bool open_burst(Ring& r, int first, Launch launch)
 {
-  if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)stream)) sl.pending = true; else (void)hipGetLastError();
-  sl.stream = stream;
+  Device& dev = device_raw();
+  if (capturing_now(dev.stream)) return false; // a captured gate would wait for a seal that a replay never gets
+  record_begin(OPEN_BURST);
+  const int s = r.cur;
+  Slot& sl = r.slot[s];
+  if (sl.pending) { (void)hipEventSynchronize(sl.done); sl.pending = false; } // the slot's previous burst (DEFER_SLOTS bursts ago)
+  sl.word->store((unsigned long long)first, std::memory_order_release);
+  bool ok = (0 == launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream));
+  if (ok) {
+    const char* name = "";
+    const int e = launch(sl, dev.stream, &name);
+    if (0 != e) { // (the gate is queued already: let it through with nothing recorded)
+      sl.word->store(SEALED, std::memory_order_release);
+      fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
+      ok = false;
+    }
+    else note_launch(name);
+  }
+  if (!ok) { record_flush(); return false; }
+  if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)dev.stream)) sl.pending = true; else (void)hipGetLastError();
+  sl.stream = dev.stream;
   r.cur = (s + 1) % DEFER_SLOTS;
-  r.kernel = k; r.stream = stream; r.ncalls = 0; r.last_c = nullptr; r.mine = s;
-  r.c_lo = r.a_lo = r.b_lo = ~(uintptr_t)0; r.c_hi = r.a_hi = r.b_hi = 0;
+  r.stream = dev.stream; r.ncalls = first; r.mine = s;
   r.last_ns.store(now_ns(), std::memory_order_relaxed);
   r.open_slot.store(s, std::memory_order_release);
-  tl_defer_open = true;
   if (0 == g_open_bursts.fetch_add(1, std::memory_order_acq_rel)) { std::lock_guard<std::mutex> guard(g_rings_lock); g_helper_wake.notify_one(); }
   return true;
 }
 
-// queue gate + batch kernel of a new burst on the caller's stream
-bool open_burst(Ring& r, Kernel* k)
+// the batch kernel of a burst of dense per-call kernels: the ring is an array of {a, b, c}
+int launch_dense_burst(const libxsmm_gemm_descriptor& d, Slot& sl, void* stream, const char** name)
 {
-  Device& dev = device_raw();
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipSuccess != hipStreamIsCapturing((hipStream_t)dev.stream, &capturing)) { (void)hipGetLastError(); return false; }
-  if (hipStreamCaptureStatusNone != capturing) return false; // a captured gate would wait for a seal that a replay never gets
-  const int s = r.cur;
-  Slot& sl = r.slot[s];
-  if (sl.pending) { (void)hipEventSynchronize(sl.done); sl.pending = false; } // the slot's previous burst (DEFER_SLOTS bursts ago)
-  sl.word->store(0, std::memory_order_release);
-  if (KC_PACKED == k->kclass) { // packed kernels: the same gate, the descriptor's own batch kernel behind it (pack p from entry p of the ring)
-    if (0 != launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream)) return false;
-    const char* pname = "";
-    const int pe = packed_launch_burst(k, sl.entries, sl.count, DEFER_CAP, dev.stream, &pname);
-    if (0 != pe) { // (the gate is queued already: let it through with nothing recorded)
-      sl.word->store(SEALED, std::memory_order_release);
-      fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", pname, pe);
-      return false;
-    }
-    note_launch(pname);
-    return burst_opened(r, sl, s, k, dev.stream);
-  }
   SmmBatch b; memset(&b, 0, sizeof(b));
-  const libxsmm_gemm_descriptor& d = k->desc;
   b.typesize = (LIBXSMM_GEMM_PRECISION_F64 == LIBXSMM_GETENUM_INP(d.datatype)) ? 8 : 4;
   b.m = (int)d.m; b.n = (int)d.n; b.k = (int)d.k; b.lda = (int)d.lda; b.ldb = (int)d.ldb; b.ldc = (int)d.ldc;
   b.flags = d.flags & (LIBXSMM_GEMM_FLAG_TRANS_B | LIBXSMM_GEMM_FLAG_BETA_0);
   b.alpha = 1.0; b.beta = (0 != (d.flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? 0.0 : 1.0;
-  b.mode = ADDR_POINTER; // the ring is an array of {a, b, c}: three pointer arrays with a stride of one entry
+  b.mode = ADDR_POINTER; // three pointer arrays with a stride of one entry
   b.a = &sl.entries[0].a; b.b = &sl.entries[0].b; b.c = &sl.entries[0].c; b.sa = b.sb = b.sc = (long long)sizeof(Entry);
   b.batch = DEFER_CAP; b.batch_ptr = sl.count;
   b.sync = (0 != (b.flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? SYNC_NONE : SYNC_RUNS; // consecutive calls with one C: a run, in call order
-  if (0 != launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream)) return false;
-  const char* name = "";
-  const int e = launch_smm_generic(b, dev.stream, &name);
-  if (0 != e) { // (the gate is queued already: let it through with nothing recorded)
-    sl.word->store(SEALED, std::memory_order_release);
-    fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-    return false;
-  }
-  note_launch("smm_deferred_calls");
-  return burst_opened(r, sl, s, k, dev.stream);
+  const int e = launch_smm_generic(b, stream, name);
+  if (0 == e) *name = "smm_deferred_calls";
+  return e;
 }
 
 } // namespace
 
+OpenKind record_open() { return tl_open; }
+
+void record_begin(OpenKind kind)
+{
+  if (kind == tl_open) return;
+  record_flush();
+  tl_open = kind;
+}
+
+void record_flush()
+{
+  const OpenKind kind = tl_open;
+  tl_open = OPEN_NONE; // first: the launches below ask for the stream, which flushes what is open
+  switch (kind) {
+    case OPEN_BURST: close_burst(*tl_ring.ring); break;
+    case OPEN_BATCH: batch_flush_record(); break;
+    case OPEN_SPMDM: spmdm_flush_record(); break;
+    case OPEN_NONE: break;
+  }
+}
+
 bool defer_bracket_open() { return 0 < tl_defer_bracket; }
 bool defer_capturing(void* stream) { return capturing_now(stream); }
-
-// Recorded batch calls (xsmm_gemm.cpp) leave in segments: consecutive calls that may run side by side. The rule is the one the
-// grouped pointer batches follow (xsmm_gemm.cpp: try_grouped_pointer_batches): a call's C must not meet another member's A, B
-// or C. A call that conflicts with a member of the open segment opens a new one -- it then runs behind all of them, in call order.
-int merge_segments(int n, const unsigned long long* hulls, int* segment_of)
-{
-  auto meet = [](const unsigned long long* x, const unsigned long long* y) { return x[0] < y[1] && y[0] < x[1]; }; // half-open ranges
-  int first = 0, segment = 0;
-  for (int i = 0; i < n; ++i) {
-    const unsigned long long* const hi = hulls + 6 * (size_t)i;
-    for (int j = first; j < i; ++j) {
-      const unsigned long long* const hj = hulls + 6 * (size_t)j;
-      if (meet(hi + 4, hj + 0) || meet(hi + 4, hj + 2) || meet(hi + 4, hj + 4) || meet(hj + 4, hi + 0) || meet(hj + 4, hi + 2)) {
-        first = i; ++segment;
-        break;
-      }
-    }
-    segment_of[i] = segment;
-  }
-  return 0 < n ? segment + 1 : 0;
-}
-
-void defer_flush()
-{
-  if (tl_batch_open) batch_flush_record();
-  if (tl_spmdm_open) spmdm_flush_record();
-  if (!tl_defer_open || nullptr == tl_ring.ring) { tl_defer_open = false; return; }
-  close_burst(*tl_ring.ring);
-}
 
 static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t bytes_a, const void* b, size_t bytes_b, void* c, size_t bytes_c, bool runs);
 
 bool defer_call(Kernel* k, const void* a, const void* b, void* c)
 {
-  if (tl_batch_open) batch_flush_record(); // (recorded batch calls and spmdm block calls come first: a burst runs at the stream position of its first call)
-  if (tl_spmdm_open) spmdm_flush_record();
   if (!defer_enabled() || nullptr == k || (KC_DENSE != k->kclass && KC_PACKED != k->kclass)) return false;
   if (KC_PACKED == k->kclass) { // kernel(a, b, c) over one pack: the ring keeps the arguments as they were passed, the overlap rules see
     PackedOps ops;             // the operand that is written in the place of C and what is only read in the places of A and B
@@ -329,7 +313,7 @@ static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t by
   Ring& r = *rp;
   const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), pc = reinterpret_cast<uintptr_t>(c);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (tl_defer_open) {
+    if (OPEN_BURST == tl_open) {
       bool fits = (r.kernel == k && r.stream == device_raw().stream && r.ncalls < DEFER_CAP && !capturing_now(r.stream));
       // operands inside device allocations already seen in this burst? (anything else is looked up, below, in a new burst)
       auto known = [&](uintptr_t p, size_t n) { return r.known[0].has(p, n) || r.known[1].has(p, n) || r.known[2].has(p, n); };
@@ -359,7 +343,7 @@ static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t by
         }
         // the helper has sealed the burst in the meantime
       }
-      close_burst(r);
+      record_flush();
     }
     // a new burst: where do the operands live? (driver queries: once per burst)
     if (0 != attempt) break;
@@ -372,7 +356,13 @@ static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t by
     if (!r.known[0].has(pa, bytes_a) || !r.known[1].has(pb, bytes_b) || !r.known[2].has(pc, bytes_c)) return false;
     if (pa < pc + bytes_c && pc < pa + bytes_a) return false; // (a call whose own operands overlap: left to the ordinary path)
     if (pb < pc + bytes_c && pc < pb + bytes_b) return false;
-    if (!open_burst(r, k)) return false;
+    // (recorded batch calls and spmdm block calls are launched first: a burst runs at the stream position of its first call)
+    const bool opened = (KC_PACKED == k->kclass) // packed kernels: the descriptor's own batch kernel behind the gate (pack p from entry p of the ring)
+      ? open_burst(r, 0, [k](Slot& sl, void* stream, const char** name) { return packed_launch_burst(k, sl.entries, sl.count, DEFER_CAP, stream, name); })
+      : open_burst(r, 0, [k](Slot& sl, void* stream, const char** name) { return launch_dense_burst(k->desc, sl, stream, name); });
+    if (!opened) return false;
+    r.kernel = k; r.last_c = nullptr;
+    r.c_lo = r.a_lo = r.b_lo = ~(uintptr_t)0; r.c_hi = r.a_hi = r.b_hi = 0;
   }
   return false;
 }
@@ -383,15 +373,13 @@ static bool defer_record(Kernel* k, const Entry& entry, const void* a, size_t by
 // from device memory), the following calls only count up as long as they continue the walk along the rows.
 bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, int typesize, int M, int N, int K, long long ldb, long long ldc, int vec)
 {
-  if (tl_batch_open) batch_flush_record();
-  if (tl_spmdm_open) spmdm_flush_record();
   if (!defer_enabled() || nullptr == handle || nullptr == jit || nullptr == B || nullptr == C) return false;
   Ring* const rp = my_ring();
   if (nullptr == rp) return false;
   Ring& r = *rp;
   const uintptr_t pb = reinterpret_cast<uintptr_t>(B), pc = reinterpret_cast<uintptr_t>(C);
   const size_t ts = (size_t)typesize, step = (size_t)N * ts;
-  if (tl_defer_open) {
+  if (OPEN_BURST == tl_open) {
     if (r.panel_handle == handle && r.stream == device_raw().stream && r.ncalls < r.max_panels
       && pb == r.b0 + (size_t)r.ncalls * step && pc == r.c0 + (size_t)r.ncalls * step && !capturing_now(r.stream))
     {
@@ -403,7 +391,7 @@ bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, in
         return true;
       }
     }
-    close_burst(r);
+    record_flush();
   }
   // a new burst: both panels in device memory, aligned for the kernel's vector width; how far may the walk go?
   if (0 != ((pb | pc) & (ts * (size_t)vec - 1))) return false;
@@ -422,31 +410,14 @@ bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, in
     const uintptr_t be = pb + rows_b + (size_t)maxp * step, ce = pc + rows_c + (size_t)maxp * step;
     if (pb < ce && pc < be) return false;
   }
-  Device& dev = device_raw();
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipSuccess != hipStreamIsCapturing((hipStream_t)dev.stream, &capturing)) { (void)hipGetLastError(); return false; }
-  if (hipStreamCaptureStatusNone != capturing) return false;
-  const int s = r.cur;
-  Slot& sl = r.slot[s];
-  if (sl.pending) { (void)hipEventSynchronize(sl.done); sl.pending = false; }
-  sl.word->store(1, std::memory_order_release); // this call is the burst's first panel
-  if (0 != launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream)) return false;
-  const int e = jit_launch_panels(jit, B, C, maxp * N, ldb, ldc, vec, dev.stream, sl.count, (long long)N);
-  if (0 != e) {
-    sl.word->store(SEALED, std::memory_order_release); // (the gate is queued already: let it through)
-    fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (fsspmdm operator, hip error %d)\n", e);
-    return false;
-  }
-  note_launch(8 == typesize ? "fsspmdm_f64_jit_operator_deferred" : "fsspmdm_f32_jit_operator_deferred");
-  if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)dev.stream)) sl.pending = true; else (void)hipGetLastError();
-  sl.stream = dev.stream;
-  r.cur = (s + 1) % DEFER_SLOTS;
-  r.kernel = nullptr; r.panel_handle = handle; r.stream = dev.stream; r.ncalls = 1; r.mine = s;
-  r.b0 = pb; r.c0 = pc; r.step = step; r.max_panels = (int)maxp;
-  r.last_ns.store(now_ns(), std::memory_order_relaxed);
-  r.open_slot.store(s, std::memory_order_release);
-  tl_defer_open = true;
-  if (0 == g_open_bursts.fetch_add(1, std::memory_order_acq_rel)) { std::lock_guard<std::mutex> guard(g_rings_lock); g_helper_wake.notify_one(); }
+  const bool opened = open_burst(r, 1 /* this call is the burst's first panel */, [&](Slot& sl, void* stream, const char** name) {
+    *name = "fsspmdm operator";
+    const int e = jit_launch_panels(jit, B, C, maxp * N, ldb, ldc, vec, stream, sl.count, (long long)N);
+    if (0 == e) *name = (8 == typesize ? "fsspmdm_f64_jit_operator_deferred" : "fsspmdm_f32_jit_operator_deferred");
+    return e;
+  });
+  if (!opened) return false;
+  r.panel_handle = handle; r.b0 = pb; r.c0 = pc; r.step = step; r.max_panels = (int)maxp;
   return true;
 }
 
@@ -454,20 +425,13 @@ bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, in
 
 using namespace xsmm;
 
-LIBXSMM_API void libxsmm_amd_flush(void) { defer_flush(); }
+LIBXSMM_API void libxsmm_amd_flush(void) { record_flush(); }
 LIBXSMM_API void libxsmm_amd_defer_begin(void) { ++tl_defer_bracket; }
 LIBXSMM_API void libxsmm_amd_defer_end(void)
 {
   if (0 < tl_defer_bracket) --tl_defer_bracket;
   // Recorded batch calls wait for the outermost end: a routine that brackets its own calls does not cut its caller's record.
-  // (Nothing else is open beside a batch record: a burst or spmdm block calls are flushed before a batch call is recorded.)
-  if (0 < tl_defer_bracket && tl_batch_open) return;
-  defer_flush(); // whatever was recorded is complete now: the caller may queue its own work behind it
-}
-
-LIBXSMM_API int libxsmm_amd_merge_segments(int n, const unsigned long long hulls[], int segment_of[])
-{ // see include/libxsmm_amd.h
-  if (n < 0 || (0 < n && (nullptr == hulls || nullptr == segment_of))) return -1;
-  return merge_segments(n, hulls, segment_of);
+  if (0 < tl_defer_bracket && OPEN_BATCH == tl_open) return;
+  record_flush(); // whatever was recorded is complete now: the caller may queue its own work behind it
 }
 LIBXSMM_API int libxsmm_amd_defer_active(void) { return defer_enabled() ? 1 : 0; }

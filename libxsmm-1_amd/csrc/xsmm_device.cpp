@@ -25,11 +25,11 @@ thread_local Scratch tl_scratch[8];
 
 // The engine's current stream is a per-thread setting (every entry point may be called from any thread, as in the
 // reference; a thread that never calls libxsmm_amd_set_stream launches on the default stream).
-// (Whoever asks for the stream is about to queue work or to wait for it: a burst of deferred per-call kernels that is still
-// open on this thread is sealed first, and recorded spmdm block calls and batch calls are launched, so that everything stays
-// in the order of the calls -- xsmm_defer.cpp)
+// (Whoever asks for the stream is about to queue work or to wait for it: what is open on this thread -- a burst of deferred
+// per-call kernels, recorded batch calls or spmdm block calls -- is sealed or launched first, so that everything stays in the
+// order of the calls -- xsmm_defer.cpp: record_flush)
 Device& device_raw() { thread_local Device tl_device; tl_device.count = g_device.count; return tl_device; }
-Device& device() { if (tl_defer_open || tl_spmdm_open || tl_batch_open) defer_flush(); return device_raw(); }
+Device& device() { if (OPEN_NONE != record_open()) record_flush(); return device_raw(); }
 
 bool device_ready()
 {
@@ -268,7 +268,9 @@ thread_local hipEvent_t tl_index_commits[INDEX_RING] = {};
 thread_local unsigned tl_index_next_commit = 0;
 }
 
-void* index_upload(const void* src, size_t bytes)
+void* index_upload(const void* src, size_t bytes) { return index_upload_on(device().stream, src, bytes); }
+
+void* index_upload_on(void* stream, const void* src, size_t bytes)
 {
   // An entry that was filled but not committed is waited for and taken over when the ring comes round to it: whoever holds
   // commits back -- the record of batch calls inside a bracket (xsmm_gemm.cpp: MERGE_MAX_UPLOADS), until its flush has queued
@@ -292,7 +294,7 @@ void* index_upload(const void* src, size_t bytes)
     e.size = want;
   }
   memcpy(e.host, src, bytes);
-  e.stream = device().stream;
+  e.stream = stream;
   if (hipSuccess != hipMemcpyAsync(e.dev, e.host, bytes, hipMemcpyHostToDevice, (hipStream_t)e.stream)) { (void)hipGetLastError(); return nullptr; }
   e.state = 1;
   return e.dev;

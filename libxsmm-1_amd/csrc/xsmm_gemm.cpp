@@ -492,6 +492,29 @@ void hull_of_pointers(unsigned long long* out, const void* const* ptrs, size_t n
   out[0] = lo; out[1] = hi + (unsigned long long)span * typesize;
 }
 
+// Recorded calls leave in segments: consecutive calls that may run side by side. The rule is the one the grouped pointer batches
+// follow (try_grouped_pointer_batches): a call's C must not meet another member's A, B or C. A call that conflicts with a member
+// of the open segment opens a new one -- it then runs behind all of them, in call order.
+// hulls: {a_lo, a_hi, b_lo, b_hi, c_lo, c_hi} per call, byte addresses, half-open. segment_of[i] receives the segment of call i
+// (0, 1, ...; non-decreasing); returns the number of segments.
+int merge_segments(int n, const unsigned long long* hulls, int* segment_of)
+{
+  auto meet = [](const unsigned long long* x, const unsigned long long* y) { return x[0] < y[1] && y[0] < x[1]; }; // half-open ranges
+  int first = 0, segment = 0;
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long* const hi = hulls + 6 * (size_t)i;
+    for (int j = first; j < i; ++j) {
+      const unsigned long long* const hj = hulls + 6 * (size_t)j;
+      if (meet(hi + 4, hj + 0) || meet(hi + 4, hj + 2) || meet(hi + 4, hj + 4) || meet(hj + 4, hi + 0) || meet(hj + 4, hi + 2)) {
+        first = i; ++segment;
+        break;
+      }
+    }
+    segment_of[i] = segment;
+  }
+  return 0 < n ? segment + 1 : 0;
+}
+
 // true: the call was recorded and runs at the next flush. false: nothing was done, the call takes the ordinary path (which
 // flushes the record on its way: it asks for the stream).
 bool record_batch_call(const Kernel* k, libxsmm_blasint index_base, libxsmm_blasint index_stride,
@@ -539,23 +562,21 @@ bool record_batch_call(const Kernel* k, libxsmm_blasint index_base, libxsmm_blas
   s.relaxed = relaxed_order(ntasks, index_stride, c) ? 1 : 0;
   s.sync = (0 != (s.flags & LIBXSMM_GEMM_FLAG_BETA_0) || batchsize < 0 || size < 2) ? SYNC_NONE : SYNC_DEVICE; // (one C for the whole batch is found out on the device as well)
   MergeRecord& r = tl_merge;
-  if (tl_defer_open || tl_spmdm_open) defer_flush(); // a burst of per-call kernels, recorded spmdm blocks: they come first
-  if (tl_batch_open) { // one fused launch takes one precision, one policy, one order of the sums; the staging ring must hold the record
+  record_begin(OPEN_BATCH); // a burst of per-call kernels, recorded spmdm blocks: they come first
+  if (!r.calls.empty()) { // one fused launch takes one precision, one policy, one order of the sums; the staging ring must hold the record
     const SmmBatch& f = r.calls.front();
     // (a change of stream needs no test here: libxsmm_amd_set_stream asks for the stream, which flushes)
     if (f.typesize != ts || f.use_mfma != s.use_mfma || f.relaxed != s.relaxed
-      || MERGE_MAX_CALLS <= (int)r.calls.size() || MERGE_MAX_UPLOADS < r.uploads + 3) batch_flush_record();
+      || MERGE_MAX_CALLS <= (int)r.calls.size() || MERGE_MAX_UPLOADS < r.uploads + 3) { record_flush(); record_begin(OPEN_BATCH); }
   }
   unsigned long long hull[6] = { 0, 0, 0, 0, 0, 0 };
   const size_t span[3] = { span_a(s), span_b(s), span_c(s) };
-  const bool was_open = tl_batch_open;
-  tl_batch_open = false; // (index_upload asks for the stream, which launches what is open)
-  bool ok = true; int uploads = 0;
+  bool ok = true; int uploads = 0; // (staged on the stream as it is: asking for it would launch the record that is being extended)
   if (ADDR_INDEX == s.mode) {
     const int** const dst[3] = { &s.ia, &s.ib, &s.ic };
     for (int o = 0; o < 3 && ok; ++o) {
       if (nullptr == host_idx[o]) continue;
-      void* const d = index_upload(host_idx[o], (size_t)(size - 1) * index_stride + sizeof(int));
+      void* const d = index_upload_on(stream, host_idx[o], (size_t)(size - 1) * index_stride + sizeof(int));
       ++uploads; ok = (nullptr != d);
       *dst[o] = static_cast<const int*>(d);
     }
@@ -566,17 +587,15 @@ bool record_batch_call(const Kernel* k, libxsmm_blasint index_base, libxsmm_blas
     }
   }
   else if (!on_device) {
-    s.a = index_upload(ta.data(), ta.size() * sizeof(void*)); s.b = index_upload(tb.data(), tb.size() * sizeof(void*));
-    s.c = index_upload(tc.data(), tc.size() * sizeof(void*));
+    s.a = index_upload_on(stream, ta.data(), ta.size() * sizeof(void*)); s.b = index_upload_on(stream, tb.data(), tb.size() * sizeof(void*));
+    s.c = index_upload_on(stream, tc.data(), tc.size() * sizeof(void*));
     uploads = 3; ok = (nullptr != s.a && nullptr != s.b && nullptr != s.c);
     s.sa = (0 != s.sa ? (long long)sizeof(void*) : 0); s.sb = (0 != s.sb ? (long long)sizeof(void*) : 0); s.sc = (0 != s.sc ? (long long)sizeof(void*) : 0);
     hull_of_pointers(hull + 0, ta.data(), ta.size(), ts, span[0]);
     hull_of_pointers(hull + 2, tb.data(), tb.size(), ts, span[1]);
     hull_of_pointers(hull + 4, tc.data(), tc.size(), ts, span[2]);
   }
-  tl_batch_open = was_open;
   if (!ok) return false; // (entries a failed upload has filled: the ordinary path's commit releases them)
-  if (!tl_batch_open) { r.calls.clear(); r.hulls.clear(); r.on_device.clear(); r.uploads = 0; tl_batch_open = true; }
   r.uploads += uploads;
   r.calls.push_back(s); r.hulls.insert(r.hulls.end(), hull, hull + 6); r.on_device.push_back(on_device ? 1 : 0);
   return true;
@@ -590,13 +609,11 @@ namespace xsmm {
 // kernel and one small copy back -- the only wait for the device this path knows, once per flush and only then. The calls are
 // cut into segments of independent calls (merge_segments); every segment is one run_groups, segment after segment on the stream:
 // dependent calls keep the call order, a segment of one call is the launch it would have been on its own.
-thread_local bool tl_batch_open = false;
 void batch_flush_record()
-{
-  if (!tl_batch_open) return;
-  tl_batch_open = false; // (first: the launches below ask for the stream, which flushes what is open)
+{ // (reached through record_flush() alone: nothing is open while the launches below ask for the stream)
   MergeRecord& r = tl_merge;
   const int n = (int)r.calls.size();
+  if (0 == n) return; // (opened for a call whose staging failed)
   void* const stream = device().stream;
   bool hulls_ok = true;
   std::vector<int> dev; // the calls the hull kernel looks at
@@ -834,7 +851,7 @@ LIBXSMM_API int libxsmm_mmbatch_kernel(libxsmm_xmmfunction kernel, libxsmm_blasi
   }
   // inside a libxsmm_amd_defer_begin/end bracket: recorded, leaves with its neighbours at the flush
   if (record_batch_call(k, index_base, index_stride, stride_a, stride_b, stride_c, a, b, c, batchsize, ntasks)) return EXIT_SUCCESS;
-  if (tl_batch_open) batch_flush_record(); // a call that is not recorded runs behind the recorded ones
+  record_flush(); // a call that is not recorded runs behind the recorded ones
   SmmBatch s = from_descriptor(k->desc);
   s.relaxed = relaxed_order(ntasks, index_stride, c) ? 1 : 0;
   s.shared_across_calls = (1 < ntasks && 0 <= batchsize) ? 1 : 0; // (a negative batchsize is the caller's promise that nothing is shared)
@@ -1136,6 +1153,12 @@ LIBXSMM_API int libxsmm_amd_gemm_batch_groups(libxsmm_gemm_precision iprec, libx
   if (0 != e) return EXIT_FAILURE;
   if (host_visible) (void)stream_sync(); // operands the CPU addresses directly are done with when the call returns
   return EXIT_SUCCESS;
+}
+
+LIBXSMM_API int libxsmm_amd_merge_segments(int n, const unsigned long long hulls[], int segment_of[])
+{ // see include/libxsmm_amd.h
+  if (n < 0 || (0 < n && (nullptr == hulls || nullptr == segment_of))) return -1;
+  return merge_segments(n, hulls, segment_of);
 }
 
 LIBXSMM_API int libxsmm_amd_merge_last_plan(int* ncalls, int* nsegments, int* ndevice_hulls, unsigned long long hulls[], int segment_of[], int capacity)

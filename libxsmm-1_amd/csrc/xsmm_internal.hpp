@@ -82,24 +82,24 @@ constexpr int FLAG_SLOT_BLOCKS = 512; // work-groups of the C ordering check (ea
 int launch_c_order_check(const SmmBatch& args, int* d_out, void* stream);
 int launch_defer_gate(unsigned long long* word, unsigned long long* count_out, void* stream); // see xsmm_defer.cpp
 int launch_smm_generic(const SmmBatch& s, void* stream, const char** name);
-// deferred per-call kernels (xsmm_defer.cpp)
+// ---- calls recorded for later inside the opt-in bracket (xsmm_defer.cpp) --------------------------------------------------
+// What is open on the calling thread: at most one kind, kept by xsmm_defer.cpp alone.
+enum OpenKind : int { OPEN_NONE = 0,
+  OPEN_BURST,   // per-call kernels or per-panel operator calls behind a gate on the stream (xsmm_defer.cpp)
+  OPEN_BATCH,   // recorded libxsmm_gemm_batch calls (xsmm_gemm.cpp)
+  OPEN_SPMDM }; // recorded spmdm block calls (xsmm_sparse.cpp)
+OpenKind record_open();
+void record_begin(OpenKind kind);         // launches whatever other kind is open, then kind is open (nothing to do if it is already)
+void record_flush();                      // nothing is open any more, then the flush function of the kind that was: it may ask for the stream
+void batch_flush_record();                // the flush functions of the records, for record_flush() alone: launch what was recorded
+void spmdm_flush_record();
 struct Kernel;
 bool defer_call(Kernel* k, const void* a, const void* b, void* c);  // true: recorded (runs later, in stream order)
-void defer_flush();
 struct JitKernel;
 // per-panel calls of a fixed operator (libxsmm_?fsspmdm_execute) that walk along the rows of B and C: recorded like per-product calls
-bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, int typesize, int M, int N, int K, long long ldb, long long ldc, int vec);                                                  // seal the calling thread's open burst
-extern thread_local bool tl_defer_open;
-extern thread_local bool tl_spmdm_open;   // spmdm block calls recorded inside a bracket (xsmm_sparse.cpp)
-void spmdm_flush_record();                // launches them
+bool defer_panels(const void* handle, JitKernel* jit, const void* B, void* C, int typesize, int M, int N, int K, long long ldb, long long ldc, int vec);
 bool defer_bracket_open();                // the calling thread is inside libxsmm_amd_defer_begin/end
 bool defer_capturing(void* stream);       // the stream is being captured (or cannot be asked): nothing is recorded for later
-extern thread_local bool tl_batch_open;   // batch calls recorded inside a bracket (xsmm_gemm.cpp)
-void batch_flush_record();                // launches them: segments of independent calls, each a fused launch
-// Cuts n calls, in call order, into maximal consecutive segments whose members are independent of each other: no call's C range
-// meets another member's A, B or C range. hulls: {a_lo, a_hi, b_lo, b_hi, c_lo, c_hi} per call, byte addresses, half-open.
-// segment_of[i] receives the segment of call i (0, 1, ...; non-decreasing); returns the number of segments.
-int merge_segments(int n, const unsigned long long* hulls, int* segment_of);
 constexpr int BATCH_HULL_CALLS = 32;      // calls per hull launch (as many as a C-ordering check launch takes)
 // Address hulls of up to BATCH_HULL_CALLS index / pointer batches whose arrays live in device memory (kernels/batch_hull.hip).
 // span_bytes: 3 per call (A, B, C); d_out: device unsigned long long [2][3 * BATCH_HULL_CALLS], initialised here on the stream:
@@ -180,7 +180,7 @@ struct Device {
   void* stream = nullptr;   // hipStream_t
 };
 Device& device();
-Device& device_raw();                     // the same without sealing an open burst of deferred calls
+Device& device_raw();                     // the same without launching what is open on the thread (record_flush)
 bool device_ready();                      // probes once; false if no HIP device
 void fail_no_device(const char* what);    // prints a loud error (always) -- the product has no CPU compute path
 bool is_device_ptr(const void* p);
@@ -190,6 +190,7 @@ void settle(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr);
 int flag_slot_set(int* slot, int equal_pairs, int decreasing_pairs); // the verdict without a check kernel (0: ok)
 constexpr int INDEX_UPLOAD_RING = 256;   // staged arrays a thread may hold before index_upload_commit (a grouped call stages three arrays per group plus its table)
 void* index_upload(const void* host_array, size_t bytes); // async copy of a host index array to the device (nullptr: failed)
+void* index_upload_on(void* stream, const void* host_array, size_t bytes); // the same without asking for the stream
 void index_upload_commit();                                // after the launches that read uploaded arrays were queued
 int library_gemm(int typesize, int transa, int transb, int m, int n, int k, double alpha, const void* a, int lda,
                  const void* b, int ldb, double beta, void* c, int ldc); // rocBLAS on the engine's stream; -1: not available

@@ -248,8 +248,7 @@ LIBXSMM_API void libxsmm_spmdm_init(int M, int N, int K, int max_threads,
 LIBXSMM_API void libxsmm_spmdm_destroy(libxsmm_spmdm_handle* handle)
 {
   if (nullptr == handle) return;
-  spmdm_flush_record();
-  if (device_ready()) (void)stream_sync();
+  if (device_ready()) (void)stream_sync(); // (asks for the stream: block calls recorded for this handle are launched first)
   dev_free(handle->base_ptr_scratch_A); handle->base_ptr_scratch_A = nullptr;
   free(handle->base_ptr_scratch_B_scratch_C); handle->base_ptr_scratch_B_scratch_C = nullptr;
 }
@@ -468,17 +467,15 @@ void add_rect(std::vector<SpmdmRect>& rects, SpmdmRect r)
 bool record_block(int kind, const libxsmm_spmdm_handle* handle, const void* src, bool bf16, char trans, char transc, float beta, float* c, SpmdmRect r)
 {
   if (!defer_bracket_open() || !pure_device(src) || (2 == kind && !pure_device(c))) return false;
-  if (tl_defer_open) defer_flush(); // an open burst of per-call kernels is sealed: later calls of that kernel must not run ahead of this block
-  if (tl_batch_open) batch_flush_record(); // recorded batch calls come first
   SpmdmRecord& p = tl_record;
-  if (tl_spmdm_open && !(p.kind == kind && p.handle.base_ptr_scratch_A == handle->base_ptr_scratch_A && p.src == src && p.bf16 == bf16
-      && is_trans(p.trans) == is_trans(trans) && is_trans(p.transc) == is_trans(transc) && p.beta == beta && p.c == c)) spmdm_flush_record();
-  if (!tl_spmdm_open) {
+  if (OPEN_SPMDM == record_open() && !(p.kind == kind && p.handle.base_ptr_scratch_A == handle->base_ptr_scratch_A && p.src == src && p.bf16 == bf16
+      && is_trans(p.trans) == is_trans(trans) && is_trans(p.transc) == is_trans(transc) && p.beta == beta && p.c == c)) record_flush();
+  if (OPEN_SPMDM != record_open()) {
+    record_begin(OPEN_SPMDM); // an open burst is sealed (later calls of its kernel must not run ahead of this block), recorded batch calls come first
     p.kind = kind; p.handle = *handle; p.src = src; p.bf16 = bf16; p.trans = trans; p.transc = transc; p.beta = beta; p.c = c; p.rects.clear();
-    tl_spmdm_open = true;
   }
   for (const SpmdmRect& q : p.rects) { // a block that is recorded already (beta != 0: it must run twice): launch what is there first
-    if (q.mb0 < r.mb0 + r.mbn && r.mb0 < q.mb0 + q.mbn && q.n0 < r.n1 && r.n0 < q.n1) { spmdm_flush_record(); return record_block(kind, handle, src, bf16, trans, transc, beta, c, r); }
+    if (q.mb0 < r.mb0 + r.mbn && r.mb0 < q.mb0 + q.mbn && q.n0 < r.n1 && r.n0 < q.n1) { record_flush(); return record_block(kind, handle, src, bf16, trans, transc, beta, c, r); }
   }
   add_rect(p.rects, r);
   return true;
@@ -486,11 +483,8 @@ bool record_block(int kind, const libxsmm_spmdm_handle* handle, const void* src,
 }
 
 namespace xsmm {
-thread_local bool tl_spmdm_open = false;
 void spmdm_flush_record()
-{
-  if (!tl_spmdm_open) return;
-  tl_spmdm_open = false; // (first: the launches below ask for the stream, which flushes what is open)
+{ // (reached through record_flush() alone: nothing is open while the launches below ask for the stream)
   SpmdmRecord& p = tl_record;
   const libxsmm_spmdm_handle* const h = &p.handle;
   if (1 == p.kind) {
