@@ -500,6 +500,53 @@ LIBXSMM_APIEXT void libxsmm_otrans_omp(void* out, const void* in, unsigned int t
   libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo);
 LIBXSMM_API void libxsmm_itrans(void* inout, unsigned int typesize, libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint ld);
 
+/* ---------------------------------------------------------------------------------------------
+ * tiled GEMM for external threads or tasks (src/template/libxsmm.h:365-383; src/libxsmm_gemm.c:790-1228,
+ * src/libxsmm_ext_gemm.c:666-755). C = op(A) * op(B) + beta * C, column major, any m, n, k >= 1, F64 or F32.
+ * Every element of C is one fused multiply-add chain over k in ascending order starting from C (beta = 1) or from 0
+ * (beta = 0): the bits of the SMM kernels at any size, independent of the number of tasks.
+ *   handle_init  the handle is plain data inside the caller's blob (no destroy call, copyable with memcpy); no device is
+ *                asked for. NULL for: blob or m NULL, ntasks < 1, an extent below 1 (NULL k: m, NULL n: k), a leading
+ *                dimension below its operand's rows (NULL: tight), alpha != 1 or beta not in {0, 1} (NULL: 1; the
+ *                reference's descriptor rule, src/libxsmm_gemm.c:978-992), a precision other than F64->F64 or F32->F32.
+ *                The COPY_* flags are accepted and ignored: the kernel re-lays the operands on their way into LDS.
+ *   scratch_size 0 (also for NULL, :1051-1064); libxsmm_gemm_thread ignores `scratch`, which may be NULL
+ *   gemm_thread  task tid of nthreads computes its rectangle of C (libxsmm_amd_gemm_task in libxsmm_amd.h) as one launch
+ *                on the calling thread's stream; nthreads may differ from ntasks (:1074-1083); the rectangles are disjoint,
+ *                cover C and are cut on multiples of the kernel's tile; k is never split. A NULL handle or a tid outside
+ *                [0, nthreads) does nothing (one line on stderr if the verbosity is not zero).
+ *   xgemm_omp    handle_init with one task, then gemm_thread(..., 0, 1); outside the handle's domain F64 and F32 take
+ *                the path of libxsmm_blas_?gemm (the reference falls back to BLAS, src/libxsmm_ext_gemm.c:739-753)
+ * Memory: operands the GPU reaches are processed in place, asynchronously; host-visible memory is complete on return;
+ * pageable memory is staged (a task stages the spans of A and B it reads and copies its rectangle of C back: the elements
+ * between m and ldc keep their bytes). Inside libxsmm_amd_defer_begin/end the calls are not recorded: they seal the open
+ * burst first, so everything runs in call order.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct libxsmm_gemm_handle libxsmm_gemm_handle; /* opaque; src/libxsmm_gemm.h */
+typedef enum libxsmm_gemm_handle_flags { /* include/libxsmm_typedefs.h:216-221 */
+  LIBXSMM_GEMM_HANDLE_FLAG_AUTO = 0,
+  LIBXSMM_GEMM_HANDLE_FLAG_COPY_A = 1,
+  LIBXSMM_GEMM_HANDLE_FLAG_COPY_B = 2,
+  LIBXSMM_GEMM_HANDLE_FLAG_COPY_C = 4
+} libxsmm_gemm_handle_flags;
+LIBXSMM_API libxsmm_gemm_handle* libxsmm_gemm_handle_init(libxsmm_gemm_blob* blob,
+  libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec, const char* transa, const char* transb,
+  const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
+  const libxsmm_blasint* lda, const libxsmm_blasint* ldb, const libxsmm_blasint* ldc,
+  const void* alpha, const void* beta, int flags, /*unsigned*/int ntasks);
+LIBXSMM_API size_t libxsmm_gemm_handle_get_scratch_size(const libxsmm_gemm_handle* handle);
+LIBXSMM_API void libxsmm_gemm_thread(const libxsmm_gemm_handle* handle, void* scratch,
+  const void* a, const void* b, void* c, /*unsigned*/int tid, /*unsigned*/int nthreads);
+LIBXSMM_APIEXT void libxsmm_xgemm_omp(libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec,
+  const char* transa, const char* transb, const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
+  const void* alpha, const void* a, const libxsmm_blasint* lda, const void* b, const libxsmm_blasint* ldb,
+  const void* beta, void* c, const libxsmm_blasint* ldc);
+/* include/libxsmm_frontend.h:544-549 */
+#define libxsmm_dgemm_omp(TRANSA, TRANSB, M, N, K, ALPHA, A, LDA, B, LDB, BETA, C, LDC) \
+  libxsmm_xgemm_omp(LIBXSMM_GEMM_PRECISION_F64, LIBXSMM_GEMM_PRECISION_F64, TRANSA, TRANSB, M, N, K, ALPHA, A, LDA, B, LDB, BETA, C, LDC)
+#define libxsmm_sgemm_omp(TRANSA, TRANSB, M, N, K, ALPHA, A, LDA, B, LDB, BETA, C, LDC) \
+  libxsmm_xgemm_omp(LIBXSMM_GEMM_PRECISION_F32, LIBXSMM_GEMM_PRECISION_F32, TRANSA, TRANSB, M, N, K, ALPHA, A, LDA, B, LDB, BETA, C, LDC)
+
 /* introspection (src/template/libxsmm.h:107-121) */
 LIBXSMM_API int libxsmm_get_kernel_kind(const void* kernel, libxsmm_kernel_kind* kind);
 LIBXSMM_API int libxsmm_get_mmkernel_info(libxsmm_xmmfunction kernel, libxsmm_mmkernel_info* info, size_t* code_size);

@@ -290,4 +290,14 @@ LIBXSMM_API int libxsmm_amd_matcopy_batch_ptr(void* const out[], const void* con
 LIBXSMM_API int libxsmm_amd_otrans_batch_ptr(void* const out[], const void* const in[], unsigned int typesize, libxsmm_blasint m,
   libxsmm_blasint n, libxsmm_blasint ldi, libxsmm_blasint ldo, long long batch);
 
+/* ---- tiled GEMM (libxsmm_gemm_handle_init / libxsmm_gemm_thread, see libxsmm.h) ----------------------------------- */
+/** The rectangle of C that task `tid` of `nthreads` computes with libxsmm_gemm_thread: rect = {m0, m1, n0, n1}, rows
+ *  m0 <= i < m1 and columns n0 <= j < n1. A task without work gets an empty rectangle (all zeros, m0 == m1). For every
+ *  nthreads >= 1 the rectangles of tid = 0 ... nthreads - 1 are pairwise disjoint and cover C; they are cut on multiples of
+ *  the kernel's work-group tile (libxsmm_amd_gemm_tile); k is never split. No device is needed. Returns EXIT_SUCCESS, or
+ *  EXIT_FAILURE (rectangle empty) for a NULL handle, nthreads < 1 or tid outside [0, nthreads). */
+LIBXSMM_API int libxsmm_amd_gemm_task(const libxsmm_gemm_handle* handle, int tid, int nthreads, unsigned int rect[4]);
+/** Extent (rows and columns alike) of the work-group tile of the tiled GEMM kernel. */
+LIBXSMM_API int libxsmm_amd_gemm_tile(void);
+
 #endif /* LIBXSMM_AMD_H */

@@ -184,6 +184,8 @@ def _declare(L):
     gemm = [C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, vp, vp, c_int_p, vp, c_int_p, vp, vp, c_int_p]
     sig("libxsmm_dgemm", None, *gemm)
     sig("libxsmm_sgemm", None, *gemm)
+    sig("libxsmm_blas_dgemm", None, *gemm)
+    sig("libxsmm_blas_sgemm", None, *gemm)
     sig("libxsmm_dfsspmdm_create", vp, i, i, i, i, i, i, C.c_double, C.c_double, vp)
     sig("libxsmm_dfsspmdm_execute", None, vp, vp, vp)
     sig("libxsmm_dfsspmdm_destroy", None, vp)
@@ -309,6 +311,13 @@ def _declare(L):
         sig(nm, i, vp, vp, u, i, i, i, i, ll, ll, ll)
     for nm in ("libxsmm_amd_matcopy_batch_ptr", "libxsmm_amd_otrans_batch_ptr"):
         sig(nm, i, vp, vp, u, i, i, i, i, ll)
+    # tiled GEMM (include/libxsmm.h; the partition query and the tile extent in include/libxsmm_amd.h)
+    sig("libxsmm_gemm_handle_init", vp, vp, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp, i, i)
+    sig("libxsmm_gemm_handle_get_scratch_size", C.c_size_t, vp)
+    sig("libxsmm_gemm_thread", None, vp, vp, vp, vp, vp, i, i)
+    sig("libxsmm_xgemm_omp", None, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, vp, vp, c_int_p, vp, c_int_p, vp, vp, c_int_p)
+    sig("libxsmm_amd_gemm_task", i, vp, i, i, C.POINTER(C.c_uint))
+    sig("libxsmm_amd_gemm_tile", i)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -583,6 +592,45 @@ def matcopy_batch_ptr(out_ptrs, in_ptrs, typesize, m, n, ldi, ldo, batch):
 def otrans_batch_ptr(out_ptrs, in_ptrs, typesize, m, n, ldi, ldo, batch):
     """libxsmm_amd_otrans_batch_ptr"""
     return lib().libxsmm_amd_otrans_batch_ptr(dptr(out_ptrs), dptr(in_ptrs), typesize, m, n, ldi, ldo, batch)
+
+
+class GemmBlob(C.Structure):  # libxsmm_gemm_blob
+    _fields_ = [("data", C.c_char * 128)]
+
+
+def _scalar(prec, v):
+    return None if v is None else C.byref(C.c_double(v) if prec == F64 else C.c_float(v))
+
+
+def _trans(t):
+    return None if t is None else t.encode()
+
+
+def gemm_handle(iprec, oprec, transa, transb, m, n, k, lda=None, ldb=None, ldc=None, alpha=None, beta=None, flags=0, ntasks=1):
+    """libxsmm_gemm_handle_init -> (blob, handle); handle is None where the call returns NULL. m, n, k, ld*: int or None."""
+    blob = GemmBlob()
+    h = lib().libxsmm_gemm_handle_init(C.byref(blob), iprec, oprec, _trans(transa), _trans(transb), iptr(m), iptr(n), iptr(k),
+                                       iptr(lda), iptr(ldb), iptr(ldc), _scalar(iprec, alpha), _scalar(oprec, beta), flags, ntasks)
+    return blob, h
+
+
+def gemm_thread(handle, a, b, c, tid=0, nthreads=1, scratch=None):
+    """libxsmm_gemm_thread"""
+    lib().libxsmm_gemm_thread(handle, dptr(scratch), dptr(a), dptr(b), dptr(c), tid, nthreads)
+
+
+def gemm_task(handle, tid, nthreads):
+    """libxsmm_amd_gemm_task -> (return code, (m0, m1, n0, n1))"""
+    rect = (C.c_uint * 4)()
+    rc = lib().libxsmm_amd_gemm_task(handle, tid, nthreads, rect)
+    return rc, tuple(rect)
+
+
+def xgemm_omp(prec, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, oprec=None):
+    """libxsmm_xgemm_omp (libxsmm_dgemm_omp / libxsmm_sgemm_omp are macros over it)"""
+    oprec = prec if oprec is None else oprec
+    lib().libxsmm_xgemm_omp(prec, oprec, _trans(transa), _trans(transb), iptr(m), iptr(n), iptr(k), _scalar(prec, alpha), dptr(a), iptr(lda),
+                            dptr(b), iptr(ldb), _scalar(oprec, beta), dptr(c), iptr(ldc))
 
 
 def call_kernel(fn_ptr, a, b, c, x3=None):

@@ -1191,6 +1191,8 @@ void xgemm(int prec, const char* transa, const char* transb, const libxsmm_blasi
   const libxsmm_blasint ildc = LIBXSMM_MAX(nullptr != ldc ? *ldc : mm, 1);
   const T aa = (nullptr != alpha ? *alpha : (T)LIBXSMM_ALPHA), bb = (nullptr != beta ? *beta : (T)LIBXSMM_BETA);
   if (mm <= 0 || nn <= 0) return;
+  // opt-in (LIBXSMM_AMD_TGEMM=1): a large product with alpha = 1 and beta in {0, 1} on the tiled matrix-core kernel (xsmm_tgemm.cpp)
+  if (tgemm_route((int)sizeof(T), flags, mm, nn, kk, ilda, ildb, ildc, (double)aa, (double)bb, a, b, c)) return;
   libxsmm_descriptor_blob blob;
   const libxsmm_gemm_descriptor* const desc = libxsmm_gemm_descriptor_dinit(&blob, (libxsmm_gemm_precision)prec, mm, nn, kk,
     ilda, ildb, ildc, (double)aa, (double)bb, flags, LIBXSMM_GEMM_PREFETCH_NONE);

@@ -269,6 +269,19 @@ int launch_xcopy_itrans(int unit, void* inout, int n, long long ld, bool vec, vo
 int launch_xcopy_copy(int unit, const void* in, void* out, long long rowbytes, long long ncols, long long pitch_in, long long pitch_out, void* stream); // pitches in bytes; in == nullptr: zeros
 int launch_xcopy_stack(int unit, const StackMove& args, int op, void* stream, const char** name);
 
+// tiled GEMM (xsmm_tgemm.cpp, kernels/tgemm.hip)
+constexpr int TGEMM_TILE = 128;           // the work-group tile of C is TGEMM_TILE x TGEMM_TILE; tasks are cut on its multiples
+struct TgemmArgs {                        // C(m x n) = op(A) * op(B) + (beta0 ? 0 : C); a: first row of op(A), b: first column of op(B)
+  int typesize;                           // 8: f64, 4: f32
+  int transa, transb, beta0;
+  int m, n, k;
+  long long lda, ldb, ldc;
+  const void* a; const void* b; void* c;  // memory the GPU reaches
+};
+int launch_tgemm(const TgemmArgs& args, void* stream, const char** name); // returns hipError_t as int
+// the tiled GEMM for a libxsmm_?gemm call (opt-in LIBXSMM_AMD_TGEMM=1); false: not taken, the caller goes on as before
+bool tgemm_route(int typesize, int flags, int m, int n, int k, int lda, int ldb, int ldc, double alpha, double beta, const void* a, const void* b, void* c);
+
 int verbosity();
 bool once(int* flag);   // true the first time
 
