@@ -630,6 +630,30 @@ LIBXSMM_API void libxsmm_sgemm(const char* transa, const char* transb,
   const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
   const float* alpha, const float* a, const libxsmm_blasint* lda, const float* b, const libxsmm_blasint* ldb,
   const float* beta, float* c, const libxsmm_blasint* ldc);
+/* single GEMM with 16-bit inputs (src/template/libxsmm.h:397-414): I16 -> I32, I16 -> F32, BF16 -> F32. Routing is that of
+ * LIBXSMM_XGEMM (include/libxsmm_frontend.h:371-411). A product with m * n * k <= LIBXSMM_MAX_MNK for which
+ * libxsmm_{wi,ws,bs}mmdispatch returns a kernel (k even, no transpose) is that kernel's call on a, b, c as given: A is then
+ * read in pairs of k (a[(k/2)*lda*2 + m*2 + k%2], see the dispatchers above). The I16 -> F32 kernel gets a pointer to 1.0f
+ * as its scaling factor; the reference passes none there (LIBXSMM_MMCALL_LDX, :385) and its kernel reads an indeterminate
+ * word. Everything else -- larger products, odd k, a transpose, a NULL dispatch -- is libxsmm_amd_lowp_gemm
+ * (libxsmm_amd.h): plain column-major operands, all four transposes, the arithmetic of the dispatched kernels. The
+ * reference's own fallback for these cases, LIBXSMM_INLINE_XGEMM (include/libxsmm_frontend.h:213-245), is not reproduced:
+ * it is NN only, multiplies raw bf16 bit patterns as integers and with beta = 0 keeps only the last k term (:226-228); the
+ * GEMM it stands for is computed instead. NULL arguments take the defaults of :373-379 (k = m, n = k, tight leading
+ * dimensions, alpha = 1, beta = LIBXSMM_BETA). alpha must be 1 and beta 0 or 1, as for every low-precision kernel of the
+ * reference: otherwise C is left untouched and one message is printed at verbosity >= 1. */
+LIBXSMM_API void libxsmm_wigemm(const char* transa, const char* transb,
+  const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
+  const int* alpha, const short* a, const libxsmm_blasint* lda, const short* b, const libxsmm_blasint* ldb,
+  const int* beta, int* c, const libxsmm_blasint* ldc);
+LIBXSMM_API void libxsmm_wsgemm(const char* transa, const char* transb,
+  const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
+  const float* alpha, const short* a, const libxsmm_blasint* lda, const short* b, const libxsmm_blasint* ldb,
+  const float* beta, float* c, const libxsmm_blasint* ldc);
+LIBXSMM_API void libxsmm_bsgemm(const char* transa, const char* transb,
+  const libxsmm_blasint* m, const libxsmm_blasint* n, const libxsmm_blasint* k,
+  const float* alpha, const libxsmm_bfloat16* a, const libxsmm_blasint* lda, const libxsmm_bfloat16* b, const libxsmm_blasint* ldb,
+  const float* beta, float* c, const libxsmm_blasint* ldc);
 /* BLAS call wrapper (reference src/libxsmm_ext_gemm.c:256-660, documentation/libxsmm_mm.md "Call Wrapper"): relink an
  * application that calls the Fortran BLAS symbols with -Wl,--wrap=dgemm_,--wrap=sgemm_ (optionally also
  * --wrap=dgemm_batch_,--wrap=sgemm_batch_,--wrap=dgemm_batch,--wrap=sgemm_batch) and its calls arrive here. Every call is

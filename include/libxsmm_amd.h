@@ -300,4 +300,35 @@ LIBXSMM_API int libxsmm_amd_gemm_task(const libxsmm_gemm_handle* handle, int tid
 /** Extent (rows and columns alike) of the work-group tile of the tiled GEMM kernel. */
 LIBXSMM_API int libxsmm_amd_gemm_tile(void);
 
+/* ---- GEMM with 16-bit inputs (libxsmm_wigemm / libxsmm_wsgemm / libxsmm_bsgemm, see libxsmm.h) ------------------------ */
+/** C(m x n) = op(A) * op(B) + beta * C with (iprec, oprec) one of (I16, I32), (I16, F32), (BF16, F32) and beta 0 or 1. The
+ *  layout is always plain column-major: op(A) is m x k, op(B) is k x n (transa / transb 'N' or 'T'), whatever the size --
+ *  unlike the front ends, which below LIBXSMM_MAX_MNK read A in pairs of k. Per element of C, from C (beta 1) or from 0:
+ *  I16 -> I32 the wrapping 32-bit sum of the 32-bit products; I16 -> F32 acc = acc + (float)(a * b), k ascending, every add
+ *  rounded; BF16 -> F32 acc = acc + a * b, k ascending, the product (exact in fp32 unless it underflows) and the add rounded
+ *  separately -- the bits of the kernels of libxsmm_wimmdispatch / wsmmdispatch (scaling factor 1) / bsmmdispatch, -0.0
+ *  included. beta = 0 never reads C; what lies between m and ldc keeps its bytes. Operands in memory the GPU reaches are
+ *  processed in place, asynchronously on the calling thread's stream; host-visible memory is complete on return; pageable
+ *  memory is staged. Inside libxsmm_amd_defer_begin/end the call is not recorded: it seals the open burst and runs in call
+ *  order. A wrong type pair, transa / transb other than N, n, T, t, a negative extent, a leading dimension below the
+ *  extent, a NULL operand or another beta returns EXIT_FAILURE before any device is asked for; m, n or k of 0 succeeds and
+ *  does nothing. The _thread form computes the rectangle of task tid of nthreads: the partition of libxsmm_amd_gemm_task
+ *  over the tiles of libxsmm_amd_gemm_tile with k never split, so the results do not depend on nthreads; tid outside
+ *  [0, nthreads) returns EXIT_FAILURE and does nothing. */
+LIBXSMM_API int libxsmm_amd_lowp_gemm(libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec, char transa, char transb,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint k, const void* a, libxsmm_blasint lda, const void* b, libxsmm_blasint ldb,
+  int beta, void* c, libxsmm_blasint ldc);
+LIBXSMM_API int libxsmm_amd_lowp_gemm_thread(libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec, char transa, char transb,
+  libxsmm_blasint m, libxsmm_blasint n, libxsmm_blasint k, const void* a, libxsmm_blasint lda, const void* b, libxsmm_blasint ldb,
+  int beta, void* c, libxsmm_blasint ldc, int tid, int nthreads);
+/** BF16 -> F32 on the bf16 matrix instruction (v_mfma_f32_32x32x16_bf16), opt-in (environment LIBXSMM_AMD_LOWP_FAST=1,
+ *  default 0): per element the sum of the exact products in the order the instruction takes, 16 products per step. The
+ *  result is the same from call to call and equals the default wherever every partial sum is exactly representable, but
+ *  its bits are not those of the default in general; the last step is padded with zeros, so a C of -0.0 whose products are
+ *  all -0.0 comes out as +0.0. The other type pairs are not affected. set returns the previous value. */
+LIBXSMM_API int libxsmm_amd_set_lowp_fast(int on);
+LIBXSMM_API int libxsmm_amd_get_lowp_fast(void);
+/** The k chunk of the kernels behind libxsmm_amd_lowp_gemm for an input precision (BF16: 64, I16: 32; 0 otherwise). */
+LIBXSMM_API int libxsmm_amd_lowp_gemm_chunk(libxsmm_gemm_precision iprec);
+
 #endif /* LIBXSMM_AMD_H */

@@ -318,6 +318,15 @@ def _declare(L):
     sig("libxsmm_xgemm_omp", None, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, vp, vp, c_int_p, vp, c_int_p, vp, vp, c_int_p)
     sig("libxsmm_amd_gemm_task", i, vp, i, i, C.POINTER(C.c_uint))
     sig("libxsmm_amd_gemm_tile", i)
+    # GEMM with 16-bit inputs (front ends in include/libxsmm.h, the one-layout entry in include/libxsmm_amd.h)
+    for nm in ("libxsmm_wigemm", "libxsmm_wsgemm", "libxsmm_bsgemm"):
+        sig(nm, None, *gemm)
+    lowp = [i, i, C.c_char, C.c_char, i, i, i, vp, i, vp, i, i, vp, i]
+    sig("libxsmm_amd_lowp_gemm", i, *lowp)
+    sig("libxsmm_amd_lowp_gemm_thread", i, *(lowp + [i, i]))
+    sig("libxsmm_amd_set_lowp_fast", i, i)
+    sig("libxsmm_amd_get_lowp_fast", i)
+    sig("libxsmm_amd_lowp_gemm_chunk", i, i)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -641,3 +650,40 @@ def call_kernel(fn_ptr, a, b, c, x3=None):
 
 def last_kernel():
     return lib().libxsmm_amd_last_kernel().decode()
+
+
+def gemm_lowp_thread(iprec, oprec, transa, transb, m, n, k, a, lda, b, ldb, beta, c, ldc, tid=0, nthreads=1):
+    """libxsmm_amd_lowp_gemm_thread: plain column-major operands, (iprec, oprec) in (I16, I32), (I16, F32), (BF16, F32), beta 0 or 1"""
+    return lib().libxsmm_amd_lowp_gemm_thread(iprec, oprec, transa.encode(), transb.encode(), m, n, k, dptr(a), lda, dptr(b), ldb, beta, dptr(c), ldc,
+                                              tid, nthreads)
+
+
+def gemm_lowp(iprec, oprec, transa, transb, m, n, k, a, lda, b, ldb, beta, c, ldc):
+    """libxsmm_amd_lowp_gemm"""
+    return lib().libxsmm_amd_lowp_gemm(iprec, oprec, transa.encode(), transb.encode(), m, n, k, dptr(a), lda, dptr(b), ldb, beta, dptr(c), ldc)
+
+
+def set_lowp_fast(on):
+    """libxsmm_amd_set_lowp_fast -> the previous value"""
+    return lib().libxsmm_amd_set_lowp_fast(1 if on else 0)
+
+
+def _lowp_front_end(name, ctype, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    sc = lambda v: None if v is None else C.byref(ctype(v))
+    getattr(lib(), name)(_trans(transa), _trans(transb), iptr(m), iptr(n), iptr(k), sc(alpha), dptr(a), iptr(lda), dptr(b), iptr(ldb), sc(beta),
+                         dptr(c), iptr(ldc))
+
+
+def wigemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    """libxsmm_wigemm (alpha, beta: Python ints or None)"""
+    _lowp_front_end("libxsmm_wigemm", C.c_int, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc)
+
+
+def wsgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    """libxsmm_wsgemm (alpha, beta: Python floats or None)"""
+    _lowp_front_end("libxsmm_wsgemm", C.c_float, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc)
+
+
+def bsgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    """libxsmm_bsgemm (alpha, beta: Python floats or None)"""
+    _lowp_front_end("libxsmm_bsgemm", C.c_float, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc)

@@ -282,6 +282,18 @@ int launch_tgemm(const TgemmArgs& args, void* stream, const char** name); // ret
 // the tiled GEMM for a libxsmm_?gemm call (opt-in LIBXSMM_AMD_TGEMM=1); false: not taken, the caller goes on as before
 bool tgemm_route(int typesize, int flags, int m, int n, int k, int lda, int ldb, int ldc, double alpha, double beta, const void* a, const void* b, void* c);
 
+// tiled GEMM for 16-bit inputs (xsmm_lowp_gemm.cpp, kernels/tgemm_lowp.hip); the first three are the kinds of the oracle's gold loops
+enum LowpGemmKind : int { LOWP_I16_I32 = 0, LOWP_I16_F32 = 1, LOWP_BF16 = 2, LOWP_BF16_FAST = 3 /* v_mfma_f32_32x32x16_bf16: opt-in */ };
+constexpr int TGEMM_LOWP_BK = 64;         // the k chunk of the bf16 kernels (the i16 kernels: half of it)
+struct TgemmLowpArgs {                    // as TgemmArgs; a, b: 16-bit elements, c: 32-bit elements
+  int kind;                               // LowpGemmKind
+  int transa, transb, beta0;
+  int m, n, k;
+  long long lda, ldb, ldc;
+  const void* a; const void* b; void* c;  // memory the GPU reaches
+};
+int launch_tgemm_lowp(const TgemmLowpArgs& args, void* stream, const char** name); // returns hipError_t as int
+
 int verbosity();
 bool once(int* flag);   // true the first time
 
