@@ -1018,5 +1018,6 @@ LIBXSMM_CXX_GEMM(libxsmm_blas_gemm, float, libxsmm_blas_sgemm)
 #endif /* __cplusplus */
 
 #include "libxsmm_amd.h"
+#include "libxsmm_math.h" /* (the reference's libxsmm.h includes its libxsmm_math.h too) */
 
 #endif /* LIBXSMM_H */

@@ -331,4 +331,23 @@ LIBXSMM_API int libxsmm_amd_get_lowp_fast(void);
 /** The k chunk of the kernels behind libxsmm_amd_lowp_gemm for an input precision (BF16: 64, I16: 32; 0 otherwise). */
 LIBXSMM_API int libxsmm_amd_lowp_gemm_chunk(libxsmm_gemm_precision iprec);
 
+/* ---- quantisation (libxsmm_dnn_quantize / _act / _fil, see libxsmm_dnn.h) ------------------------------------------------ */
+/** The reference forms without their wait: the same arguments and arithmetic, but `scf` points to one byte the GPU reaches
+ *  (device, pinned or managed memory). The last kernel of the call writes it and the call returns without waiting for the
+ *  calling thread's stream (libxsmm_amd_set_stream): a consumer queued on that stream sees the quantised tensor and the byte.
+ *  in / out in host memory are still staged or waited for as in the reference forms. A wrong call (see libxsmm_dnn.h) or an
+ *  scf the GPU does not reach returns EXIT_FAILURE and writes nothing; an empty tensor returns EXIT_SUCCESS, writes nothing
+ *  and leaves *scf alone. Inside libxsmm_amd_defer_begin/end the calls are not recorded: they seal the open burst and run
+ *  in call order. */
+LIBXSMM_API int libxsmm_amd_dnn_quantize_async(float* in_buffer, short* out_buffer, int length, unsigned char add_shift, unsigned char* scf, int round_mode);
+LIBXSMM_API int libxsmm_amd_dnn_quantize_act_async(float* in_buffer, short* out_buffer, unsigned int N, unsigned int C, unsigned int H, unsigned int W,
+  unsigned int cblk_f32, unsigned int cblk_i16, unsigned int lp_blk, unsigned char add_shift, unsigned char* scf, int round_mode);
+LIBXSMM_API int libxsmm_amd_dnn_quantize_fil_async(float* in_buffer, short* out_buffer, unsigned int K, unsigned int C, unsigned int R, unsigned int S,
+  unsigned int cblk_f32, unsigned int cblk_i16, unsigned int kblk_f32, unsigned int kblk_i16, unsigned int lp_blk, unsigned char add_shift,
+  unsigned char* scf, int round_mode);
+/** LIBXSMM_DNN_QUANT_STOCH_ROUND draws p of element i from a counter-based generator of (seed, i), i being the element's
+ *  index in the output. seed == 0 (the default): every call takes a seed from libxsmm_timer_tick(), as the reference seeds
+ *  rand(); any other value makes a call a pure function of its inputs. Process-wide. */
+LIBXSMM_API void libxsmm_amd_dnn_quantize_set_seed(unsigned int seed);
+
 #endif /* LIBXSMM_AMD_H */

@@ -327,6 +327,21 @@ def _declare(L):
     sig("libxsmm_amd_set_lowp_fast", i, i)
     sig("libxsmm_amd_get_lowp_fast", i)
     sig("libxsmm_amd_lowp_gemm_chunk", i, i)
+    # quantisation and bf16 conversion (include/libxsmm_dnn.h; the stream-ordered forms in include/libxsmm_amd.h)
+    ub = C.c_ubyte
+    sig("libxsmm_sexp2_u8", C.c_float, ub)
+    sig("libxsmm_sexp2_i8", C.c_float, C.c_byte)
+    sig("libxsmm_sexp2_i8i", C.c_float, i)
+    sig("libxsmm_dnn_quantize", None, vp, vp, i, ub, vp, i)
+    sig("libxsmm_dnn_quantize_act", None, vp, vp, u, u, u, u, u, u, u, ub, vp, i)
+    sig("libxsmm_dnn_quantize_fil", None, vp, vp, u, u, u, u, u, u, u, u, u, ub, vp, i)
+    sig("libxsmm_amd_dnn_quantize_async", i, vp, vp, i, ub, vp, i)
+    sig("libxsmm_amd_dnn_quantize_act_async", i, vp, vp, u, u, u, u, u, u, u, ub, vp, i)
+    sig("libxsmm_amd_dnn_quantize_fil_async", i, vp, vp, u, u, u, u, u, u, u, u, u, ub, vp, i)
+    sig("libxsmm_amd_dnn_quantize_set_seed", None, u)
+    sig("libxsmm_dnn_dequantize", None, vp, vp, i, ub)
+    for nm in ("libxsmm_truncate_convert_f32_bf16", "libxsmm_rnaz_convert_fp32_bfp16", "libxsmm_rne_convert_fp32_bfp16", "libxsmm_convert_bf16_f32"):
+        sig(nm, None, vp, vp, u)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -687,3 +702,52 @@ def wsgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
 def bsgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
     """libxsmm_bsgemm (alpha, beta: Python floats or None)"""
     _lowp_front_end("libxsmm_bsgemm", C.c_float, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc)
+
+
+# ---- quantisation and bf16 conversion (include/libxsmm_dnn.h) ----------------------------------------------------------------
+QUANT_NO_ROUND, QUANT_BIAS_ROUND, QUANT_STOCH_ROUND, QUANT_NEAREST_ROUND, QUANT_FPHW_ROUND = 80000, 80001, 80002, 80003, 80004
+
+
+def _quantize(name, args, scf):
+    """the reference form (scf None: the byte is returned) or the _async form (scf: one byte the GPU reaches; returns the status)"""
+    if scf is not None:
+        return getattr(lib(), "libxsmm_amd_" + name + "_async")(*(args[:-1] + [dptr(scf), args[-1]]))
+    byte = C.c_ubyte(0xa5)
+    getattr(lib(), "libxsmm_" + name)(*(args[:-1] + [C.cast(C.byref(byte), C.c_void_p), args[-1]]))
+    return byte.value
+
+
+def dnn_quantize(inp, out, length, add_shift, round_mode, scf=None):
+    """libxsmm_dnn_quantize / libxsmm_amd_dnn_quantize_async"""
+    return _quantize("dnn_quantize", [dptr(inp), dptr(out), length, add_shift, round_mode], scf)
+
+
+def dnn_quantize_act(inp, out, N, Cc, H, W, cblk_f32, cblk_i16, lp_blk, add_shift, round_mode, scf=None):
+    """libxsmm_dnn_quantize_act / libxsmm_amd_dnn_quantize_act_async"""
+    return _quantize("dnn_quantize_act", [dptr(inp), dptr(out), N, Cc, H, W, cblk_f32, cblk_i16, lp_blk, add_shift, round_mode], scf)
+
+
+def dnn_quantize_fil(inp, out, K, Cc, R, S, cblk_f32, cblk_i16, kblk_f32, kblk_i16, lp_blk, add_shift, round_mode, scf=None):
+    """libxsmm_dnn_quantize_fil / libxsmm_amd_dnn_quantize_fil_async"""
+    return _quantize("dnn_quantize_fil", [dptr(inp), dptr(out), K, Cc, R, S, cblk_f32, cblk_i16, kblk_f32, kblk_i16, lp_blk, add_shift, round_mode], scf)
+
+
+def dnn_quantize_set_seed(seed):
+    """libxsmm_amd_dnn_quantize_set_seed: 0 draws a seed per call"""
+    lib().libxsmm_amd_dnn_quantize_set_seed(seed)
+
+
+def dnn_dequantize(inp, out, length, scf):
+    """libxsmm_dnn_dequantize"""
+    lib().libxsmm_dnn_dequantize(dptr(inp), dptr(out), length, scf)
+
+
+def convert_f32_bf16(inp, out, length, rounding="rne"):
+    """libxsmm_truncate_convert_f32_bf16 / libxsmm_rnaz_convert_fp32_bfp16 / libxsmm_rne_convert_fp32_bfp16"""
+    name = {"truncate": "libxsmm_truncate_convert_f32_bf16", "rnaz": "libxsmm_rnaz_convert_fp32_bfp16", "rne": "libxsmm_rne_convert_fp32_bfp16"}[rounding]
+    getattr(lib(), name)(dptr(inp), dptr(out), length)
+
+
+def convert_bf16_f32(inp, out, length):
+    """libxsmm_convert_bf16_f32"""
+    lib().libxsmm_convert_bf16_f32(dptr(inp), dptr(out), length)

@@ -294,6 +294,29 @@ struct TgemmLowpArgs {                    // as TgemmArgs; a, b: 16-bit elements
 };
 int launch_tgemm_lowp(const TgemmLowpArgs& args, void* stream, const char** name); // returns hipError_t as int
 
+// quantisation and bf16 conversion (xsmm_quant.cpp, kernels/quant.hip)
+enum QuantMode : int { QUANT_NO = 0, QUANT_BIAS = 1, QUANT_STOCH = 2, QUANT_NEAREST = 3, QUANT_FPHW = 4 }; // LIBXSMM_DNN_QUANT_*_ROUND - 80000
+struct QuantHead {                        // what a quantise kernel needs besides its tensors
+  int mode;                               // QuantMode
+  unsigned add_shift, seed;               // seed: stochastic rounding
+  const unsigned* maxword;                // device word written by launch_quant_absmax earlier on the same stream
+  unsigned char* scf;                     // one byte the GPU reaches: written by the quantise kernel
+};
+struct QuantLayout {                      // libxsmm_dnn_quantize_act (fil == 0) / _fil (fil != 0; H, W stand for R, S)
+  unsigned C, H, W, cb32, cb16, lp, cblk, kb32, kb16; // cblk = C / (cb16 * lp)
+  int fil;
+  long long total;                        // elements
+};
+struct QuantTiles { int CB, pitch, chunks; long long P, ptiles, ntiles; }; // filled in by launch_quant_act_tiled
+// all return hipError_t as int; every pointer is memory the GPU reaches, aligned to its element
+int launch_quant_absmax(const float* in, long long n, unsigned* maxword, void* stream); // zeroes the word on the stream first
+int launch_quant_flat(const float* in, short* out, long long n, const QuantHead& h, void* stream);
+int launch_quant_layout(const float* in, short* out, const QuantLayout& g, const QuantHead& h, void* stream); // any block sizes
+// plain input (cb32 == 1), CB = cb16 * lp even, out aligned to 4 bytes: nblocks = N * C / CB slabs of CB rows of P = H * W pixels
+int launch_quant_act_tiled(const float* in, short* out, long long nblocks, int CB, long long P, const QuantHead& h, void* stream);
+int launch_dequant_flat(const short* in, float* out, long long n, float scale, void* stream);
+int launch_bf16_narrow(int rounding /*0: truncate, 1: nearest-away, 2: nearest-even*/, const float* in, unsigned short* out, long long n, void* stream);
+
 int verbosity();
 bool once(int* flag);   // true the first time
 
