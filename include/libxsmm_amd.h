@@ -350,4 +350,36 @@ LIBXSMM_API int libxsmm_amd_dnn_quantize_fil_async(float* in_buffer, short* out_
  *  rand(); any other value makes a call a pure function of its inputs. Process-wide. */
 LIBXSMM_API void libxsmm_amd_dnn_quantize_set_seed(unsigned int seed);
 
+/* ---- matdiff on operands in device memory (libxsmm_matdiff, see libxsmm.h) ------------------------------------------------- */
+/** libxsmm_matdiff runs on the GPU whenever ref or tst is plain device memory (the other operand may be any memory; pageable
+ *  memory is staged), waits and fills the caller's struct. Two host operands take the host loop as before. The device path
+ *  follows the reference's definition: all five datatypes (F64, F32, I32, I16, I8), m <= ld required, the
+ *  contiguous sums in normi_abs and the strided ones in norm1_abs. A non-finite test value gives its first location in m, n,
+ *  +inf in norm1_abs, norm1_rel, normi_abs, normi_rel, normf_rel, linf_abs, linf_rel, l2_abs and l2_rel, and leaves the other
+ *  fields as libxsmm_matdiff_clear sets them. The same call on the same data returns the same bytes.
+ *
+ *  libxsmm_amd_matdiff_async is the same call without its wait: `info` lies in memory the GPU reaches (device, pinned or
+ *  managed), the last kernel of the call writes it, and the call returns without waiting for the calling thread's stream
+ *  (libxsmm_amd_set_stream): a consumer queued on that stream sees it. A wrong call (NULL info, no operand, m > ld, a negative
+ *  size, another datatype, an info the GPU does not reach) returns EXIT_FAILURE at once and writes nothing; m == 0 or n == 0
+ *  writes a cleared info and launches nothing. A lone operand (ref == NULL and tst given, or the other way round) is walked by
+ *  ldref, as the reference does. Inside libxsmm_amd_defer_begin/end the calls are not recorded: they seal the open burst
+ *  and run in call order, so they see the results of the calls recorded before them. */
+LIBXSMM_API int libxsmm_amd_matdiff_async(libxsmm_matdiff_info* info, libxsmm_datatype datatype, libxsmm_blasint m, libxsmm_blasint n,
+  const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst);
+/** `batch` pairs of m x n matrices, item i at ref + i * stride_ref and tst + i * stride_tst (strides in elements, not
+ *  negative; a lone operand goes by ldref and stride_ref), compared by one set of launches. `items` is NULL or an array of
+ *  `batch` infos in host or device memory: entry i is what a single call on item i gives. `info` is the combination of all
+ *  items as libxsmm_matdiff_reduce of the reference forms it from a cleared info (src/libxsmm_math.c:182-238): every field on
+ *  its own, the larger of the maxima and norms, the smaller of the minima, l1_ref and l1_tst summed; m, n are those of the
+ *  first item with the largest linf_abs, whose index goes to *item (item may be NULL; -1 if nothing differs). One deviation:
+ *  avg_ref and avg_tst are l1 / (m * n * batch), the mean over the batch -- the running half-sum of the reduce depends on the
+ *  order of the items and forgets all but the last ones. A non-finite test value in any item gives `info` the nine +inf and
+ *  the cleared fields of the single call, with m, n and *item of the first such item. batch == 0 is an empty comparison
+ *  (cleared info, *item = -1), batch < 0 a wrong call. The call waits if info (or items, or item) is plain host memory;
+ *  otherwise it returns without waiting, like libxsmm_amd_matdiff_async. */
+LIBXSMM_API int libxsmm_amd_matdiff_batch(libxsmm_matdiff_info* info, libxsmm_matdiff_info* items, long long* item, libxsmm_datatype datatype,
+  libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst,
+  long long stride_ref, long long stride_tst, long long batch);
+
 #endif /* LIBXSMM_AMD_H */

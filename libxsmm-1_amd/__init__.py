@@ -342,6 +342,9 @@ def _declare(L):
     sig("libxsmm_dnn_dequantize", None, vp, vp, i, ub)
     for nm in ("libxsmm_truncate_convert_f32_bf16", "libxsmm_rnaz_convert_fp32_bfp16", "libxsmm_rne_convert_fp32_bfp16", "libxsmm_convert_bf16_f32"):
         sig(nm, None, vp, vp, u)
+    # matdiff on device operands
+    sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
+    sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -751,3 +754,37 @@ def convert_f32_bf16(inp, out, length, rounding="rne"):
 def convert_bf16_f32(inp, out, length):
     """libxsmm_convert_bf16_f32"""
     lib().libxsmm_convert_bf16_f32(dptr(inp), dptr(out), length)
+
+
+# ---- matdiff on device operands (include/libxsmm_amd.h) --------------------------------------------------------------------------
+MATDIFF_DATATYPES = {"torch.float64": F64, "torch.float32": F32, "torch.int32": 4, "torch.int16": 5, "torch.int8": 6,
+                     "float64": F64, "float32": F32, "int32": 4, "int16": 5, "int8": 6}
+
+
+def matdiff(ref, tst, m=None, n=None, ldref=None, ldtst=None, info=None):
+    """libxsmm_matdiff on torch tensors (or numpy arrays) holding n lines of m elements, ld apart; returns the filled MatdiffInfo.
+    m, n default to a 2-d operand's shape (n lines of m), or to a vector. info: memory the GPU reaches (a tensor of
+    sizeof(MatdiffInfo) bytes) -- the call is libxsmm_amd_matdiff_async then and its status is returned instead."""
+    x = ref if ref is not None else tst
+    if m is None:
+        m, n = (int(x.shape[-1]), int(x.shape[0])) if 2 == len(x.shape) else (int(x.numel() if hasattr(x, "numel") else x.size), 1)
+    dt = MATDIFF_DATATYPES[str(x.dtype)]
+    if info is not None:
+        return lib().libxsmm_amd_matdiff_async(C.cast(dptr(info), C.POINTER(MatdiffInfo)), dt, m, n, dptr(ref), dptr(tst), iptr(ldref), iptr(ldtst))
+    out = MatdiffInfo()
+    rc = lib().libxsmm_matdiff(C.byref(out), dt, m, n, dptr(ref), dptr(tst), iptr(ldref), iptr(ldtst))
+    if 0 != rc:
+        raise RuntimeError("libxsmm_matdiff failed")
+    return out
+
+
+def matdiff_batch(ref, tst, dt, m, n, ldref, ldtst, stride_ref, stride_tst, batch, items=False, info=None):
+    """libxsmm_amd_matdiff_batch; returns (status, info, list of item infos or None, item index)"""
+    out = MatdiffInfo() if info is None else None
+    arr = (MatdiffInfo * max(1, batch))() if items is True else None
+    which = C.c_longlong(-2)
+    pinfo = C.byref(out) if info is None else C.cast(dptr(info), C.POINTER(MatdiffInfo))
+    pitems = arr if items is True else (None if items is None or items is False else C.cast(dptr(items), C.POINTER(MatdiffInfo)))
+    rc = lib().libxsmm_amd_matdiff_batch(pinfo, pitems, C.byref(which), dt, m, n, dptr(ref), dptr(tst), iptr(ldref), iptr(ldtst),
+                                         stride_ref, stride_tst, batch)
+    return rc, out, (list(arr)[:batch] if arr is not None else None), which.value

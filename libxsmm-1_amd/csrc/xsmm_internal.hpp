@@ -317,6 +317,36 @@ int launch_quant_act_tiled(const float* in, short* out, long long nblocks, int C
 int launch_dequant_flat(const short* in, float* out, long long n, float scale, void* stream);
 int launch_bf16_narrow(int rounding /*0: truncate, 1: nearest-away, 2: nearest-even*/, const float* in, unsigned short* out, long long n, void* stream);
 
+// matdiff on device operands (xsmm_matdiff.cpp, kernels/matdiff.hip)
+constexpr int MATDIFF_FIELDS = 19;        // the doubles of libxsmm_matdiff_info, in its order
+enum MatdiffField : int { MD_NORM1_ABS = 0, MD_NORM1_REL, MD_NORMI_ABS, MD_NORMI_REL, MD_NORMF_REL, MD_LINF_ABS, MD_LINF_REL, MD_L2_ABS, MD_L2_REL,
+  MD_L1_REF, MD_MIN_REF, MD_MAX_REF, MD_AVG_REF, MD_VAR_REF, MD_L1_TST, MD_MIN_TST, MD_MAX_TST, MD_AVG_TST, MD_VAR_TST };
+struct MatdiffRecord {                    // the finished statistics of one item, as the kernels pass them on
+  double f[MATDIFF_FIELDS];
+  long long m, n;                         // where linf_abs is (-1: nowhere), or the first non-finite test value (nan != 0)
+  long long item;                         // the item that m, n belong to
+  long long nan;
+};
+struct MatdiffArgs {                      // items of nn lines of mm contiguous elements; every length in elements
+  int datatype;                           // libxsmm_datatype: F64, F32, I32, I16, I8
+  int vec_ref, vec_tst;                   // that operand's base, pitch and stride allow one load per MATDIFF_VEC elements
+  long long mm, nn, ldr, ldt;
+  long long sr, st, batch, item0;         // item i at ref + i * sr and is reported as item0 + i
+  const void* ref; const void* tst;       // memory the GPU reaches; tst may be NULL
+};
+bool matdiff_small(long long mm, long long nn);             // a wave takes a whole item (launch_matdiff_items), else tiles
+size_t matdiff_tiled_workspace(const MatdiffArgs& a);       // bytes launch_matdiff_tiled needs
+long long matdiff_reduce_records(long long count);          // records one level of launch_matdiff_reduce leaves
+// all return hipError_t as int
+int launch_matdiff_items(const MatdiffArgs& a, MatdiffRecord* rec /* [batch] */, void* stream);
+int launch_matdiff_tiled(const MatdiffArgs& a /* batch == 1 */, void* workspace, MatdiffRecord* rec, void* stream);
+int launch_matdiff_reduce(const MatdiffRecord* in, long long count, MatdiffRecord* out, void* stream);
+int launch_matdiff_emit(const MatdiffRecord* rec, long long count, libxsmm_matdiff_info* out, long long* item_out, int swap_norms, int swap_ref,
+  double avg_size, void* stream);
+// libxsmm_matdiff with an operand in plain device memory; false: both are host memory (or there is no device), *rc untouched
+bool matdiff_route(libxsmm_matdiff_info* info, libxsmm_datatype datatype, libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst,
+  const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst, int* rc);
+
 int verbosity();
 bool once(int* flag);   // true the first time
 

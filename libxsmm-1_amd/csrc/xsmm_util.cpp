@@ -232,6 +232,8 @@ LIBXSMM_API void libxsmm_matdiff_clear(libxsmm_matdiff_info* info)
 LIBXSMM_API int libxsmm_matdiff(libxsmm_matdiff_info* info, libxsmm_datatype datatype, libxsmm_blasint m, libxsmm_blasint n,
   const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst)
 {
+  int routed = EXIT_FAILURE; // an operand in plain device memory: the kernels of kernels/matdiff.hip (xsmm_matdiff.cpp)
+  if (xsmm::matdiff_route(info, datatype, m, n, ref, tst, ldref, ldtst, &routed)) return routed;
   bool swapped = false; // statistics of a single set: src/libxsmm_math.c:54,161-172
   if (nullptr == ref && nullptr != tst) { ref = tst; tst = nullptr; swapped = true; }
   if (nullptr == info || nullptr == ref || (LIBXSMM_DATATYPE_F64 != datatype && LIBXSMM_DATATYPE_F32 != datatype) || m < 0 || n < 0) return EXIT_FAILURE;
