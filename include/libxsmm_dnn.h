@@ -1,7 +1,12 @@
-/* libxsmm_dnn.h -- the part of the reference's DNN interface that feeds the low-precision GEMM path: fp32 -> int16
- * quantisation, its inverse and the fp32 <-> bf16 converters (reference: include/libxsmm_dnn.h:331-357 and :414-426,
- * src/libxsmm_dnn.c:2394-2907). The convolution, pooling and tensor-handle interface of that header is not provided
- * (DESIGN.md 9). Line numbers below refer to the reference's include/libxsmm_dnn.h.
+/* libxsmm_dnn.h -- the common part of the reference's DNN interface: error codes, data types, tensor formats, datalayouts and
+ * tensor handles that link caller memory (reference: include/libxsmm_dnn.h:47-263 and :359-390, include/libxsmm_typedefs.h:
+ * 311-346, src/libxsmm_dnn.c:70-189, :330-360, :1000-1570), and the producers of low-precision GEMM inputs: fp32 -> int16
+ * quantisation, its inverse and the fp32 <-> bf16 converters (:331-357 and :414-426, src/libxsmm_dnn.c:2394-2907). The layer
+ * that uses the tensor handles is the fully-connected one (libxsmm_dnn_fullyconnected.h). The convolution, pooling, fused
+ * batch-norm and RNN entry points of the reference are not provided, nor are the descriptors and enumerations
+ * only they use. The common part lies in libxsmm_dnn_tensor.h, a file of this project's that this header includes (the
+ * reference keeps it in libxsmm_dnn.h itself); the quantisation and conversion functions are declared below. Line numbers
+ * refer to the reference's include/libxsmm_dnn.h unless a file is named.
  *
  * Where operands may live: memory the GPU reaches (device, pinned, managed) is processed in place on the calling thread's
  * stream (libxsmm_amd_set_stream); host-visible memory (pinned, managed) is complete on return; pageable host memory is
@@ -11,6 +16,8 @@
 #define LIBXSMM_DNN_H
 
 #include "libxsmm.h"
+
+#include "libxsmm_dnn_tensor.h" /* error codes, data types, formats, datalayouts and tensor handles */
 
 typedef union libxsmm_intfloat { unsigned int ui; float f; } libxsmm_intfloat; /* :334-337 */
 

@@ -78,6 +78,16 @@ class MatdiffInfo(C.Structure):
         [("m", C.c_int), ("n", C.c_int)]
 
 
+class TensorDatalayout(C.Structure):  # libxsmm_dnn_tensor_datalayout
+    _fields_ = [("dim_type", C.POINTER(C.c_int)), ("dim_size", C.POINTER(C.c_uint)), ("num_dims", C.c_uint), ("format", C.c_int),
+                ("custom_format", C.c_int), ("datatype", C.c_int), ("tensor_type", C.c_int)]
+
+
+class FullyconnectedDesc(C.Structure):  # libxsmm_dnn_fullyconnected_desc
+    _fields_ = [(n, C.c_int) for n in ("N", "C", "K", "bn", "bk", "bc", "threads", "datatype_in", "datatype_out", "buffer_format",
+                                       "filter_format", "fuse_ops")]
+
+
 def build(verbose=False):
     """Compile csrc/ into lib/libxsmm.so for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
@@ -342,6 +352,37 @@ def _declare(L):
     sig("libxsmm_dnn_dequantize", None, vp, vp, i, ub)
     for nm in ("libxsmm_truncate_convert_f32_bf16", "libxsmm_rnaz_convert_fp32_bfp16", "libxsmm_rne_convert_fp32_bfp16", "libxsmm_convert_bf16_f32"):
         sig(nm, None, vp, vp, u)
+    # DNN tensors and the fully-connected layer (include/libxsmm_dnn.h, include/libxsmm_dnn_fullyconnected.h)
+    up = C.POINTER(C.c_uint)
+    lp = C.POINTER(TensorDatalayout)
+    sig("libxsmm_dnn_get_error", C.c_char_p, u)
+    sig("libxsmm_dnn_typesize", C.c_size_t, i)
+    sig("libxsmm_dnn_link_tensor", vp, lp, vp, up)
+    sig("libxsmm_dnn_link_qtensor", vp, lp, vp, ub, up)
+    sig("libxsmm_dnn_destroy_tensor", u, vp)
+    sig("libxsmm_dnn_destroy_tensor_datalayout", u, lp)
+    sig("libxsmm_dnn_duplicate_tensor_datalayout", lp, lp, up)
+    sig("libxsmm_dnn_compare_tensor_datalayout", u, lp, lp, up)
+    sig("libxsmm_dnn_get_tensor_size", u, lp, up)
+    sig("libxsmm_dnn_get_tensor_elements", u, lp, up)
+    sig("libxsmm_dnn_set_tensor_data_ptr", u, vp, vp)
+    sig("libxsmm_dnn_get_tensor_data_ptr", vp, vp, up)
+    sig("libxsmm_dnn_get_tensor_datalayout", lp, vp, up)
+    sig("libxsmm_dnn_get_qtensor_scf", ub, vp, up)
+    sig("libxsmm_dnn_set_qtensor_scf", u, vp, ub)
+    sig("libxsmm_dnn_zero_tensor", u, vp)
+    sig("libxsmm_dnn_copyin_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_copyout_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_create_fullyconnected", vp, FullyconnectedDesc, up)
+    sig("libxsmm_dnn_destroy_fullyconnected", u, vp)
+    sig("libxsmm_dnn_fullyconnected_create_tensor_datalayout", lp, vp, i, up)
+    sig("libxsmm_dnn_fullyconnected_get_scratch_size", C.c_size_t, vp, up)
+    sig("libxsmm_dnn_fullyconnected_bind_scratch", u, vp, vp)
+    sig("libxsmm_dnn_fullyconnected_release_scratch", u, vp)
+    sig("libxsmm_dnn_fullyconnected_bind_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_fullyconnected_get_tensor", vp, vp, i, up)
+    sig("libxsmm_dnn_fullyconnected_release_tensor", u, vp, i)
+    sig("libxsmm_dnn_fullyconnected_execute_st", u, vp, i, i, i)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -788,3 +829,63 @@ def matdiff_batch(ref, tst, dt, m, n, ldref, ldtst, stride_ref, stride_tst, batc
     rc = lib().libxsmm_amd_matdiff_batch(pinfo, pitems, C.byref(which), dt, m, n, dptr(ref), dptr(tst), iptr(ldref), iptr(ldtst),
                                          stride_ref, stride_tst, batch)
     return rc, out, (list(arr)[:batch] if arr is not None else None), which.value
+
+
+# ---- DNN tensors and the fully-connected layer (include/libxsmm_dnn.h, include/libxsmm_dnn_fullyconnected.h) ------------------
+DNN_F32, DNN_BF16 = F32, 2
+DNN_FORMAT_LIBXSMM, DNN_FORMAT_NHWC, DNN_FORMAT_NCHW, DNN_FORMAT_RSCK, DNN_FORMAT_KCRS = 1, 2, 4, 8, 16
+DNN_FORMAT_CKPACKED, DNN_FORMAT_NCPACKED = 64, 128
+DNN_FWD, DNN_BWD, DNN_UPD, DNN_BWDUPD, DNN_ALL = 0, 1, 2, 3, 4
+DNN_REGULAR_INPUT, DNN_GRADIENT_INPUT, DNN_REGULAR_OUTPUT, DNN_GRADIENT_OUTPUT, DNN_REGULAR_FILTER, DNN_GRADIENT_FILTER = 0, 3, 5, 6, 10, 12
+DNN_TENSOR_TYPES = (DNN_REGULAR_INPUT, DNN_GRADIENT_INPUT, DNN_REGULAR_OUTPUT, DNN_GRADIENT_OUTPUT, DNN_REGULAR_FILTER, DNN_GRADIENT_FILTER)
+
+
+def fc_create(N, Cc, K, bn=0, bk=0, bc=0, threads=1, datatype_in=DNN_F32, datatype_out=DNN_F32, buffer_format=DNN_FORMAT_LIBXSMM,
+              filter_format=DNN_FORMAT_LIBXSMM, fuse_ops=0):
+    """libxsmm_dnn_create_fullyconnected; returns (handle or None, status)"""
+    st = C.c_uint(0xdead)
+    desc = FullyconnectedDesc(N, Cc, K, bn, bk, bc, threads, datatype_in, datatype_out, buffer_format, filter_format, fuse_ops)
+    h = lib().libxsmm_dnn_create_fullyconnected(desc, C.byref(st))
+    return h, st.value
+
+
+def fc_layout(handle, ttype):
+    """libxsmm_dnn_fullyconnected_create_tensor_datalayout; returns (pointer or None, status). The caller destroys the layout."""
+    st = C.c_uint(0xdead)
+    l = lib().libxsmm_dnn_fullyconnected_create_tensor_datalayout(handle, ttype, C.byref(st))
+    return (l if l else None), st.value
+
+
+def dnn_layout_fields(l):
+    """what a layout says: (num_dims, dim_type list, dim_size list, datatype, format, custom_format, tensor_type)"""
+    c = l.contents
+    n = int(c.num_dims)
+    return n, [int(c.dim_type[j]) for j in range(n)], [int(c.dim_size[j]) for j in range(n)], int(c.datatype), int(c.format), int(c.custom_format), int(c.tensor_type)
+
+
+def dnn_link_tensor(layout, data):
+    """libxsmm_dnn_link_tensor on a torch tensor / numpy array / address; returns (tensor handle or None, status)"""
+    st = C.c_uint(0xdead)
+    t = lib().libxsmm_dnn_link_tensor(layout, dptr(data), C.byref(st))
+    return t, st.value
+
+
+def fc_bind_new(handle, ttype, data):
+    """layout of ttype, a tensor linked to data, bound to the handle; returns the tensor handle (the caller destroys it)"""
+    L = lib()
+    l, st = fc_layout(handle, ttype)
+    if l is None:
+        raise RuntimeError("no layout: status %d" % st)
+    t, st = dnn_link_tensor(l, data)
+    L.libxsmm_dnn_destroy_tensor_datalayout(l)
+    if not t:
+        raise RuntimeError("link failed: status %d" % st)
+    st = L.libxsmm_dnn_fullyconnected_bind_tensor(handle, t, ttype)
+    if 0 != st:
+        raise RuntimeError("bind failed: status %d" % st)
+    return t
+
+
+def fc_execute(handle, kind, start_thread=0, tid=0):
+    """libxsmm_dnn_fullyconnected_execute_st; returns the status"""
+    return lib().libxsmm_dnn_fullyconnected_execute_st(handle, kind, start_thread, tid)

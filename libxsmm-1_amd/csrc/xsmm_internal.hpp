@@ -347,6 +347,22 @@ int launch_matdiff_emit(const MatdiffRecord* rec, long long count, libxsmm_matdi
 bool matdiff_route(libxsmm_matdiff_info* info, libxsmm_datatype datatype, libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst,
   const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst, int* rc);
 
+// fully-connected layer (xsmm_dnn_fc.cpp, kernels/fc.hip): D(i, j) = chain over r of P(i, r) * Q(r, j), blocked operands
+struct FcDim { int blk; long long outer, inner; }; // index x lies at (x / blk) * outer + (x % blk) * inner elements; a plain dimension: blk >= extent
+constexpr int FC_PLAIN = 1 << 30;         // blk of a dimension that is not blocked
+struct FcArgs {
+  const void* p; const void* q; void* d;  // memory the GPU reaches
+  FcDim pi, pr, qr, qj, di, dj;           // the address of an element is the sum of its two dimensions' parts
+  int p_bf16, q_bf16, d_bf16;             // 16-bit elements: widened on load (bits << 16), rounded to nearest even on store
+  int p_rfast, q_rfast;                   // the operand's fast dimension in memory is r: how a work-group's loads are laid over a chunk
+  int R;                                  // length of the chains
+  int i0, i1, j0, j1;                     // the rectangle of D this launch covers (tiles are laid out from i0, j0)
+  // a share that is no rectangle: the element (i, j) belongs to block (i / sbi) * mi + (j / sbj) * mj and is stored if w0 <= block < w1
+  int masked, sbi, mi, sbj, mj, w0, w1;
+  int tile;                               // 64 or 128
+};
+int launch_fc(const FcArgs& args, void* stream, const char** name); // returns hipError_t as int
+
 int verbosity();
 bool once(int* flag);   // true the first time
 
