@@ -8,10 +8,10 @@
 // a two-level strided function (x / blk) * outer + (x % blk) * inner (FcDim), and the address of an element is the sum over
 // its two indices. A work-group re-lays its part on the way into LDS, so no transposed copy and no scratch exist.
 //
-// The tile scheme is that of tgemm.hip: 256 threads (four waves, 2 x 2) own a BT x BT tile of D, BT = 128 (a wave holds
-// 2 x 2 tiles of 32 x 32 in 64 accumulator registers) or BT = 64 (one tile per wave, 16 registers: more work-groups for
-// layers that are small in one dimension -- R is never split, so tiles of D are all the parallelism there is). r advances
-// in chunks of 32 through LDS; the next chunk travels from memory into registers while the matrix cores work.
+// The tile scheme, the arithmetic of a wave and the r loop are those of tile_gemm.cuh: 256 threads (four waves, 2 x 2) own
+// a BT x BT tile of D, BT = 128 (a wave holds 2 x 2 tiles of 32 x 32 in 64 accumulator registers) or BT = 64 (one tile per
+// wave, 16 registers: more work-groups for layers that are small in one dimension -- R is never split, so tiles of D are
+// all the parallelism there is). r advances in chunks of 32 through LDS.
 //
 // Loads. A thread takes BK * BT / 256 elements per operand and chunk. If the operand's fast dimension in memory is the
 // tile index (i or j), the thread keeps one tile index and walks r; if it is r, the thread keeps one r and walks the tile
@@ -28,19 +28,16 @@
 // The table of the tile's output offsets (one division per column, computed by the first BT threads) is read by all lanes
 // of a group at one address per register: a broadcast.
 //
-// The r tail: what is left after the last whole matrix step (R mod 2) is finished with fma on the vector ALU, accumulator
-// element by element. A zero-padded matrix step would not do: fma(0, 0, -0.0) is +0.0.
+// The r tail (R mod 2, on the vector ALU): tile_gemm.cuh.
 #include <hip/hip_runtime.h>
 
 #include "../xsmm_internal.hpp"
+#include "tile_gemm.cuh"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int NTHREADS = 256;
+using tile::NTHREADS;
 constexpr int BK = 32;   // r per chunk
-constexpr int TS = 32;   // extent of a matrix-core tile
 constexpr int LI = 8;    // tile indices per group of loads when r is the fast dimension
 
 struct Walk { int q, rem; }; // an index as (x / blk, x % blk)
@@ -126,19 +123,15 @@ template<int BT> struct Loader {
   }
 };
 
-__device__ __forceinline__ int nrow(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; } // column inside a tile: register r, lane half kl
-
 template<int BT, bool PB, bool QB, bool DB>
 __global__ __launch_bounds__(NTHREADS) void fc_kernel(const xsmm::FcArgs g)
 {
-  constexpr int P = BT + 8, NL = BK * BT / NTHREADS, WT = BT / 2, TW = WT / TS;
+  constexpr int P = BT + 8, NL = BK * BT / NTHREADS, TW = BT / 2 / tile::MfmaF32::TS; // tiles per side of a wave's part
   __shared__ float Ps[BK * P];
   __shared__ float Qs[BK * P];
   __shared__ long long offj[BT]; // where column j of the tile lies in D
   __shared__ int linj[BT];       // its part of the share's block number
-  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int lm = lane % TS, kl = lane / TS;
-  const int wm = WT * (wave & 1), wn = WT * (wave >> 1);
+  const int t = (int)threadIdx.x;
   const int tiles_i = (g.i1 - g.i0 + BT - 1) / BT;
   const int tj = (int)blockIdx.x / tiles_i, ti = (int)blockIdx.x - tj * tiles_i;
   const int it0 = g.i0 + BT * ti, jt0 = g.j0 + BT * tj;
@@ -157,94 +150,33 @@ __global__ __launch_bounds__(NTHREADS) void fc_kernel(const xsmm::FcArgs g)
   lp.init(g.p, g.pi, g.pr, 0 != g.p_rfast, it0, iend, t);
   lq.init(g.q, g.qj, g.qr, 0 != g.q_rfast, jt0, jend, t);
 
-  f32x16 acc[TW][TW]; // [j][i]
-#pragma unroll
-  for (int j = 0; j < TW; ++j) {
-#pragma unroll
-    for (int i = 0; i < TW; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
-    }
-  }
+  tile::MatrixCores<tile::MfmaF32, TW, BK, tile::Plain<float, P> > eng;
+  eng.init(t);
 
   const int R = g.R;
   float rp[NL], rq[NL];
-  lp.template load<PB>(rp, 0, R, t);
-  lq.template load<QB>(rq, 0, R, t);
-  for (int k0 = 0; k0 < R; k0 += BK) {
-    __syncthreads(); // the previous chunk has been consumed
-    lp.store(Ps, rp, t);
-    lq.store(Qs, rq, t);
-    __syncthreads();
-    if (k0 + BK < R) { // the next chunk travels during this chunk's matrix instructions
-      lp.template load<PB>(rp, k0 + BK, R, t);
-      lq.template load<QB>(rq, k0 + BK, R, t);
-    }
-    const int kc = (R - k0 < BK) ? (R - k0) : BK;
-    const int steps = kc / 2;
-    if (BK == kc) {
-#pragma unroll
-      for (int s = 0; s < BK / 2; ++s) {
-        const int kk = 2 * s + kl;
-        float av[TW], bv[TW];
-#pragma unroll
-        for (int i = 0; i < TW; ++i) { av[i] = Ps[kk * P + wm + i * TS + lm]; bv[i] = Qs[kk * P + wn + i * TS + lm]; }
-#pragma unroll
-        for (int j = 0; j < TW; ++j) {
-#pragma unroll
-          for (int i = 0; i < TW; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j], av[i], acc[j][i], 0, 0, 0);
-        }
-      }
-    }
-    else { // the last chunk: whole matrix steps first, then the tail on the vector ALU (no zero-padded step: see above)
-      for (int s = 0; s < steps; ++s) {
-        const int kk = 2 * s + kl;
-        float av[TW], bv[TW];
-#pragma unroll
-        for (int i = 0; i < TW; ++i) { av[i] = Ps[kk * P + wm + i * TS + lm]; bv[i] = Qs[kk * P + wn + i * TS + lm]; }
-#pragma unroll
-        for (int j = 0; j < TW; ++j) {
-#pragma unroll
-          for (int i = 0; i < TW; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j], av[i], acc[j][i], 0, 0, 0);
-        }
-      }
-      for (int kk = 2 * steps; kk < kc; ++kk) {
-        float av[TW];
-#pragma unroll
-        for (int i = 0; i < TW; ++i) av[i] = Ps[kk * P + wm + i * TS + lm];
-#pragma unroll
-        for (int j = 0; j < TW; ++j) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float bn = Qs[kk * P + wn + j * TS + nrow(r, kl)];
-#pragma unroll
-            for (int i = 0; i < TW; ++i) acc[j][i][r] = __builtin_fmaf(av[i], bn, acc[j][i][r]);
-          }
-        }
-      }
-    }
-  }
+  tile::k_loop<BK>(R,
+    [&](int k0) TILE_INLINE { lp.template load<PB>(rp, k0, R, t); lq.template load<QB>(rq, k0, R, t); },
+    [&]() TILE_INLINE { lp.store(Ps, rp, t); lq.store(Qs, rq, t); },
+    [&](int kc) TILE_INLINE { eng.chunk(Ps, Qs, kc); });
 
   // only valid elements of the share are stored (R >= 1: the barriers of the loop have published offj and linj)
+  long long off_i[TW];
+  int lin_i[TW];
 #pragma unroll
   for (int i = 0; i < TW; ++i) {
-    const int ii = it0 + wm + i * TS + lm;
-    if (ii >= iend) continue;
-    const long long off_i = walk_off(walk_init(ii, g.di.blk), g.di);
-    const int lin_i = (0 != g.masked ? (ii / g.sbi) * g.mi : 0);
-#pragma unroll
-    for (int j = 0; j < TW; ++j) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int jl = wn + j * TS + nrow(r, kl);
-        if (jt0 + jl >= jend) continue;
-        if (0 != g.masked) { const int lin = lin_i + linj[jl]; if (lin < g.w0 || lin >= g.w1) continue; }
-        const long long off = off_i + offj[jl];
-        if (DB) static_cast<unsigned short*>(g.d)[off] = rne_bf16(acc[j][i][r]);
-        else static_cast<float*>(g.d)[off] = acc[j][i][r];
-      }
-    }
+    const int ii = it0 + eng.row(i);
+    off_i[i] = walk_off(walk_init(ii, g.di.blk), g.di);
+    lin_i[i] = (0 != g.masked ? (ii / g.sbi) * g.mi : 0);
   }
+  eng.each([&](int i, int j, int r, float v) TILE_INLINE {
+    const int jl = eng.col(j, r);
+    if (it0 + eng.row(i) >= iend || jt0 + jl >= jend) return;
+    if (0 != g.masked) { const int lin = lin_i[i] + linj[jl]; if (lin < g.w0 || lin >= g.w1) return; }
+    const long long off = off_i[i] + offj[jl];
+    if (DB) static_cast<unsigned short*>(g.d)[off] = rne_bf16(v);
+    else static_cast<float*>(g.d)[off] = v;
+  });
 }
 
 template<int BT, bool PB, bool QB, bool DB>

@@ -279,6 +279,14 @@ struct TgemmArgs {                        // C(m x n) = op(A) * op(B) + (beta0 ?
   const void* a; const void* b; void* c;  // memory the GPU reaches
 };
 int launch_tgemm(const TgemmArgs& args, void* stream, const char** name); // returns hipError_t as int
+// One rectangle {m0, m1, n0, n1} of C = op(A) * op(B) + (beta0 ? 0 : C) for a tiled kernel, operands in any memory and plain
+// column-major: ti and to are the element sizes of A / B and of C. Memory the GPU reaches is processed in place, pageable
+// spans of A and B are staged (scratch slots 3 and 4), a pageable C travels as a tight image of the rectangle (slot 5);
+// host-visible memory is complete on return. launch queues the kernel for the rectangle's part of the operands as the GPU
+// sees them and returns hipError_t as int plus the kernel's name. Returns EXIT_SUCCESS or EXIT_FAILURE.
+typedef std::function<int(void* stream, const void* a, const void* b, void* c, long long ldc, int m, int n, const char** name)> RectLaunch;
+int run_rect(size_t ti, size_t to, bool ta, bool tb, int beta0, long long k, long long lda, long long ldb, long long ldc,
+  const unsigned int rect[4], const void* a, const void* b, void* c, const RectLaunch& launch, const char* what);
 // the tiled GEMM for a libxsmm_?gemm call (opt-in LIBXSMM_AMD_TGEMM=1); false: not taken, the caller goes on as before
 bool tgemm_route(int typesize, int flags, int m, int n, int k, int lda, int ldb, int ldc, double alpha, double beta, const void* a, const void* b, void* c);
 

@@ -12,8 +12,6 @@
 #include "xsmm_internal.hpp"
 #include "../../include/libxsmm_amd.h"
 
-#include <hip/hip_runtime_api.h>
-
 #include <atomic>
 #include <cstring>
 
@@ -53,59 +51,18 @@ bool problem_fill(Problem* p, int iprec, int oprec, char transa, char transb, lo
   return true;
 }
 
-// one rectangle {m0, m1, n0, n1} of C, operands in any memory (the twin of run_rect in xsmm_tgemm.cpp: 2-byte inputs, 4-byte C)
-int run_rect(const Problem& h, const unsigned int rect[4], const void* a, const void* b, void* c, const char* what)
+// one rectangle of C through kernels/tgemm_lowp.hip: 2-byte inputs, 4-byte C
+int run_problem(const Problem& h, const unsigned int rect[4], const void* a, const void* b, void* c, const char* what)
 {
-  if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
-  void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  const hipStream_t st = (hipStream_t)stream;
-  constexpr size_t ti = 2, to = 4;
-  const size_t m0 = rect[0], n0 = rect[2];
-  TgemmLowpArgs g; memset(&g, 0, sizeof(g));
-  g.kind = (LOWP_BF16 == h.kind && 0 != fast_mode().load()) ? LOWP_BF16_FAST : h.kind;
-  g.transa = h.ta ? 1 : 0; g.transb = h.tb ? 1 : 0; g.beta0 = h.beta0;
-  g.m = (int)(rect[1] - rect[0]); g.n = (int)(rect[3] - rect[2]); g.k = (int)h.k;
-  g.lda = h.lda; g.ldb = h.ldb; g.ldc = h.ldc;
-  // what the rectangle reads and writes: rows m0 ... of op(A), columns n0 ... of op(B)
-  const char* pa = static_cast<const char*>(a) + (h.ta ? m0 * (size_t)h.lda : m0) * ti;
-  const char* pb = static_cast<const char*>(b) + (h.tb ? n0 : n0 * (size_t)h.ldb) * ti;
-  char* const pc = static_cast<char*>(c) + (n0 * (size_t)h.ldc + m0) * to;
-  const int ka = pointer_kind(pa), kb = pointer_kind(pb), kc = pointer_kind(pc);
-  const bool visible = (0 != ((ka | kb | kc) & 2));
-  bool staged = false;
-  if (0 == (ka & 1)) { // the span of A the task reads, as it lies
-    const size_t nbytes = (h.ta ? ((size_t)(g.m - 1) * h.lda + h.k) : ((size_t)(h.k - 1) * h.lda + g.m)) * ti;
-    void* const p = scratch(3, nbytes);
-    if (nullptr == p || 0 != h2d(p, pa, nbytes)) return EXIT_FAILURE;
-    pa = static_cast<const char*>(p); staged = true;
-  }
-  if (0 == (kb & 1)) {
-    const size_t nbytes = (h.tb ? ((size_t)(h.k - 1) * h.ldb + g.n) : ((size_t)(g.n - 1) * h.ldb + h.k)) * ti;
-    void* const p = scratch(4, nbytes);
-    if (nullptr == p || 0 != h2d(p, pb, nbytes)) return EXIT_FAILURE;
-    pb = static_cast<const char*>(p); staged = true;
-  }
-  char* dc = pc;
-  const size_t tight = (size_t)g.m * to; // bytes of a column of the rectangle
-  if (0 == (kc & 1)) { // a tight image of the rectangle: only the rectangle travels, what lies between m and ldc keeps its bytes
-    dc = static_cast<char*>(scratch(5, tight * g.n));
-    if (nullptr == dc) return EXIT_FAILURE;
-    g.ldc = g.m;
-    if (0 == g.beta0 && hipSuccess != hipMemcpy2DAsync(dc, tight, pc, (size_t)h.ldc * to, tight, (size_t)g.n, hipMemcpyHostToDevice, st)) {
-      (void)hipGetLastError(); return EXIT_FAILURE;
-    }
-  }
-  g.a = pa; g.b = pb; g.c = dc;
-  const char* name = "";
-  const int e = launch_tgemm_lowp(g, stream, &name);
-  note_launch(name);
-  if (0 != e) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e); return EXIT_FAILURE; }
-  if (dc != pc) {
-    if (hipSuccess != hipMemcpy2DAsync(pc, (size_t)h.ldc * to, dc, tight, tight, (size_t)g.n, hipMemcpyDeviceToHost, st)) { (void)hipGetLastError(); return EXIT_FAILURE; }
-    return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  }
-  if (staged || visible) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
+  return run_rect(2, 4, h.ta, h.tb, h.beta0, h.k, h.lda, h.ldb, h.ldc, rect, a, b, c,
+    [&](void* stream, const void* da, const void* db, void* dc, long long ldc, int m, int n, const char** name) {
+      TgemmLowpArgs g; memset(&g, 0, sizeof(g));
+      g.kind = (LOWP_BF16 == h.kind && 0 != fast_mode().load()) ? LOWP_BF16_FAST : h.kind;
+      g.transa = h.ta ? 1 : 0; g.transb = h.tb ? 1 : 0; g.beta0 = h.beta0;
+      g.m = m; g.n = n; g.k = (int)h.k; g.lda = h.lda; g.ldb = h.ldb; g.ldc = ldc;
+      g.a = da; g.b = db; g.c = dc;
+      return launch_tgemm_lowp(g, stream, name);
+    }, what);
 }
 
 // the rectangle of task tid: the partition rule of libxsmm_amd_gemm_task, asked of a handle with the extents of this C
@@ -178,7 +135,7 @@ LIBXSMM_API int libxsmm_amd_lowp_gemm_thread(libxsmm_gemm_precision iprec, libxs
   if (0 == m || 0 == n || 0 == k) return EXIT_SUCCESS;
   unsigned int rect[4];
   if (!task_rect(p, tid, nthreads, rect)) return EXIT_SUCCESS; // a task without work
-  return run_rect(p, rect, a, b, c, "libxsmm_amd_lowp_gemm");
+  return run_problem(p, rect, a, b, c, "libxsmm_amd_lowp_gemm");
 }
 
 LIBXSMM_API int libxsmm_amd_lowp_gemm(libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec, char transa, char transb,

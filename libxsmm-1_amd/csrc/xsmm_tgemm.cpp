@@ -67,66 +67,73 @@ bool task_rect(const libxsmm_gemm_handle& h, int tid, int nthreads, unsigned int
   return m0 < m1 && n0 < n1;
 }
 
-int report(int e, const char* name)
-{
-  note_launch(name);
-  if (0 == e) return EXIT_SUCCESS;
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-  return EXIT_FAILURE;
-}
+} // namespace
 
-// one rectangle {m0, m1, n0, n1} of C, operands in any memory
-int run_rect(const libxsmm_gemm_handle& h, const unsigned int rect[4], const void* a, const void* b, void* c, const char* what)
+int xsmm::run_rect(size_t ti, size_t to, bool ta, bool tb, int beta0, long long k, long long lda, long long ldb, long long ldc,
+  const unsigned int rect[4], const void* a, const void* b, void* c, const RectLaunch& launch, const char* what)
 {
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
   const hipStream_t st = (hipStream_t)stream;
-  const size_t ts = (size_t)h.typesize;
-  const bool ta = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_TRANS_A)), tb = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_TRANS_B));
   const size_t m0 = rect[0], n0 = rect[2];
-  TgemmArgs g; memset(&g, 0, sizeof(g));
-  g.typesize = h.typesize; g.transa = ta ? 1 : 0; g.transb = tb ? 1 : 0; g.beta0 = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? 1 : 0;
-  g.m = (int)(rect[1] - rect[0]); g.n = (int)(rect[3] - rect[2]); g.k = h.k;
-  g.lda = h.lda; g.ldb = h.ldb; g.ldc = h.ldc;
+  const int m = (int)(rect[1] - rect[0]), n = (int)(rect[3] - rect[2]);
   // what the rectangle reads and writes: rows m0 ... of op(A), columns n0 ... of op(B)
-  const char* pa = static_cast<const char*>(a) + (ta ? m0 * (size_t)h.lda : m0) * ts;
-  const char* pb = static_cast<const char*>(b) + (tb ? n0 : n0 * (size_t)h.ldb) * ts;
-  char* const pc = static_cast<char*>(c) + (n0 * (size_t)h.ldc + m0) * ts;
+  const char* pa = static_cast<const char*>(a) + (ta ? m0 * (size_t)lda : m0) * ti;
+  const char* pb = static_cast<const char*>(b) + (tb ? n0 : n0 * (size_t)ldb) * ti;
+  char* const pc = static_cast<char*>(c) + (n0 * (size_t)ldc + m0) * to;
   const int ka = pointer_kind(pa), kb = pointer_kind(pb), kc = pointer_kind(pc);
   const bool visible = (0 != ((ka | kb | kc) & 2));
   bool staged = false;
   if (0 == (ka & 1)) { // the span of A the task reads, as it lies
-    const size_t nbytes = (ta ? ((size_t)(g.m - 1) * h.lda + h.k) : ((size_t)(h.k - 1) * h.lda + g.m)) * ts;
+    const size_t nbytes = (ta ? ((size_t)(m - 1) * lda + k) : ((size_t)(k - 1) * lda + m)) * ti;
     void* const p = scratch(3, nbytes);
     if (nullptr == p || 0 != h2d(p, pa, nbytes)) return EXIT_FAILURE;
     pa = static_cast<const char*>(p); staged = true;
   }
   if (0 == (kb & 1)) {
-    const size_t nbytes = (tb ? ((size_t)(h.k - 1) * h.ldb + g.n) : ((size_t)(g.n - 1) * h.ldb + h.k)) * ts;
+    const size_t nbytes = (tb ? ((size_t)(k - 1) * ldb + n) : ((size_t)(n - 1) * ldb + k)) * ti;
     void* const p = scratch(4, nbytes);
     if (nullptr == p || 0 != h2d(p, pb, nbytes)) return EXIT_FAILURE;
     pb = static_cast<const char*>(p); staged = true;
   }
   char* dc = pc;
-  const size_t tight = (size_t)g.m * ts; // bytes of a column of the rectangle
+  long long dldc = ldc;
+  const size_t tight = (size_t)m * to; // bytes of a column of the rectangle
   if (0 == (kc & 1)) { // a tight image of the rectangle: only the rectangle travels, what lies between m and ldc keeps its bytes
-    dc = static_cast<char*>(scratch(5, tight * g.n));
+    dc = static_cast<char*>(scratch(5, tight * n));
     if (nullptr == dc) return EXIT_FAILURE;
-    g.ldc = g.m;
-    if (0 == g.beta0 && hipSuccess != hipMemcpy2DAsync(dc, tight, pc, (size_t)h.ldc * ts, tight, (size_t)g.n, hipMemcpyHostToDevice, st)) {
+    dldc = m;
+    if (0 == beta0 && hipSuccess != hipMemcpy2DAsync(dc, tight, pc, (size_t)ldc * to, tight, (size_t)n, hipMemcpyHostToDevice, st)) {
       (void)hipGetLastError(); return EXIT_FAILURE;
     }
   }
-  g.a = pa; g.b = pb; g.c = dc;
   const char* name = "";
-  const int e = launch_tgemm(g, stream, &name);
-  if (EXIT_SUCCESS != report(e, name)) return EXIT_FAILURE;
+  const int e = launch(stream, pa, pb, dc, dldc, m, n, &name);
+  note_launch(name);
+  if (0 != e) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e); return EXIT_FAILURE; }
   if (dc != pc) {
-    if (hipSuccess != hipMemcpy2DAsync(pc, (size_t)h.ldc * ts, dc, tight, tight, (size_t)g.n, hipMemcpyDeviceToHost, st)) { (void)hipGetLastError(); return EXIT_FAILURE; }
+    if (hipSuccess != hipMemcpy2DAsync(pc, (size_t)ldc * to, dc, tight, tight, (size_t)n, hipMemcpyDeviceToHost, st)) { (void)hipGetLastError(); return EXIT_FAILURE; }
     return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
   }
   if (staged || visible) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
   return EXIT_SUCCESS;
+}
+
+namespace {
+
+// one rectangle of C through kernels/tgemm.hip
+int run_handle(const libxsmm_gemm_handle& h, const unsigned int rect[4], const void* a, const void* b, void* c, const char* what)
+{
+  const bool ta = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_TRANS_A)), tb = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_TRANS_B));
+  const int beta0 = (0 != (h.gemm_flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? 1 : 0;
+  return run_rect((size_t)h.typesize, (size_t)h.typesize, ta, tb, beta0, h.k, h.lda, h.ldb, h.ldc, rect, a, b, c,
+    [&](void* stream, const void* da, const void* db, void* dc, long long ldc, int m, int n, const char** name) {
+      TgemmArgs g; memset(&g, 0, sizeof(g));
+      g.typesize = h.typesize; g.transa = ta ? 1 : 0; g.transb = tb ? 1 : 0; g.beta0 = beta0;
+      g.m = m; g.n = n; g.k = h.k; g.lda = h.lda; g.ldb = h.ldb; g.ldc = ldc;
+      g.a = da; g.b = db; g.c = dc;
+      return launch_tgemm(g, stream, name);
+    }, what);
 }
 
 bool handle_fill(libxsmm_gemm_handle* h, int iprec, int oprec, const char* transa, const char* transb,
@@ -169,7 +176,7 @@ bool tgemm_route(int typesize, int flags, int m, int n, int k, int lda, int ldb,
   h.magic = HANDLE_MAGIC; h.typesize = typesize; h.gemm_flags = (flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) | (0.0 == beta ? LIBXSMM_GEMM_FLAG_BETA_0 : 0);
   h.m = m; h.n = n; h.k = k; h.lda = lda; h.ldb = ldb; h.ldc = ldc; h.ntasks = 1;
   const unsigned int rect[4] = { 0, (unsigned int)m, 0, (unsigned int)n };
-  (void)run_rect(h, rect, a, b, c, "libxsmm_?gemm");
+  (void)run_handle(h, rect, a, b, c, "libxsmm_?gemm");
   return true;
 }
 
@@ -214,7 +221,7 @@ LIBXSMM_API void libxsmm_gemm_thread(const libxsmm_gemm_handle* handle, void* sc
   if (nullptr == a || nullptr == b || nullptr == c) { complain(&error_once, "libxsmm_gemm_thread: an operand is NULL!"); return; }
   unsigned int rect[4];
   if (!task_rect(*handle, tid, nthreads, rect)) return; // a task without work
-  (void)run_rect(*handle, rect, a, b, c, "libxsmm_gemm_thread");
+  (void)run_handle(*handle, rect, a, b, c, "libxsmm_gemm_thread");
 }
 
 LIBXSMM_APIEXT void libxsmm_xgemm_omp(libxsmm_gemm_precision iprec, libxsmm_gemm_precision oprec, const char* transa, const char* transb,
