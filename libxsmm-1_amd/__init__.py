@@ -88,6 +88,11 @@ class FullyconnectedDesc(C.Structure):  # libxsmm_dnn_fullyconnected_desc
                                        "filter_format", "fuse_ops")]
 
 
+class PoolingDesc(C.Structure):  # libxsmm_dnn_pooling_desc
+    _fields_ = [(n, C.c_int) for n in ("N", "C", "H", "W", "R", "S", "u", "v", "pad_h", "pad_w", "pad_h_in", "pad_w_in", "pad_h_out", "pad_w_out",
+                                       "threads", "datatype_in", "datatype_out", "datatype_mask", "buffer_format", "pooling_type")]
+
+
 def build(verbose=False):
     """Compile csrc/ into lib/libxsmm.so for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
@@ -383,6 +388,17 @@ def _declare(L):
     sig("libxsmm_dnn_fullyconnected_get_tensor", vp, vp, i, up)
     sig("libxsmm_dnn_fullyconnected_release_tensor", u, vp, i)
     sig("libxsmm_dnn_fullyconnected_execute_st", u, vp, i, i, i)
+    # the pooling layer (include/libxsmm_dnn_pooling.h)
+    sig("libxsmm_dnn_create_pooling", vp, PoolingDesc, up)
+    sig("libxsmm_dnn_destroy_pooling", u, vp)
+    sig("libxsmm_dnn_pooling_create_tensor_datalayout", lp, vp, i, up)
+    sig("libxsmm_dnn_pooling_get_scratch_size", C.c_size_t, vp, up)
+    sig("libxsmm_dnn_pooling_bind_scratch", u, vp, vp)
+    sig("libxsmm_dnn_pooling_release_scratch", u, vp)
+    sig("libxsmm_dnn_pooling_bind_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_pooling_get_tensor", vp, vp, i, up)
+    sig("libxsmm_dnn_pooling_release_tensor", u, vp, i)
+    sig("libxsmm_dnn_pooling_execute_st", u, vp, i, i, i)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -889,3 +905,47 @@ def fc_bind_new(handle, ttype, data):
 def fc_execute(handle, kind, start_thread=0, tid=0):
     """libxsmm_dnn_fullyconnected_execute_st; returns the status"""
     return lib().libxsmm_dnn_fullyconnected_execute_st(handle, kind, start_thread, tid)
+
+
+# ---- the pooling layer (include/libxsmm_dnn_pooling.h) ---------------------------------------------------------------------------
+DNN_I32, DNN_I16 = 4, 5
+DNN_POOLING_MAX, DNN_POOLING_AVG = 1, 2
+DNN_POOLING_MASK = 31
+
+
+def pool_create(N, Cc, H, W, R, S, u, v, pad_h=0, pad_w=0, pad_h_in=0, pad_w_in=0, pad_h_out=0, pad_w_out=0, threads=1, datatype_in=DNN_F32,
+                datatype_out=DNN_F32, datatype_mask=DNN_I32, buffer_format=DNN_FORMAT_LIBXSMM, pooling_type=DNN_POOLING_MAX):
+    """libxsmm_dnn_create_pooling; returns (handle or None, status)"""
+    st = C.c_uint(0xdead)
+    desc = PoolingDesc(N, Cc, H, W, R, S, u, v, pad_h, pad_w, pad_h_in, pad_w_in, pad_h_out, pad_w_out, threads, datatype_in, datatype_out,
+                       datatype_mask, buffer_format, pooling_type)
+    h = lib().libxsmm_dnn_create_pooling(desc, C.byref(st))
+    return h, st.value
+
+
+def pool_layout(handle, ttype):
+    """libxsmm_dnn_pooling_create_tensor_datalayout; returns (pointer or None, status). The caller destroys the layout."""
+    st = C.c_uint(0xdead)
+    l = lib().libxsmm_dnn_pooling_create_tensor_datalayout(handle, ttype, C.byref(st))
+    return (l if l else None), st.value
+
+
+def pool_bind_new(handle, ttype, data):
+    """layout of ttype, a tensor linked to data, bound to the handle; returns the tensor handle (the caller destroys it)"""
+    L = lib()
+    l, st = pool_layout(handle, ttype)
+    if l is None:
+        raise RuntimeError("no layout: status %d" % st)
+    t, st = dnn_link_tensor(l, data)
+    L.libxsmm_dnn_destroy_tensor_datalayout(l)
+    if not t:
+        raise RuntimeError("link failed: status %d" % st)
+    st = L.libxsmm_dnn_pooling_bind_tensor(handle, t, ttype)
+    if 0 != st:
+        raise RuntimeError("bind failed: status %d" % st)
+    return t
+
+
+def pool_execute(handle, kind, start_thread=0, tid=0):
+    """libxsmm_dnn_pooling_execute_st; returns the status"""
+    return lib().libxsmm_dnn_pooling_execute_st(handle, kind, start_thread, tid)

@@ -1,0 +1,362 @@
+"""The pooling layer restated in numpy: handle rules, datalayouts, scratch formula, the statuses of execute_st, the split over
+logical threads, seeded inputs, and the arithmetic contract of include/libxsmm_dnn_pooling.h (FWD and BWD, MAX and AVG, fp32
+and bf16) as plain array code. Shared by tests/test_pool_cpu.py, tests/test_pool_gpu.py and tools/golden/pool_capture.py; the
+reference's own answers are in tests/golden/pool.npz and tests/test_pool_cpu.py holds this file against them bit for bit."""
+import os
+import zlib
+
+import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+F32, BF16, I32, I16 = 1, 2, 4, 5
+FMT_LIBXSMM, FMT_NHWC, FMT_NCHW = 1, 2, 4
+FWD, BWD, UPD, BWDUPD, ALL = 0, 1, 2, 3, 4
+MAX, AVG = 1, 2
+REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, GEN_IN, GEN_OUT, REG_FIL, MASK = 0, 3, 5, 6, 7, 8, 10, 31
+BINDABLE = (REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, MASK)
+LAYOUT_TYPES = BINDABLE + (GEN_IN, GEN_OUT, REG_FIL)  # the layouts the capture asks for (the last one is no pooling tensor)
+DIM_N, DIM_H, DIM_W, DIM_C = 0, 1, 2, 3
+
+SUCCESS = 0
+ERR_GENERAL, ERR_UNSUPPORTED_DATATYPE, ERR_INVALID_HANDLE, ERR_DATA_NOT_BOUND = 100000, 100002, 100004, 100005
+ERR_MISMATCH_TENSOR, ERR_INVALID_HANDLE_TENSOR, ERR_INVALID_KIND, ERR_INVALID_FORMAT_GENERAL = 100008, 100009, 100010, 100016
+ERR_SCRATCH_NOT_ALLOCED, ERR_UNKNOWN_TENSOR_TYPE, ERR_INVALID_FORMAT_FUSEDBN, ERR_UNSUPPORTED_POOLING = 100020, 100021, 100032, 100033
+
+FLT_MAX = np.float32(3.4028234663852886e38)
+SENTINEL = -1  # what the mask is pre-filled with: FWD leaves it where no input exceeded -FLT_MAX
+
+DESC_FIELDS = ("N", "C", "H", "W", "R", "S", "u", "v", "pad_h", "pad_w", "pad_h_in", "pad_w_in", "pad_h_out", "pad_w_out", "threads",
+               "datatype_in", "datatype_out", "datatype_mask", "buffer_format", "pooling_type")
+
+
+def desc(H, W, R, S, u, v, pad_h=0, pad_w=0, pin=(0, 0), pout=(0, 0), N=2, C=32, pool=MAX, dt=F32, dt_out=None, dt_mask=I32, fmt=FMT_LIBXSMM, threads=1):
+    return dict(N=N, C=C, H=H, W=W, R=R, S=S, u=u, v=v, pad_h=pad_h, pad_w=pad_w, pad_h_in=pin[0], pad_w_in=pin[1], pad_h_out=pout[0],
+                pad_w_out=pout[1], threads=threads, datatype_in=dt, datatype_out=dt if dt_out is None else dt_out, datatype_mask=dt_mask,
+                buffer_format=fmt, pooling_type=pool)
+
+
+# the shapes of tests/test_pool_gpu.py: the smallest at which each mistake shows (N = 2, C = 32: two channel blocks, four items)
+SHAPES = {
+    "a": dict(H=7, W=7, R=3, S=3, u=2, v=2, pad_h=1, pad_w=1),                                  # overlap, logical padding on all four edges
+    "b": dict(H=9, W=11, R=2, S=3, u=2, v=1, pad_h=0, pad_w=1, pin=(1, 2), pout=(2, 1)),        # H/W, R/S, u/v swapped; padded strides
+    "c": dict(H=8, W=8, R=2, S=2, u=2, v=2),                                                    # no overlap
+    "d": dict(H=8, W=8, R=3, S=3, u=2, v=2),                                                    # the floor leaves row / column 7 uncovered
+    "e": dict(H=9, W=9, R=2, S=2, u=3, v=3),                                                    # stride above kernel: holes inside
+    "f": dict(H=7, W=7, R=7, S=7, u=1, v=1),                                                    # global pooling
+    "g": dict(H=6, W=6, R=3, S=3, u=1, v=1, pad_h=1, pad_w=1),                                  # nine covering outputs per input
+    "h": dict(H=33, W=33, R=3, S=3, u=2, v=2, pad_h=1, pad_w=1),                                # 17 x 17 outputs: more than one tile
+}
+
+
+def compute_cases():
+    """name -> desc; the name ends in the kind of input: n random normals, t a 7-value alphabet (ties in most windows)"""
+    out = {}
+    for s, shape in SHAPES.items():
+        for pool, pname in ((MAX, "max"), (AVG, "avg")):
+            for dt, dname in ((F32, "f32"), (BF16, "bf16")):
+                for kind in ("n", "t"):
+                    out["%s_%s_%s_%s" % (s, pname, dname, kind)] = desc(pool=pool, dt=dt, **shape)
+    out["c24_max_f32_n"] = desc(C=24, **SHAPES["a"])   # the remainder of 8 channels is dropped silently: one block
+    out["c24_avg_bf16_n"] = desc(C=24, pool=AVG, dt=BF16, **SHAPES["a"])
+    return out
+
+
+COMPUTE_CASES = compute_cases()
+# windows that are all NaN / all -FLT_MAX (bf16: -Inf, as -FLT_MAX is no bf16 number): FWD only, the mask keeps its sentinel there
+SPECIAL_CASES = {"nanwin_f32": desc(**SHAPES["c"]), "nanwin_bf16": desc(dt=BF16, **SHAPES["c"])}
+# what the capture stores of the compute cases: all of them would exceed the size aimed at, and the alphabet kind (ties) says
+# nothing about AVG, or about the 16-bit MAX, that the normals and the fp32 MAX do not
+GOLDEN_CASES = [n for n in COMPUTE_CASES if n.endswith("_n") or "_max_f32_" in n]
+STATUS_CASES = {
+    "e_f32_bf16": desc(dt=F32, dt_out=BF16, **SHAPES["c"]), "e_bf16_f32": desc(dt=BF16, dt_out=F32, **SHAPES["c"]),
+    "e_c8": desc(C=8, **SHAPES["c"]), "e_nhwc": desc(fmt=FMT_NHWC, **SHAPES["c"]), "e_nhwc_bf16": desc(fmt=FMT_NHWC, dt=BF16, dt_mask=I16, **SHAPES["c"]),
+    "e_nchw": desc(fmt=FMT_NCHW, **SHAPES["c"]),
+    "e_fmt3": desc(fmt=FMT_LIBXSMM | FMT_NHWC, pool=AVG, **SHAPES["c"]), "e_pool3": desc(pool=3, **SHAPES["c"]), "e_avg_nomask": desc(pool=AVG, **SHAPES["c"]),
+    "e_unbound_regin": desc(pool=AVG, **SHAPES["c"]), "e_unbound_regout": desc(pool=AVG, **SHAPES["c"]), "e_unbound_gradin": desc(pool=AVG, **SHAPES["c"]),
+    "e_unbound_gradout": desc(pool=AVG, **SHAPES["c"]), "e_unbound_mask": desc(**SHAPES["c"]), "e_mask_i16": desc(dt_mask=I16, **SHAPES["c"]),
+}
+UNBOUND = {"e_avg_nomask": (MASK,), "e_unbound_regin": (REG_IN,), "e_unbound_regout": (REG_OUT,), "e_unbound_gradin": (GRAD_IN,),
+           "e_unbound_gradout": (GRAD_OUT,), "e_unbound_mask": (MASK,)}
+# cases the reference must not execute: it writes C-wide pixels into an output layout of zero elements (C = 8) and 32-bit
+# indices into a 16-bit mask
+NO_RUN = ("e_c8", "e_mask_i16")
+
+
+def all_cases():
+    out = dict(COMPUTE_CASES)
+    out.update(SPECIAL_CASES)
+    out.update(STATUS_CASES)
+    return out
+
+
+def captured_cases():
+    out = {n: COMPUTE_CASES[n] for n in GOLDEN_CASES}
+    out.update(SPECIAL_CASES)
+    out.update(STATUS_CASES)
+    return out
+
+
+def _cdiv(a, b):
+    """C's integer division (towards zero)"""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+# ---- handle rules (src/libxsmm_dnn_pooling.c:44-95, src/libxsmm_dnn_setup.c:197-252) -------------------------------------------
+class Handle:
+    def __init__(self, d):
+        self.d = d
+        self.ok = False
+        pair = (d["datatype_in"], d["datatype_out"])
+        if pair not in ((F32, F32), (BF16, BF16)):
+            self.status = ERR_UNSUPPORTED_DATATYPE
+            return
+        self.status = SUCCESS
+        self.f32 = pair == (F32, F32)
+        Cc = d["C"]
+        if self.f32:
+            self.ifmblock, self.fm_lp_block = (16 if Cc >= 16 else Cc), 1
+        else:
+            self.ifmblock, self.fm_lp_block = (8 if Cc >= 16 else Cc // 2), 2
+            if Cc == 3:
+                self.ifmblock, self.fm_lp_block = 3, 1
+        self.ofmblock = 16
+        self.ifmblock_hp, self.ofmblock_lp = self.ifmblock * self.fm_lp_block, self.ofmblock // self.fm_lp_block
+        self.blocksifm = Cc // (self.ifmblock if self.f32 else self.ifmblock_hp)
+        self.blocksofm = Cc // self.ofmblock
+        self.ofh = _cdiv(d["H"] + 2 * d["pad_h"] - d["R"], d["u"]) + 1
+        self.ofw = _cdiv(d["W"] + 2 * d["pad_w"] - d["S"], d["v"]) + 1
+        self.scratch_size = 4 * (d["H"] + 2 * max(d["pad_h_in"], d["pad_h_out"])) * (d["W"] + 2 * max(d["pad_w_in"], d["pad_w_out"])) \
+            * max(self.ofmblock, self.ifmblock) * d["threads"]
+        self.ifhp, self.ifwp = d["H"] + 2 * d["pad_h_in"], d["W"] + 2 * d["pad_w_in"]
+        self.ofhp, self.ofwp = self.ofh + 2 * d["pad_h_out"], self.ofw + 2 * d["pad_w_out"]
+        self.ok = True
+
+    def scratch(self):
+        return self.scratch_size + 64
+
+    def layout(self, t):
+        """(status, None) or (0, dict) as libxsmm_dnn_pooling_create_tensor_datalayout (:114-291)"""
+        d = self.d
+        inp, out, mask = t in (REG_IN, GRAD_IN, GEN_IN), t in (REG_OUT, GRAD_OUT, GEN_OUT), t == MASK
+        fmt = d["buffer_format"]
+
+        def made(types, sizes, datatype):
+            return SUCCESS, dict(num_dims=len(types), dim_type=list(types), dim_size=[int(s) for s in sizes], datatype=datatype, format=fmt,
+                                 custom_format=1, tensor_type=0)
+        if not (inp or out or mask):
+            return ERR_UNKNOWN_TENSOR_TYPE, None
+        if fmt & FMT_LIBXSMM:
+            if mask:  # always five dimensions over (ofw, ofh), without physical padding
+                return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), (self.ofmblock, self.ofw, self.ofh, self.blocksofm, d["N"]), d["datatype_mask"])
+            if self.f32:
+                sizes = (self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp else (self.ofmblock, self.ofwp, self.ofhp, self.blocksofm, d["N"])
+                return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, F32)
+            sizes = (self.fm_lp_block, self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp \
+                else (self.fm_lp_block, self.ofmblock_lp, self.ofwp, self.ofhp, self.blocksofm, d["N"])
+            return made((DIM_C, DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, BF16)
+        if fmt & FMT_NHWC:
+            if mask:  # (the reference sets the mask's datatype to datatype_in and then has no sizes for it)
+                return ERR_UNKNOWN_TENSOR_TYPE, None
+            sizes = (d["C"], self.ifwp, self.ifhp, d["N"]) if inp else (d["C"], self.ofwp, self.ofhp, d["N"])
+            return made((DIM_C, DIM_W, DIM_H, DIM_N), sizes, d["datatype_in"])
+        return ERR_INVALID_FORMAT_GENERAL, None
+
+    def runnable(self):
+        """the channel block is the 16 the kernels are written for, on both sides"""
+        return self.ifmblock_hp == 16 and self.blocksifm == self.blocksofm
+
+    def execute_status(self, kind, bound, ltid=0):
+        """what execute_st returns before anything is computed (bound: the tensor types that are bound). Up to
+        ERR_UNSUPPORTED_POOLING the reference's order; the last three checks are this engine's own."""
+        d = self.d
+        if kind not in (FWD, BWD):
+            return ERR_INVALID_KIND
+        if d["buffer_format"] != FMT_LIBXSMM:
+            return ERR_INVALID_FORMAT_FUSEDBN
+        need = (REG_IN, REG_OUT) if kind == FWD else (GRAD_IN, GRAD_OUT)
+        if any(t not in bound for t in need) or (d["pooling_type"] == MAX and MASK not in bound):
+            return ERR_DATA_NOT_BOUND
+        if d["pooling_type"] not in (MAX, AVG):
+            return ERR_UNSUPPORTED_POOLING
+        if ltid < 0 or d["threads"] < 1:
+            return ERR_GENERAL
+        if d["pooling_type"] == MAX and d["datatype_mask"] != I32:
+            return ERR_UNSUPPORTED_DATATYPE
+        if not self.runnable():
+            return ERR_GENERAL
+        return SUCCESS
+
+    def work(self):
+        return self.d["N"] * self.blocksifm
+
+    def share(self, ltid):
+        work, threads = self.work(), self.d["threads"]
+        chunk = work // threads if work % threads == 0 else work // threads + 1
+        return min(ltid * chunk, work), min((ltid + 1) * chunk, work)
+
+    # shapes of the blocked tensors as arrays [item][row][column][16]
+    def in_shape(self):
+        return (self.work(), self.ifhp, self.ifwp, 16)
+
+    def out_shape(self):
+        return (self.work(), self.ofhp, self.ofwp, 16)
+
+    def mask_shape(self):
+        return (self.work(), self.ofh, self.ofw, 16)
+
+
+def layout_size(l):
+    n = 1
+    for s in l["dim_size"]:
+        n *= s
+    return n * {F32: 4, BF16: 2, I32: 4, I16: 2}[l["datatype"]], n
+
+
+# ---- 16-bit elements: widened by a shift, stored by truncation (the generic templates' union) -------------------------------------
+def widen(a):
+    return (np.asarray(a, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def truncate(a):
+    return (np.ascontiguousarray(a, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
+
+
+def as_f32(h, a):
+    return a if h.f32 else widen(a)
+
+
+def stored(h, a):
+    return a.astype(np.float32) if h.f32 else truncate(a)
+
+
+def elem_dtype(h):
+    return np.float32 if h.f32 else np.uint16
+
+
+# ---- inputs: seeded, in the tensors' own layout (physical padding included: it is never read) -----------------------------------
+def inputs(name, d):
+    """(x, dout): the whole REGULAR_INPUT and GRADIENT_OUTPUT tensors, [item][row][column][16] in the element type"""
+    h = Handle(d)
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    if name.endswith("_t"):
+        x = rng.integers(-3, 4, size=h.in_shape()).astype(np.float32)
+        dout = rng.integers(-3, 4, size=h.out_shape()).astype(np.float32)
+    else:
+        x = rng.standard_normal(h.in_shape()).astype(np.float32)
+        dout = rng.standard_normal(h.out_shape()).astype(np.float32)
+    if name.startswith("nanwin"):
+        lowest = -FLT_MAX if h.f32 else np.float32(-np.inf)
+        x[0, 0:2, 0:2, :] = np.nan          # item 0, output (0, 0): a NaN never wins
+        x[1, 2:4, 4:6, :] = lowest          # item 1, output (1, 2): nothing exceeds -FLT_MAX
+        x[3, 6:8, 0:2, 3] = np.nan          # item 3, output (3, 0): one channel lane only
+    if not h.f32:
+        x, dout = truncate(x), truncate(dout)
+    return x, dout
+
+
+# ---- the arithmetic contract ---------------------------------------------------------------------------------------------------------
+def _windows(h):
+    """per (kh, kw): the outputs whose window position lies inside the plane, and the input coordinates it reads"""
+    d = h.d
+    for kh in range(d["R"]):
+        hi = np.arange(h.ofh) * d["u"] - d["pad_h"] + kh
+        hv = np.nonzero((hi >= 0) & (hi < d["H"]))[0]
+        for kw in range(d["S"]):
+            wi = np.arange(h.ofw) * d["v"] - d["pad_w"] + kw
+            wv = np.nonzero((wi >= 0) & (wi < d["W"]))[0]
+            if hv.size and wv.size:
+                yield hv, wv, hi[hv], wi[wv]
+
+
+def forward(h, x, out, mask=None):
+    """FWD into the pre-filled destinations out (element type) and mask (int32, MAX only), in place: the interior of out and
+    the mask elements whose output found an input above -FLT_MAX are written, nothing else."""
+    d = h.d
+    iph, ipw, oph, opw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
+    xin = as_f32(h, x)[:, iph:iph + d["H"], ipw:ipw + d["W"], :]
+    lanes = np.arange(16, dtype=np.int32)
+    work = h.work()
+    if d["pooling_type"] == MAX:
+        cur = np.full((work, h.ofh, h.ofw, 16), -FLT_MAX, dtype=np.float32)
+        idx = np.full((work, h.ofh, h.ofw, 16), SENTINEL, dtype=np.int32)
+        for hv, wv, hi, wi in _windows(h):  # kh ascending, then kw ascending; a strict > replaces: the first maximum wins, a NaN never
+            v = xin[:, hi[:, None], wi[None, :], :]
+            here = ((hi[:, None] * d["W"] + wi[None, :]) * 16).astype(np.int32)[None, :, :, None] + lanes
+            c, i = cur[:, hv[:, None], wv[None, :], :], idx[:, hv[:, None], wv[None, :], :]
+            won = v > c
+            cur[:, hv[:, None], wv[None, :], :] = np.where(won, v, c)
+            idx[:, hv[:, None], wv[None, :], :] = np.where(won, here, i)
+        np.copyto(mask, idx, where=idx != SENTINEL)
+        res = cur
+    else:
+        acc = np.zeros((work, h.ofh, h.ofw, 16), dtype=np.float32)
+        for hv, wv, hi, wi in _windows(h):
+            acc[:, hv[:, None], wv[None, :], :] = acc[:, hv[:, None], wv[None, :], :] + xin[:, hi[:, None], wi[None, :], :]
+        recp = np.float32(1.0) / (np.float32(d["R"]) * np.float32(d["S"]))
+        res = acc * recp
+    out[:, oph:oph + h.ofh, opw:opw + h.ofw, :] = stored(h, res)
+
+
+def _fma(a, b, c):
+    """fp32 fma of arrays through float64: the product is exact there; the sum is rounded twice (to 53, then 24 bits), which
+    differs from one rounding only in rare halfway cases -- good enough to tell the fused form from the separate one"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def backward(h, dout, mask, din, fused=False):
+    """BWD into the interior of the pre-filled din (element type), in place. Per input element the contributions arrive with ho
+    ascending, then wo ascending -- the order of the reference's scatter and of the engine's gather -- from +0.0.
+    AVG: acc + dout * recp as a separate multiply and add (fused=True: the form the reference does not have; for the test that
+    tells them apart). MAX trusts only masks FWD could have written: inside the output's window, in the element's own lane."""
+    d = h.d
+    iph, ipw, oph, opw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
+    H, W, work = d["H"], d["W"], h.work()
+    g = as_f32(h, dout)[:, oph:oph + h.ofh, opw:opw + h.ofw, :]
+    acc = np.zeros((work, H, W, 16), dtype=np.float32)
+    recp = np.float32(1.0) / (np.float32(d["R"]) * np.float32(d["S"]))
+    lanes = np.arange(16, dtype=np.int64)
+    flat = acc.reshape(work, H * W * 16)
+    for ho in range(h.ofh):
+        h0 = ho * d["u"] - d["pad_h"]
+        for wo in range(h.ofw):
+            w0 = wo * d["v"] - d["pad_w"]
+            if d["pooling_type"] == MAX:
+                m = mask[:, ho, wo, :].astype(np.int64)
+                mh, mw = (m // 16) // W, (m // 16) % W
+                ok = (m >= 0) & (m < H * W * 16) & (m % 16 == lanes) & (mh >= h0) & (mh < h0 + d["R"]) & (mw >= w0) & (mw < w0 + d["S"])
+                ii, ll = np.nonzero(ok)
+                flat[ii, m[ii, ll]] = flat[ii, m[ii, ll]] + g[ii, ho, wo, ll]  # (one element per lane: no index repeats)
+            else:
+                a0, a1, b0, b1 = max(h0, 0), min(h0 + d["R"], H), max(w0, 0), min(w0 + d["S"], W)
+                if a0 < a1 and b0 < b1:
+                    t = g[:, ho, wo, :][:, None, None, :]
+                    part = acc[:, a0:a1, b0:b1, :]
+                    acc[:, a0:a1, b0:b1, :] = _fma(np.broadcast_to(t, part.shape), recp, part) if fused else part + t * recp
+    din[:, iph:iph + H, ipw:ipw + W, :] = stored(h, acc)
+
+
+def expected(name, d, fused=False):
+    """dict of the tensors of a case after FWD and BWD on destinations pre-filled with ones bits (NaN / 0xffff) and a mask
+    pre-filled with SENTINEL: x, dout, out, mask (MAX), din (None where BWD must not run on the reference: sentinels left)"""
+    h = Handle(d)
+    x, dout = inputs(name, d)
+    fill = np.float32(np.nan) if h.f32 else np.uint16(0xffff)
+    out = np.full(h.out_shape(), fill, dtype=elem_dtype(h))
+    din = np.full(h.in_shape(), fill, dtype=elem_dtype(h))
+    if h.f32:  # (the capture fills with 0xff bytes: that NaN's bits)
+        out.view(np.uint32)[...] = 0xffffffff
+        din.view(np.uint32)[...] = 0xffffffff
+    mask = np.full(h.mask_shape(), SENTINEL, dtype=np.int32) if d["pooling_type"] == MAX else None
+    forward(h, x, out, mask)
+    backward(h, dout, mask, din, fused)
+    return dict(x=x, dout=dout, out=out, mask=mask, din=din)
+
+
+def crc(a):
+    return zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+def load_golden():
+    return np.load(os.path.join(GOLDEN, "pool.npz"))
