@@ -1,0 +1,375 @@
+"""Operands whose element offsets pass 2^31 (and whose byte offsets pass 2^32): the 64-bit instantiation of the quantise layout
+kernel, leading dimensions of 2^30 + 7 in the tiled GEMMs, a strided batch with a C stride of 2^20 elements, fsspmdm at the
+leading dimension of BASELINE config 3, and pooling over more than 2^31 elements.
+
+The operands are built on the device and never travel whole. Each case checks (i) a sample gathered to the host against the
+family's host reference -- everywhere the call writes where that is small, otherwise at least 256 places that include the
+first and the last element and the neighbours of offset 2^31 --, (ii) canaries: what the call must not touch, compared on the
+device in slabs, and (iii) a property of the whole array where there is one. A case needs up to 20 GiB and skips only where
+torch.cuda.mem_get_info() shows less free memory than it needs; on an MI355X none does."""
+import ctypes as C
+import glob
+import os
+
+import numpy as np
+import pytest
+
+import launch_limits as ll
+import lowp_gemm_common as lg
+import pool_common as pc
+import quant_common as qc
+from conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+GiB = 1 << 30
+W31 = 1 << 31
+SLAB = 1 << 28  # elements compared at once on the device
+
+
+def need(torch, nbytes):
+    assert nbytes <= 20 * GiB
+    free = torch.cuda.mem_get_info()[0]
+    if free < nbytes + GiB:
+        pytest.skip("%.1f GiB free, the case needs %.1f" % (free / GiB, nbytes / GiB + 1))
+
+
+def all_equal(torch, t, value, lo, hi):
+    """t[lo:hi] == value everywhere, slab by slab"""
+    for s in range(lo, hi, SLAB):
+        if not bool((t[s:min(hi, s + SLAB)] == value).all()):
+            return False
+    return True
+
+
+def none_is(torch, t, pred):
+    for s in range(0, t.numel(), SLAB):
+        if bool(pred(t[s:s + SLAB]).any()):
+            return False
+    return True
+
+
+# ---- quantise: the layout kernel with 64-bit indices ------------------------------------------------------------------------------
+def act_source_at(o, N, Cc, H, W, cb32, cb16, lp):
+    """tests/quant_common.py:act_source for single output positions (int64 arrays)"""
+    cb = cb16 * lp
+    cin = o % cb; o = o // cb
+    i4 = o % W; o = o // W
+    i3 = o % H; o = o // H
+    i2 = o % (Cc // cb); i1 = o // (Cc // cb)
+    c = i2 * cb + cin
+    return (((i1 * (Cc // cb32) + c // cb32) * H + i3) * W + i4) * cb32 + c % cb32
+
+
+def act_dest_at(s, N, Cc, H, W, cb32, cb16, lp):
+    """the output position that reads input position s"""
+    cb = cb16 * lp
+    fi5 = s % cb32; s = s // cb32
+    i4 = s % W; s = s // W
+    i3 = s % H; s = s // H
+    fi2 = s % (Cc // cb32); i1 = s // (Cc // cb32)
+    c = fi2 * cb32 + fi5
+    return (((i1 * (Cc // cb) + c // cb) * H + i3) * W + i4) * cb + c % cb
+
+
+def fil_source_at(o, K, Cc, R, S, cb32, cb16, kb32, kb16, lp):
+    i7 = o % lp; o = o // lp
+    i6 = o % kb16; o = o // kb16
+    i5 = o % cb16; o = o // cb16
+    i4 = o % S; o = o // S
+    i3 = o % R; o = o // R
+    cblk = Cc // (cb16 * lp)
+    i2 = o % cblk; i1 = o // cblk
+    k = i1 * kb16 + i6
+    c = (i2 * cb16 + i5) * lp + i7
+    return ((((k // kb32 * (Cc // cb32) + c // cb32) * R + i3) * S + i4) * cb32 + c % cb32) * kb32 + k % kb32
+
+
+def fil_dest_at(s, K, Cc, R, S, cb32, cb16, kb32, kb16, lp):
+    fi6 = s % kb32; s = s // kb32
+    fi5 = s % cb32; s = s // cb32
+    i4 = s % S; s = s // S
+    i3 = s % R; s = s // R
+    fi2 = s % (Cc // cb32); fi1 = s // (Cc // cb32)
+    k, c = fi1 * kb32 + fi6, fi2 * cb32 + fi5
+    cb = cb16 * lp
+    return (((((k // kb16 * (Cc // cb) + c // cb) * R + i3) * S + i4) * cb16 + (c % cb) // lp) * kb16 + k % kb16) * lp + c % lp
+
+
+def test_the_index_maps_of_this_file():
+    """single positions against the whole maps of tests/quant_common.py, both directions (no GPU involved)"""
+    for case in qc.ACT_CASES:
+        n = int(np.prod(case[:4]))
+        o = np.arange(n, dtype=np.int64)
+        assert np.array_equal(act_source_at(o, *case), qc.act_source(*case)) and np.array_equal(act_dest_at(act_source_at(o, *case), *case), o)
+    for case in qc.FIL_CASES:
+        n = int(np.prod(case[:4]))
+        o = np.arange(n, dtype=np.int64)
+        assert np.array_equal(fil_source_at(o, *case), qc.fil_source(*case)) and np.array_equal(fil_dest_at(fil_source_at(o, *case), *case), o)
+
+
+WIDE_ACT = (33, 64, 1024, 1024, 16, 4, 2)        # N, C, H, W, cb32, cb16, lp: 2^31 + 2^26 elements
+WIDE_FIL = (2048, 2048, 23, 23, 16, 4, 16, 16, 2)  # K, C, R, S, cb32, cb16, kb32, kb16, lp: 529 * 2^22 elements
+
+
+@pytest.mark.parametrize("layout", ["act", "fil"])
+def test_quant_layout_past_2_31_outputs(xs, torch_gpu, layout):
+    """quant_layout_kernel<MODE, unsigned long long>: the largest magnitude sits three elements before the end of the input; 4096
+    and some output positions on the host -- both ends, the neighbours of output 2^31 (byte 2^32 of the output), and the
+    outputs that read the neighbours of input 2^30 (byte 2^32) and 2^31. No output keeps the fill, none exceeds what the scale
+    allows: every position was written."""
+    torch = torch_gpu
+    case = WIDE_ACT if layout == "act" else WIDE_FIL
+    src_at, dest_at = (act_source_at, act_dest_at) if layout == "act" else (fil_source_at, fil_dest_at)
+    fn = xs.dnn_quantize_act if layout == "act" else xs.dnn_quantize_fil
+    total = int(np.prod([int(v) for v in case[:4]]))
+    assert total >= ll.threshold("quant_layout_wide") and total % 2 == 0
+    guard, fill = 64, 0x7b7b
+    need(torch, total * 6)
+    g = torch.Generator(device="cuda"); g.manual_seed(7)
+    x = torch.rand(total, device="cuda", generator=g)
+    x.sub_(0.5).mul_(0.9)
+    x[total - 3] = 1.75
+    x[5] = 0.0
+    dq = torch.full((total + 2 * guard,), fill, dtype=torch.int16, device="cuda")
+    assert dq.data_ptr() % 16 == 0
+    mode, shift = qc.NEAREST_ROUND, 2
+    scf = fn(x, dq[guard:guard + total], *case, shift, mode)
+    torch.cuda.synchronize()
+    assert xs.last_kernel() == "quant_" + layout
+    rng = np.random.default_rng(3)
+    near = np.array([-2, -1, 0, 1, 2], dtype=np.int64)
+    o = np.concatenate([[0, 1, total - 2, total - 1], W31 + near, dest_at(W31 + near, *case), dest_at((1 << 30) + near, *case),
+                        dest_at(np.array([total - 3, total - 1, 0, 5], dtype=np.int64), *case), rng.integers(0, total, 4096)]).astype(np.int64)
+    o = np.unique(o)
+    s = src_at(o, *case)
+    assert o.size >= 256 and s.min() == 0 and s.max() == total - 1 and (s > W31).any() and (o > W31).any()
+    xin = x[torch.from_numpy(s).cuda()].cpu().numpy()
+    gq, gscf = qc.quantize(np.concatenate([xin, [np.float32(1.75)]]), shift, mode)  # (the maximum is part of the sample anyway)
+    got = dq[guard:guard + total][torch.from_numpy(o).cuda()].cpu().numpy()
+    assert scf == gscf and np.array_equal(got, gq[:-1]), (scf, gscf, o[got != gq[:-1]][:8])
+    assert all_equal(torch, dq, fill, 0, guard) and all_equal(torch, dq, fill, guard + total, total + 2 * guard)
+    limit = int(np.abs(qc.quantize(np.array([1.75], dtype=np.float32), shift, mode)[0].astype(np.int64)).max()) + 1
+    assert limit < fill and none_is(torch, dq[guard:guard + total], lambda t: (t > limit) | (t < -limit))
+
+
+# ---- tiled GEMM: a leading dimension of 2^30 + 7 -----------------------------------------------------------------------------------
+WIDE_LD = (1 << 30) + 7
+CANARY = -7.25e11
+
+
+def strided_columns(t, ld, rows, cols):
+    return t.as_strided((cols, rows), (ld, 1))
+
+
+@pytest.mark.parametrize("wide", ["ldc", "ldb"])
+@pytest.mark.parametrize("kind", ["f32", "bf16"])
+def test_tgemm_leading_dimension_past_2_30(xs, orc, torch_gpu, kind, wide):
+    """m = T + 1, n = 3, k = 35, NN: column 2 of C (of B) starts at element 2^31 + 14. Every element of the product against the
+    reference on tight copies (the leading dimension only places the columns); all that lies between the columns keeps its bits"""
+    torch = torch_gpu
+    T = xs.lib().libxsmm_amd_gemm_tile()
+    m, n, k = T + 1, 3, 35
+    ldb, ldc = (WIDE_LD, m + 3) if wide == "ldb" else (k, WIDE_LD)
+    assert 2 * WIDE_LD > W31
+    rng = np.random.default_rng(5)
+    if kind == "f32":
+        a, b = rng.uniform(-1, 1, m * k).astype(np.float32), rng.uniform(-1, 1, k * n).astype(np.float32)
+    else:
+        a, b = lg.rand_bf16(rng, m * k), lg.rand_bf16(rng, k * n)
+    c = rng.uniform(-1, 1, m * n).astype(np.float32)
+    if kind == "f32":
+        gold = c.copy()
+        orc.smm(orc.FMA, 0, m, n, k, m, k, m, a, b, gold)
+    else:
+        gold = lg.reference(2, False, False, m, n, k, a, m, b, k, 1, c, m)
+    in_t = torch.float32 if kind == "f32" else torch.int16
+    nb, nc = (n - 1) * ldb + k, (n - 1) * ldc + m
+    need(torch, nb * (4 if kind == "f32" else 2) + nc * 4)
+    bfill = 0.0 if kind == "f32" else 0
+    db = torch.full((nb,), bfill, dtype=in_t, device="cuda")
+    dc = torch.full((nc,), CANARY, dtype=torch.float32, device="cuda")
+    da = torch.from_numpy(a if kind == "f32" else a.view(np.int16)).cuda()
+    strided_columns(db, ldb, k, n).copy_(torch.from_numpy((b if kind == "f32" else b.view(np.int16)).reshape(n, k)))
+    strided_columns(dc, ldc, m, n).copy_(torch.from_numpy(c.reshape(n, m)))
+    if kind == "f32":
+        keep, h = xs.gemm_handle(xs.F32, xs.F32, "N", "N", m, n, k, m, ldb, ldc, 1.0, 1.0)
+        assert h
+        xs.gemm_thread(h, da, db, dc)
+    else:
+        assert 0 == xs.gemm_lowp(xs.BF16, xs.F32, "N", "N", m, n, k, da, m, db, ldb, 1, dc, ldc)
+    torch.cuda.synchronize()
+    assert xs.last_kernel() == ("tgemm_f32_nn" if kind == "f32" else lg.NAMES[2] + "nn")
+    got = strided_columns(dc, ldc, m, n).cpu().numpy().reshape(-1)
+    assert lg.same_bits(got, gold), int(np.argmax(lg.bits(got) != lg.bits(gold)))
+    for j in range(n - 1):  # between the columns
+        assert all_equal(torch, dc, CANARY, j * ldc + m, (j + 1) * ldc), j
+        assert all_equal(torch, db, bfill, j * ldb + k, (j + 1) * ldb), j
+    hb = strided_columns(db, ldb, k, n).cpu().numpy().reshape(-1)
+    assert np.array_equal(hb if kind == "f32" else hb.view(np.uint16), b)
+
+
+# ---- strided dense batch: the items of C 2^20 elements apart ----------------------------------------------------------------------
+@pytest.mark.parametrize("config", [("f32", 32, 1), ("f32", 32, 0), ("f64", 23, 0)])
+def test_strided_batch_with_c_items_2_20_apart(xs, orc, torch_gpu, config):
+    """2049 items, A and B tight: the last C starts at element 2^31. All items against the oracle (fp32 32^3 on the matrix cores within
+    the bound tests/test_edge_gpu.py uses for them, the scalar kernels bit for bit); the gaps between the items keep their bits"""
+    torch, L = torch_gpu, xs.lib()
+    name, m, mfma = config
+    dtype, tt, prec = (np.float32, torch.float32, xs.F32) if name == "f32" else (np.float64, torch.float64, xs.F64)
+    stride, batch, sz = 1 << 20, 2049, m * m
+    assert (batch - 1) * stride >= W31
+    need(torch, ((batch - 1) * stride + sz) * np.dtype(dtype).itemsize)
+    rng = np.random.default_rng(m)
+    a, b, c = (rng.uniform(-1, 1, batch * sz).astype(dtype) for _ in range(3))
+    ref = c.copy()
+    orc.gemm_batch_strided(orc.FMA, 0, m, m, m, m, m, m, a, b, ref, sz, sz, sz, batch, 4)
+    da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    dc = torch.full(((batch - 1) * stride + sz,), CANARY, dtype=tt, device="cuda")
+    items = dc.as_strided((batch, sz), (stride, 1))
+    items.copy_(torch.from_numpy(c.reshape(batch, sz)))
+    blob, desc = xs.descriptor(prec, m, m, m, m, m, m, 1.0, 1.0)
+    assert desc
+    old = L.libxsmm_amd_set_mfma(mfma)
+    try:
+        assert 0 == L.libxsmm_amd_gemm_batch_strided(desc, xs.dptr(da), xs.dptr(db), xs.dptr(dc), sz, sz, stride, batch)
+        torch.cuda.synchronize()
+    finally:
+        L.libxsmm_amd_set_mfma(old)
+    kernel = xs.last_kernel()
+    assert kernel == {("f32", 1): "smm_f32_32x32x32_mfma", ("f32", 0): "smm_f32_32x32x32_fma", ("f64", 0): "smm_f64_jit_shape"}[(name, mfma)], kernel
+    got = items.cpu().numpy().reshape(-1)
+    if mfma:
+        assert np.max(np.abs(got - ref)) <= 1e-6 * np.max(np.abs(ref))
+    else:
+        bad = np.flatnonzero(got != ref)
+        assert bad.size == 0, (bad.size, int(bad[0]) // sz)
+    gaps = dc[:(batch - 1) * stride].view(batch - 1, stride)[:, sz:]
+    for i in range(0, batch - 1, 256):
+        assert bool((gaps[i:i + 256] == CANARY).all()), i
+
+
+# ---- fsspmdm at the leading dimension of BASELINE config 3 ------------------------------------------------------------------------
+def test_fsspmdm_at_the_leading_dimension_of_config_3(xs, orc, torch_gpu):
+    """ldb = ldc = 25 165 824 (262 144 panels of 96 columns), fp32, the PyFR operator p4_pri_m3 (75 x 105: the largest of
+    tests/golden/mtx/pyfr whose B and C fit 20 GiB together). 64 panels each at the start, in the middle and at the end of the
+    row; rows 86 and up of B start past element 2^31, rows 43 and up of C past byte 2^32. The rest of C is canary."""
+    torch, L = torch_gpu, xs.lib()
+    ld, N, npan = 25165824, 96, 64
+    path = os.path.join(GOLDEN, "mtx", "pyfr", "p4_pri_m3-sp.mtx")
+    assert path in glob.glob(os.path.join(GOLDEN, "mtx", "pyfr", "*-sp.mtx"))
+    rowptr, colidx, vals, M, K, nnz = orc.read_csr(path)
+    A = np.zeros((M, K), dtype=np.float32)
+    A[np.repeat(np.arange(M), np.diff(rowptr)), colidx] = vals.astype(np.float32)
+    assert (K - 1) * ld > W31 and (M - 1) * ld * 4 > (1 << 32)
+    need(torch, (M + K) * ld * 4)
+    width = npan * N
+    starts = [0, (ld // N // 2) * N, ld - width]
+    rng = np.random.default_rng(9)
+    dB = torch.zeros((K, ld), dtype=torch.float32, device="cuda")
+    dC = torch.full((M, ld), CANARY, dtype=torch.float32, device="cuda")
+    hd = L.libxsmm_sfsspmdm_create(M, N, K, K, ld, ld, 1.0, 1.0, xs.dptr(A))
+    assert hd
+    want = []
+    for s in starts:
+        B, Cin = rng.uniform(-1, 1, (K, width)).astype(np.float32), rng.uniform(-1, 1, (M, width)).astype(np.float32)
+        dB[:, s:s + width].copy_(torch.from_numpy(B))
+        dC[:, s:s + width].copy_(torch.from_numpy(Cin))
+        ref = Cin.copy()
+        h = orc.Fsspmdm(A, M, width, K, K, width, width, 1.0, 1.0, have_avx512=False)
+        h.execute(B, ref); h.close()
+        want.append(ref)
+    for s in starts:
+        assert 0 == L.libxsmm_amd_sfsspmdm_execute_batch(hd, C.c_void_p(dB.data_ptr() + 4 * s), C.c_void_p(dC.data_ptr() + 4 * s), npan)
+    torch.cuda.synchronize()
+    assert xs.last_kernel().startswith("fsspmdm_")
+    L.libxsmm_sfsspmdm_destroy(hd)
+    for s, ref in zip(starts, want):
+        got = dC[:, s:s + width].cpu().numpy()
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), s
+    for lo, hi in ((starts[0] + width, starts[1]), (starts[1] + width, starts[2])):
+        for r in range(M):
+            assert bool((dC[r, lo:hi] == CANARY).all()), (r, lo)
+
+
+# ---- pooling over more than 2^31 elements ------------------------------------------------------------------------------------------
+POOL_WIDE = dict(H=64, W=64, R=2, S=2, u=2, v=2, N=33, C=16 * 1000)  # 33000 items of 64 x 64 x 16: items 32768 and up start past 2^31
+BAND = 256
+
+
+def banded(torch, n, dtype, fill):
+    t = torch.full((n + 2 * BAND,), -77, dtype=dtype, device="cuda")
+    t[BAND:BAND + n] = fill
+    return t, t[BAND:BAND + n]
+
+
+def bands_intact(t):
+    return bool((t[:BAND] == -77).all()) and bool((t[-BAND:] == -77).all())
+
+
+def pool_sample(items):
+    rng = np.random.default_rng(1)
+    return np.unique(np.concatenate([[0, 1, 32767, 32768, 32769, items - 1], rng.integers(0, items, 18)]))
+
+
+@pytest.mark.parametrize("kind", ["fwd", "bwd"])
+def test_pool_past_2_31_elements(xs, torch_gpu, kind):
+    """max pooling, fp32: 24 items against tests/pool_common.py (a layer of those items alone: items do not meet), among them the
+    first, the last and the two on either side of element 2^31; destinations pre-filled with NaN and -1 hold neither afterwards"""
+    torch, L = torch_gpu, xs.lib()
+    d = pc.desc(**POOL_WIDE)
+    h = pc.Handle(d)
+    items, plane_in, plane_out = h.work(), 64 * 64 * 16, 32 * 32 * 16
+    assert items * plane_in >= W31 and h.in_shape() == (items, 64, 64, 16) and h.out_shape() == (items, 32, 32, 16)
+    need(torch, items * (plane_in + 2 * plane_out) * 4)
+    handle, st = xs.pool_create(*[d[k] for k in pc.DESC_FIELDS])
+    assert handle and 0 == st
+    sel = pool_sample(items)
+    dsel = torch.from_numpy(sel).cuda()
+    small = pc.Handle(pc.desc(**dict(POOL_WIDE, N=1, C=16 * sel.size)))
+    g = torch.Generator(device="cuda"); g.manual_seed(3)
+    if kind == "fwd":
+        bx, x = banded(torch, items * plane_in, torch.float32, 0.0)
+        x.normal_(generator=g)
+        bo, out = banded(torch, items * plane_out, torch.float32, float("nan"))
+        bm, mask = banded(torch, items * plane_out, torch.int32, pc.SENTINEL)
+        bound = [xs.pool_bind_new(handle, t, v) for t, v in ((pc.REG_IN, x), (pc.REG_OUT, out), (pc.MASK, mask))]
+        assert 0 == xs.pool_execute(handle, pc.FWD)
+        torch.cuda.synchronize()
+        assert xs.last_kernel() == "pool_fwd_max_f32"
+        hx = x.view(items, 64, 64, 16)[dsel].cpu().numpy()
+        wout = np.full(small.out_shape(), np.nan, dtype=np.float32)
+        wmask = np.full(small.mask_shape(), pc.SENTINEL, dtype=np.int32)
+        pc.forward(small, hx, wout, wmask)
+        assert out.view(items, -1)[dsel].cpu().numpy().tobytes() == wout.tobytes()
+        assert mask.view(items, -1)[dsel].cpu().numpy().tobytes() == wmask.tobytes()
+        assert none_is(torch, out, torch.isnan) and none_is(torch, mask, lambda t: t < 0)
+        assert bands_intact(bx) and bands_intact(bo) and bands_intact(bm)
+    else:
+        bi, din = banded(torch, items * plane_in, torch.float32, float("nan"))
+        bo, dout = banded(torch, items * plane_out, torch.float32, 0.0)
+        dout.normal_(generator=g)
+        bm, mask = banded(torch, items * plane_out, torch.int32, 0)
+        # a mask FWD could have written: per output and lane one of the four elements of its window
+        ho = torch.arange(32, device="cuda", dtype=torch.int32).view(1, 32, 1, 1)
+        wo = torch.arange(32, device="cuda", dtype=torch.int32).view(1, 1, 32, 1)
+        lane = torch.arange(16, device="cuda", dtype=torch.int32).view(1, 1, 1, 16)
+        for i0 in range(0, items, 3000):  # (in parts: the temporaries stay small)
+            part = mask.view(items, 32, 32, 16)[i0:i0 + 3000]
+            pick = torch.randint(0, 4, part.shape, device="cuda", generator=g, dtype=torch.int32)
+            part.copy_(((2 * ho + pick // 2) * 64 + 2 * wo + pick % 2) * 16 + lane)
+        del pick, part
+        bound = [xs.pool_bind_new(handle, t, v) for t, v in ((pc.GRAD_IN, din), (pc.GRAD_OUT, dout), (pc.MASK, mask))]
+        assert 0 == xs.pool_execute(handle, pc.BWD)
+        torch.cuda.synchronize()
+        assert xs.last_kernel() == "pool_bwd_max_f32"
+        hd = dout.view(items, 32, 32, 16)[dsel].cpu().numpy()
+        hm = mask.view(items, 32, 32, 16)[dsel].cpu().numpy()
+        wdin = np.full(small.in_shape(), np.nan, dtype=np.float32)
+        pc.backward(small, hd, hm, wdin)
+        assert din.view(items, -1)[dsel].cpu().numpy().tobytes() == wdin.tobytes()
+        assert none_is(torch, din, torch.isnan)
+        assert bands_intact(bi) and bands_intact(bo) and bands_intact(bm)
+    for t in bound:
+        L.libxsmm_dnn_destroy_tensor(t)
+    assert 0 == L.libxsmm_dnn_destroy_pooling(handle)
