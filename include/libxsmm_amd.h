@@ -305,9 +305,19 @@ LIBXSMM_API int libxsmm_amd_gemm_tile(void);
  *  layout is always plain column-major: op(A) is m x k, op(B) is k x n (transa / transb 'N' or 'T'), whatever the size --
  *  unlike the front ends, which below LIBXSMM_MAX_MNK read A in pairs of k. Per element of C, from C (beta 1) or from 0:
  *  I16 -> I32 the wrapping 32-bit sum of the 32-bit products; I16 -> F32 acc = acc + (float)(a * b), k ascending, every add
- *  rounded; BF16 -> F32 acc = acc + a * b, k ascending, the product (exact in fp32 unless it underflows) and the add rounded
- *  separately -- the bits of the kernels of libxsmm_wimmdispatch / wsmmdispatch (scaling factor 1) / bsmmdispatch, -0.0
- *  included. beta = 0 never reads C; what lies between m and ldc keeps its bytes. Operands in memory the GPU reaches are
+ *  rounded; BF16 -> F32 acc = acc + a * b, k ascending, the product and the add rounded separately -- the bits of the kernels
+ *  of libxsmm_wimmdispatch / wsmmdispatch (scaling factor 1) / bsmmdispatch, -0.0 included. ONE DIVERGENCE: the BF16 kernel
+ *  runs on the fp32 matrix instruction, which is acc = fma(a, b, acc): one rounding per step. The product of two bf16 numbers
+ *  is exact in fp32 -- and the two chains are the same -- unless it is subnormal (below 2^-126) or beyond FLT_MAX; an element
+ *  of C whose chain meets such a product has the bits of the fma chain, not of the separately rounded one (a subnormal
+ *  product is not rounded before it is added; a product beyond FLT_MAX is not Inf before it is added, so Inf - Inf = NaN of
+ *  the gold loop can come out as +-Inf or a finite number). The batch calls over a bf16 descriptor (bsmmdispatch /
+ *  bmmdispatch kinds) do the same on their matrix-core form only (one wave per item, smm_bf16f32/bf16_mfma_wave_jit_lowp),
+ *  which serves a batch when all of this holds: matrix cores on (libxsmm_amd_set_mfma), M > 31 or N > 31, K % 8 == 0 (bf16
+ *  output: M % 8 == 0 as well), tight leading dimensions, at least LIBXSMM_AMD_JIT_MINBATCH items and, in a strided batch,
+ *  operands and byte strides that are multiples of 16. Otherwise the same descriptor is served by a kernel that rounds
+ *  product and sum separately: the bits of such elements change with these conditions.
+ *  beta = 0 never reads C; what lies between m and ldc keeps its bytes. Operands in memory the GPU reaches are
  *  processed in place, asynchronously on the calling thread's stream; host-visible memory is complete on return; pageable
  *  memory is staged. Inside libxsmm_amd_defer_begin/end the call is not recorded: it seals the open burst and runs in call
  *  order. A wrong type pair, transa / transb other than N, n, T, t, a negative extent, a leading dimension below the

@@ -4,8 +4,10 @@
 //   LOWP_I16_I32   wrapping 32-bit sum of the 32-bit products                                        (vector ALU)
 //   LOWP_I16_F32   acc = fadd(acc, (float)(a * b as int32)), k ascending                             (vector ALU)
 //   LOWP_BF16      acc = fma(a, b, acc) over the widened operands, k ascending: v_mfma_f32_32x32x2_f32, which computes that
-//                  chain per element (tests/test_mfma_runs_gpu.py). A bf16 x bf16 product is exact in fp32 unless it
-//                  underflows, so this is the chain acc = fadd(acc, fmul(a, b)) of the bf16 SMM kernels (smm_lowp.hip).
+//                  chain per element (tests/test_mfma_runs_gpu.py). A bf16 x bf16 product is exact in fp32 unless it is
+//                  subnormal or beyond FLT_MAX, so this is the chain acc = fadd(acc, fmul(a, b)) of the bf16 SMM kernels
+//                  (smm_lowp.hip) everywhere else; where a chain meets such a product it keeps the fma's bits (pinned by
+//                  tests/test_hostile_operands_gpu.py::test_values_tgemm_bf16).
 //   LOWP_BF16_FAST v_mfma_f32_32x32x16_bf16: 16 products per step, summed in the order the instruction takes. Opt-in.
 //
 // The block, the k loop and the arithmetic of LOWP_BF16 are those of tile_gemm.cuh: 256 threads own a 128 x 128 tile of C,

@@ -755,8 +755,15 @@ void call_kernel(Kernel* k, const void* a, const void* b, void* c, const void* x
     SmmBatch s = from_descriptor(k->desc);
     s.jit_always = 1; // a batch-reduce kernel is dispatched once and called over and over with short batches
     void* cc = c;
-    // one run: every product lands in the same C (stride_c == NULL), accumulated in batch order
-    (void)batch_execute(s, 0, 0, &ptrsize, &ptrsize, nullptr, a, b, &cc, 0, (long long)count, false);
+    // one run: every product lands in the same C (stride_c == NULL), accumulated in batch order. beta = 0: only the first
+    // product overwrites C and the chain goes on from there (the reference's kernel zeroes its accumulators once) -- a batch of
+    // beta = 0 products is a batch of independent overwrites, so the first product goes ahead on its own
+    long long first = 0;
+    if (0 != (s.flags & LIBXSMM_GEMM_FLAG_BETA_0)) {
+      if (EXIT_SUCCESS != batch_execute(s, 0, 0, &ptrsize, &ptrsize, nullptr, a, b, &cc, 0, 1, false)) return;
+      s.flags &= ~LIBXSMM_GEMM_FLAG_BETA_0; s.beta = 1.0; first = 1;
+    }
+    (void)batch_execute(s, 0, 0, &ptrsize, &ptrsize, nullptr, a, b, &cc, first, (long long)count, false);
   }
   else if (KC_TEXT == k->kclass) { // kernel(a, b, c) of the SOA family: one product (batch form: libxsmm_amd_kernel_execute_batch)
     (void)text_kernel_execute(k->text, a, b, c, 0, 0, 1);

@@ -273,6 +273,19 @@ __device__ __forceinline__ void store_c_pairs(T* Cs, unsigned* pc, int lane, int
 }
 #endif
 #endif
+#if (2 == XLOWP || 3 == XLOWP)
+// bf16 inputs: product and sum are rounded one after the other, as in the gold loop and in the pre-compiled kernel (smm_lowp.hip).
+// The product of two bf16 numbers is exact in float32 unless it is subnormal or beyond FLT_MAX; there an fma has other bits, and a
+// descriptor must not change its result with the size of the batch. (The pragma: the compiler's default contracts a * b + c.)
+__device__ __forceinline__ float xstep(float a, float b, float c)
+{
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return c + p;
+}
+#else
+template<typename X> __device__ __forceinline__ X xstep(X a, X b, X c) { return xfma(a, b, c); }
+#endif
 // acc(i,j) = fma(A(m,k), B(k,n), acc(i,j)) for k ascending: the reference's per-element chain
 __device__ __forceinline__ void multiply(const T* As, const T* Bs, int tx, int ncol0, T (&acc)[TM][TN])
 {
@@ -286,7 +299,7 @@ __device__ __forceinline__ void multiply(const T* As, const T* Bs, int tx, int n
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = xfma(av[i], bv[j], acc[i][j]);
+      for (int j = 0; j < TN; ++j) acc[i][j] = xstep(av[i], bv[j], acc[i][j]);
     }
   }
 }
@@ -813,7 +826,8 @@ constexpr int A_ELEMS = (C_ELEMS > KP4 * MS) ? C_ELEMS : KP4 * MS, B_ELEMS = XTR
 // bf16 inputs (XLOWP 3: fp32 result, 2: bf16 result) as the reference's low-precision kernels store them: A in pairs of k
 // (a[(k/2)*M*2 + m*2 + k%2]), B column-major -- both sequences of 32-bit k pairs. A 16-byte chunk is four pairs (A: four
 // rows m of one pair of k; B: eight consecutive k of one column); the halves are widened on the way into the same fp32 LDS
-// images (a bf16 product is exact in fp32, so fma(a, b, acc) is the gold loop's product-then-add, samples/xgemm/kernel.c).
+// images (a bf16 product is exact in fp32 unless it is subnormal or beyond FLT_MAX, so fma(a, b, acc) is the gold loop's
+// product-then-add, samples/xgemm/kernel.c, everywhere else; the exception is pinned and documented, DESIGN.md 8j).
 typedef unsigned UV __attribute__((ext_vector_type(4)));
 constexpr int LDA = M, LDB = K, LDC = M;
 constexpr bool TIGHT = true;

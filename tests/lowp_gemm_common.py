@@ -76,6 +76,34 @@ def reference(kind, ta, tb, m, n, k, a, lda, b, ldb, beta, c, ldc):
     return out
 
 
+def pairs_gold(kind, beta0, m, n, k, lda, ldb, ldc, a, b, c, scf):
+    """the gold loops of the dispatched kernels (A in pairs of k; tests/test_lowp.py pins the oracle with them), vectorised over the C tile: one term after the other in ascending k, every step rounded to
+    float32 (numpy float32 arithmetic rounds each operation)."""
+    out = c.copy()
+    A = a.reshape(k // 2, lda, 2)   # a[(s*lda + i)*2 + k2]
+    B = b.reshape(n, ldb)           # b[j*ldb + kk]
+    C2 = out.reshape(n, ldc)
+    if kind == 0:
+        acc = np.zeros((n, m), dtype=np.int64) if beta0 else C2[:, :m].astype(np.int64)
+        for kk in range(k):
+            acc += np.outer(B[:, kk].view(np.int16).astype(np.int64), A[kk // 2, :m, kk % 2].view(np.int16).astype(np.int64))
+        C2[:, :m] = (acc & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        return out
+    if kind == 3:
+        acc = np.zeros((n, m), dtype=np.float32) if beta0 else widen(C2[:, :m])
+    else:
+        acc = np.zeros((n, m), dtype=np.float32) if beta0 else C2[:, :m].astype(np.float32)
+    for kk in range(k):
+        if kind == 1:
+            iprod = np.outer(B[:, kk].view(np.int16).astype(np.int32), A[kk // 2, :m, kk % 2].view(np.int16).astype(np.int32))
+            term = (iprod.astype(np.float32) * np.float32(scf)).astype(np.float32)
+        else:
+            term = np.outer(widen(B[:, kk]), widen(A[kk // 2, :m, kk % 2])).astype(np.float32)
+        acc = (acc + term).astype(np.float32)
+    C2[:, :m] = (np.ascontiguousarray(acc, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16) if kind == 3 else acc
+    return out
+
+
 def pack_pairs(a, lda, m, k):
     """plain column-major A (m x k, lda) -> the reading of the dispatched kernels: a[(kk/2)*lda*2 + i*2 + kk%2]"""
     assert k % 2 == 0

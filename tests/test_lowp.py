@@ -16,6 +16,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from lowp_gemm_common import pairs_gold as _numpy_gold
+
 
 def _bf16(x):
     """float32 array -> its bf16 truncation as uint16 (what the harness stores: the upper half of the float)"""
@@ -40,34 +42,6 @@ def _inputs(kind, m, n, k, lda, ldb, ldc, seed):
     else:
         c = rng.uniform(-1, 1, ldc * n).astype(np.float32)
     return a, b, c
-
-
-def _numpy_gold(kind, beta0, m, n, k, lda, ldb, ldc, a, b, c, scf):
-    """kernel.c's gold loops, vectorised over the C tile: one term after the other in ascending k, every step rounded to
-    float32 (numpy float32 arithmetic rounds each operation)."""
-    out = c.copy()
-    A = a.reshape(k // 2, lda, 2)   # a[(s*lda + i)*2 + k2]
-    B = b.reshape(n, ldb)           # b[j*ldb + kk]
-    C2 = out.reshape(n, ldc)
-    if kind == 0:
-        acc = np.zeros((n, m), dtype=np.int64) if beta0 else C2[:, :m].astype(np.int64)
-        for kk in range(k):
-            acc += np.outer(B[:, kk].view(np.int16).astype(np.int64), A[kk // 2, :m, kk % 2].view(np.int16).astype(np.int64))
-        C2[:, :m] = (acc & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
-        return out
-    if kind == 3:
-        acc = np.zeros((n, m), dtype=np.float32) if beta0 else _f32(C2[:, :m])
-    else:
-        acc = np.zeros((n, m), dtype=np.float32) if beta0 else C2[:, :m].astype(np.float32)
-    for kk in range(k):
-        if kind == 1:
-            iprod = np.outer(B[:, kk].view(np.int16).astype(np.int32), A[kk // 2, :m, kk % 2].view(np.int16).astype(np.int32))
-            term = (iprod.astype(np.float32) * np.float32(scf)).astype(np.float32)
-        else:
-            term = np.outer(_f32(B[:, kk]), _f32(A[kk // 2, :m, kk % 2])).astype(np.float32)
-        acc = (acc + term).astype(np.float32)
-    C2[:, :m] = _bf16(acc) if kind == 3 else acc
-    return out
 
 
 CASES = [(16, 9, 8, 16, 8, 16), (32, 32, 32, 32, 32, 32), (16, 5, 6, 20, 10, 24), (48, 7, 64, 48, 64, 48)]
