@@ -79,6 +79,18 @@ LIBXSMM_API int libxsmm_amd_merge_segments(int n, const unsigned long long hulls
  *  the first `capacity` calls -- the hulls (6 per call) and segments as for libxsmm_amd_merge_segments. Any pointer may be
  *  NULL. Returns the number of calls written. */
 LIBXSMM_API int libxsmm_amd_merge_last_plan(int* ncalls, int* nsegments, int* ndevice_hulls, unsigned long long hulls[], int segment_of[], int capacity);
+/** DIAGNOSTIC, not a stable part of the interface (the tests use it to hold the launch plans against a table of cases). The plan of a
+ *  dense batch as text: the ordered alternatives of both tiers that a batch call tries before the pre-compiled kernels serve. No device
+ *  is needed and nothing is compiled or launched. mode: 0 strided, 1 index arrays, 2 pointer arrays; sync: 0 every item its own C,
+ *  1 C in runs known to the host, 3 the verdict on the device; the strides are those of a strided batch (elements); address_bits: the
+ *  low bits of the operands' addresses (0: aligned to 16 bytes); mfma: matrix cores on or off; lowp: 0, or 1 i16 -> i32, 3 bf16 -> f32,
+ *  4 bf16 -> bf16 (the descriptor then gives the shape and leading dimensions only). One line per alternative:
+ *    <position> <mfma|jit> <name> parts=<n> [<variant bits>:<all|packed|rest> ...] tiles=<n> [<m>x<n>:<variant bits> ...]
+ *  compile_tiles != 0: the grouped kernel text of an alternative that runs the tiles of C is compiled for gfx950 as well.
+ *  Returns the length of the text (an empty plan: 0), -1 for arguments out of range, -2 if such a text did not compile. */
+LIBXSMM_API int libxsmm_amd_smm_plan_describe(const libxsmm_gemm_descriptor* descriptor, int mode, int sync, long long batch,
+  long long stride_a, long long stride_b, long long stride_c, unsigned int address_bits, int relaxed, long long uniform_run, int mfma, int lowp,
+  char* buffer, size_t buffer_size, int compile_tiles);
 /** Block until all work enqueued by this library on its stream has completed. Returns EXIT_SUCCESS/FAILURE. */
 LIBXSMM_API int libxsmm_amd_synchronize(void);
 /** Device memory (hipMalloc/hipFree) -- what libxsmm_malloc returns when a device is present is host-pinned
@@ -102,6 +114,10 @@ LIBXSMM_API int libxsmm_amd_get_mfma(void);
 LIBXSMM_API const char* libxsmm_amd_last_kernel(void);
 /** Number of device kernel launches issued by this process (monotonic). */
 LIBXSMM_API unsigned long long libxsmm_amd_launch_count(void);
+/** DIAGNOSTIC, not a stable part of the interface: the number of launches of run-time specialised dense kernels by this process
+ *  (monotonic). An alternative of a launch plan that has two parts makes two, the pre-compiled kernels make none; the tests tell
+ *  alternatives of one name apart by it. */
+LIBXSMM_API unsigned long long libxsmm_amd_jit_launch_count(void);
 
 /** Measurement aid: c[i] += a[i] + b[i] over `bytes` bytes per operand (device memory, 16-byte aligned) -- the
  *  3-read/1-write traffic mix of a beta=1 SMM batch with no arithmetic; bench.py reports its rate as the measured

@@ -259,6 +259,7 @@ def _declare(L):
     sig("libxsmm_amd_get_mfma", i)
     sig("libxsmm_amd_last_kernel", C.c_char_p)
     sig("libxsmm_amd_launch_count", C.c_ulonglong)
+    sig("libxsmm_amd_jit_launch_count", C.c_ulonglong)
     sig("libxsmm_amd_flush", None)
     sig("libxsmm_amd_defer_begin", None)
     sig("libxsmm_amd_defer_end", None)
@@ -266,6 +267,7 @@ def _declare(L):
     ull_p = C.POINTER(C.c_ulonglong)
     sig("libxsmm_amd_merge_segments", i, i, ull_p, c_int_p)
     sig("libxsmm_amd_merge_last_plan", i, c_int_p, c_int_p, c_int_p, ull_p, c_int_p, i)
+    sig("libxsmm_amd_smm_plan_describe", i, vp, i, i, ll, ll, ll, ll, C.c_uint, i, ll, i, i, vp, C.c_size_t, i)
     sig("libxsmm_amd_is_device_pointer", i, vp)
     sig("libxsmm_amd_gemm_batch_strided", i, vp, vp, vp, vp, ll, ll, ll, ll)
     sig("libxsmm_amd_stream_probe", i, vp, vp, vp, ll)
@@ -514,6 +516,29 @@ def merge_last_plan(capacity=64):
     m = lib().libxsmm_amd_merge_last_plan(C.byref(nc), C.byref(ns), C.byref(nd), flat, seg, capacity)
     return dict(calls=nc.value, segments=ns.value, device_hulls=nd.value, hulls=[tuple(flat[6 * j + o] for o in range(6)) for j in range(m)],
                 segment_of=[seg[j] for j in range(m)])
+
+
+ADDR_STRIDED, ADDR_INDEX, ADDR_POINTER = 0, 1, 2  # how a batch addresses its items
+SYNC_NONE, SYNC_RUNS, SYNC_DEVICE = 0, 1, 3       # every item its own C; C in runs the host knows of; the verdict on the device
+
+
+def smm_plan(desc, mode, sync, batch, strides=(0, 0, 0), address_bits=0, relaxed=False, uniform_run=0, mfma=1, lowp=0, compile_tiles=False):
+    """libxsmm_amd_smm_plan_describe -> [dict(pos, tier, name, parts=[(variant bits, slice)], tiles=[(m, n, variant bits)])], one per
+    alternative in the order a batch call tries them (diagnostic: no device needed)"""
+    buf = C.create_string_buffer(1 << 12)
+    rc = lib().libxsmm_amd_smm_plan_describe(desc, mode, sync, batch, strides[0], strides[1], strides[2], address_bits, 1 if relaxed else 0,
+                                             uniform_run, mfma, lowp, buf, len(buf), 1 if compile_tiles else 0)
+    if rc < 0:
+        raise RuntimeError("libxsmm_amd_smm_plan_describe: %d" % rc)
+    plan = []
+    for line in buf.value.decode().splitlines():
+        w = line.split()
+        nparts = int(w[3].split("=")[1])
+        parts = [(int(x.split(":")[0]), x.split(":")[1]) for x in w[4:4 + nparts]]
+        ntiles = int(w[4 + nparts].split("=")[1])
+        tiles = [(int(x.split(":")[0].split("x")[0]), int(x.split(":")[0].split("x")[1]), int(x.split(":")[1])) for x in w[5 + nparts:5 + nparts + ntiles]]
+        plan.append(dict(pos=int(w[0]), tier=w[1], name=w[2], parts=parts, tiles=tiles))
+    return plan
 
 
 # ---- packed kernels (libxsmm_dispatch_pgemm / getrf / trmm / trsm) ------------------------------------------------------

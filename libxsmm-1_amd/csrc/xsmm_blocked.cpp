@@ -183,7 +183,7 @@ void bgemm_run(const libxsmm_blocked_gemm_handle* h, const void* a, const void* 
   s.use_mfma = libxsmm_amd_get_mfma(); s.alpha = 1; s.beta = 1;
   s.uniform_run = h->kb; // every C block's k blocks follow each other in the work list
   const char* name = "";
-  int e = launch_smm_special(s, device().stream, &name);
+  int e = (0 == (smm_skip_mask() & SMM_SKIP_SPECIAL)) ? launch_smm_special(s, device().stream, &name) : -1;
   if (e < 0) {
     // The work list is a sequence of runs (all k blocks of a C block follow each other). The reference sums a run into a
     // thread-local block and adds that to C under a lock (tpl :95-103): the order of the partial sums is open, so the

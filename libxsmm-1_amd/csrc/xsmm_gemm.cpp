@@ -31,7 +31,7 @@ int run_smm(const SmmBatch& s, int host_visible = -1)
   const char* name = "";
   int e = -1;
   e = launch_smm_jit_mfma(s, device().stream, &name);                               // matrix-core kernels of this very descriptor
-  if (e < 0 && 0 == s.general) e = launch_smm_special(s, device().stream, &name);  // hand-tuned shapes; the same kernels for any descriptor
+  if (e < 0 && 0 == s.general && 0 == (smm_skip_mask() & SMM_SKIP_SPECIAL)) e = launch_smm_special(s, device().stream, &name);  // hand-tuned shapes; the same kernels for any descriptor
   if (e < 0) e = launch_smm_jit(s, device().stream, &name);                         // shape-specialised via hiprtc (SYNC_DEVICE: whatever the verdict on the device, one of its kernels works)
   if (e < 0) e = launch_smm_generic(s, device().stream, &name);                     // any descriptor
   if (SYNC_DEVICE == s.sync) flag_slot_commit(); // the launches that read the verdict are queued
@@ -1181,6 +1181,26 @@ LIBXSMM_API int libxsmm_amd_merge_last_plan(int* ncalls, int* nsegments, int* nd
     if (nullptr != hulls) memcpy(hulls + 6 * (size_t)i, r.plan_hulls.data() + 6 * (size_t)i, 6 * sizeof(unsigned long long));
   }
   return 0 < m ? m : 0;
+}
+
+LIBXSMM_API int libxsmm_amd_smm_plan_describe(const libxsmm_gemm_descriptor* descriptor, int mode, int sync, long long batch,
+  long long stride_a, long long stride_b, long long stride_c, unsigned int address_bits, int relaxed, long long uniform_run, int mfma, int lowp,
+  char* buffer, size_t buffer_size, int compile_tiles)
+{ // see include/libxsmm_amd.h
+  if (nullptr == descriptor || mode < ADDR_STRIDED || mode > ADDR_POINTER || sync < SYNC_NONE || sync > SYNC_DEVICE || batch < 0) return -1;
+  if (0 != lowp && 1 != lowp && 3 != lowp && 4 != lowp) return -1;
+  SmmBatch s = from_descriptor(*descriptor);
+  if (0 != lowp) { s.typesize = 2; s.lowp = lowp; s.flags &= LIBXSMM_GEMM_FLAG_BETA_0; } // (as lowp_from_descriptor)
+  s.mode = mode; s.sync = sync; s.batch = batch; s.sa = stride_a; s.sb = stride_b; s.sc = stride_c;
+  s.a = s.b = s.c = reinterpret_cast<void*>(static_cast<uintptr_t>(address_bits)); // (never followed: the planner looks at the low bits only)
+  s.index_stride = (int)sizeof(int); s.relaxed = relaxed; s.uniform_run = uniform_run; s.use_mfma = mfma; s.c_atomics = 1;
+  int failed = 0;
+  const std::string text = smm_plan_describe(s, 0 != compile_tiles, &failed);
+  if (nullptr != buffer && 0 < buffer_size) {
+    const size_t n = (text.size() < buffer_size - 1 ? text.size() : buffer_size - 1);
+    memcpy(buffer, text.data(), n); buffer[n] = 0;
+  }
+  return 0 != failed ? -2 : (int)text.size();
 }
 
 // ---- BLAS-like single GEMM (reference LIBXSMM_XGEMM, include/libxsmm_frontend.h:371-411) ---------------------------

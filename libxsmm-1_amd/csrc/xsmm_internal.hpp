@@ -150,6 +150,9 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
 bool smm_jit_eligible(const SmmBatch& s);
 int launch_smm_jit_mfma(const SmmBatch& s, void* stream, const char** name); // matrix-core kernels specialised per descriptor (before the hand-written ones); -1: none ready
 int launch_smm_jit(const SmmBatch& s, void* stream, const char** name); // the other specialised kernels, 16-bit inputs included; -1: none ready
+int smm_skip_mask(); // XSMM_SMMJIT_SKIP: links of the launch chains treated as not ready (bits 0-7: alternatives of a plan by position, bit 8: launch_smm_special)
+constexpr int SMM_SKIP_SPECIAL = 256;
+std::string smm_plan_describe(const SmmBatch& s, bool check_tiles, int* failed); // the plan of a batch as text (diagnostic; no device needed)
 bool smm_jit_grouped_eligible(const SmmBatch& s);
 int smm_jit_prebuild(const SmmBatch* shapes, int nshapes, int grouped, int* built); // code objects into the cache on disk; returns failures
 std::string gen_smm_grouped_source_for(const SmmBatch* groups, int ngroups, bool tiles = false);

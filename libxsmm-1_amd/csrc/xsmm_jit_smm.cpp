@@ -2116,8 +2116,7 @@ static SmmGeom smm_jit_geometry(const SmmBatch& s, int variant, JitKernel* k)
       per_cu = smm_per_cu(g.lds, 3);
     }
     if (0 < bpc64_env) per_cu = bpc64_env;
-    g.runlen = (SYNC_RUNS == s.sync) ? s.uniform_run : 1;
-    units = s.batch / g.runlen;
+    units = s.batch; // (the plan offers this kernel to independent items only: runs of one)
   }
   else { // the register-tiled streaming and wave run forms: work-groups of up to four waves
     const int pack = smm_jit_pack_of(variant);
@@ -2468,7 +2467,7 @@ void plan_packed(SmmPlan& p, const char* name, int variant, int pack, int rest)
   if (0 != p.batch.batch % pack) plan_part(p, a, rest, SLICE_REST);
 }
 
-// the matrix-core tier (32 < max(M, N) <= 64, K <= 64; independent items, or runs of a uniform length): the descriptor baked in
+// the matrix-core tier (32 < max(M, N) <= 64, K <= 64; independent items): the descriptor baked in
 void plan_mfma(const SmmBatch& s, SmmPlan& p)
 {
   static const int on = (int)knob("XSMM_SMMJIT_MFMA", 1);
@@ -2479,8 +2478,9 @@ void plan_mfma(const SmmBatch& s, SmmPlan& p)
   const bool transb = (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B)); // (B^T in memory: served by the one-wave-per-item form only)
   if (!((wave_min < s.m || wave_min < s.n) && s.m <= 64 && s.n <= 64 && 0 < s.k && s.k <= 64 && s.lda >= s.m && s.ldb >= (transb ? s.n : s.k) && s.ldc >= s.m)) return;
   if (4 == s.typesize && 64 == s.m && 64 == s.n && 64 == s.k && 64 == s.lda && 64 == s.ldb && 64 == s.ldc && SYNC_NONE == s.sync) return; // the hand-tuned tight 64^3 kernel
-  const bool runs = (SYNC_RUNS == s.sync && 0 < s.uniform_run && 0 == s.batch % s.uniform_run);
-  if (!(SYNC_NONE == s.sync || runs) || (runs ? s.batch / s.uniform_run : s.batch) < 1) return;
+  // (independent items only: runs of a uniform length come from blocked GEMM alone, which goes to the pre-compiled run kernels of
+  // kernels/smm_special.hip and the specialised tier without asking this one -- DESIGN.md section 8k)
+  if (SYNC_NONE != s.sync || s.batch < 1) return;
   if (s.batch < smm_jit_min_batch() && 0 == s.jit_always) return;
   const bool f64 = (8 == s.typesize);
   // 16-byte chunks for strided batches of suitably shaped and aligned items, else element by element (any shape, index and
@@ -2510,8 +2510,7 @@ void plan_mfma(const SmmBatch& s, SmmPlan& p)
   if (!(32 < s.m || 32 < s.n)) return; // (the work-group forms below are for shapes beyond 32)
   const bool tight = !f64 && s.lda == s.m && s.ldb == s.k && 0 == ((s.m * s.k) & 3) && 0 == ((s.k * s.n) & 3);
   const bool tightc = !f64 && s.ldc == s.m && 0 == ((s.m * s.n) & 3) && 0 != (s.m & 31) && 0 != tightc_on;
-  plan_add(p, TIER_MFMA, f64 ? (runs ? "smm_f64_mfma_wg_runs_jit" : "smm_f64_mfma_wg_jit") : (runs ? "smm_f32_mfma_wg_runs_jit" : "smm_f32_mfma_wg_jit"),
-           SMM_JIT_MFMA | (tight ? SMM_JIT_MFMA_TIGHT : 0) | (tightc ? SMM_JIT_MFMA_TIGHTC : 0));
+  plan_add(p, TIER_MFMA, f64 ? "smm_f64_mfma_wg_jit" : "smm_f32_mfma_wg_jit", SMM_JIT_MFMA | (tight ? SMM_JIT_MFMA_TIGHT : 0) | (tightc ? SMM_JIT_MFMA_TIGHTC : 0));
 }
 
 // 16-bit inputs (lowp 1: i16 -> i32, 3: bf16 -> f32, 4: bf16 -> bf16): tight items with independent C
@@ -2644,13 +2643,19 @@ static SmmBatch smm_slice(const SmmPlan& p, int slice)
   return s;
 }
 
+// XSMM_SMMJIT_SKIP (developer knob, read on every call: the tests run every link of a launch chain alone): a bit mask of links that
+// are treated as not ready. Bits 0-7: the alternatives of a plan by their position in SmmPlan::alts (both tiers counted); bit 8: the
+// hand-written kernels (launch_smm_special). A skipped alternative is not asked for: nothing is compiled for it.
+int smm_skip_mask() { return (int)knob("XSMM_SMMJIT_SKIP", 0); }
+
 // Launches the first alternative of the tier whose kernels are all ready (every kernel of an alternative is asked for, so that
 // the compiler thread builds them all). -1: none is (the caller's next tier serves, with the same bits).
 static int smm_jit_execute(const SmmPlan& p, int tier, void* stream, const char** name)
 {
+  const int skip = smm_skip_mask();
   for (int i = 0; i < p.nalts; ++i) {
     const SmmAlt& a = p.alts[i];
-    if (tier != a.tier) continue;
+    if (tier != a.tier || 0 != (skip & (1 << i))) continue;
     if (0 < a.ntiles) {
       GroupedPlan gp;
       JitKernel* const kern = grouped_resolve(a.tiles, a.ntiles, false, true, gp);
@@ -2682,6 +2687,32 @@ int launch_smm_jit(const SmmBatch& s, void* stream, const char** name)
   SmmPlan p;
   smm_jit_plan(s, p);
   return smm_jit_execute(p, TIER_JIT, stream, name);
+}
+
+// The plan of batch s as text, one line per alternative (libxsmm_amd_smm_plan_describe; no device needed):
+//   <position> <mfma|jit> <name> parts=<n> [<variant>:<all|packed|rest> ...] tiles=<n> [<m>x<n>:<variant> ...]
+// check_tiles: the grouped text of every alternative that runs the tiles of C is compiled as well; *failed counts those that do not.
+std::string smm_plan_describe(const SmmBatch& s, bool check_tiles, int* failed)
+{
+  static const char* const slice_name[] = { "all", "packed", "rest" };
+  SmmPlan p;
+  smm_jit_plan(s, p);
+  std::string out;
+  char word[160];
+  for (int i = 0; i < p.nalts; ++i) {
+    const SmmAlt& a = p.alts[i];
+    snprintf(word, sizeof(word), "%d %s %s parts=%d", i, TIER_MFMA == a.tier ? "mfma" : "jit", a.name, a.nparts); out += word;
+    for (int j = 0; j < a.nparts; ++j) { snprintf(word, sizeof(word), " %d:%s", a.part[j].key.variant, slice_name[a.part[j].slice]); out += word; }
+    snprintf(word, sizeof(word), " tiles=%d", a.ntiles); out += word;
+    for (int j = 0; j < a.ntiles; ++j) { snprintf(word, sizeof(word), " %dx%d:%d", a.tiles[j].m, a.tiles[j].n, smm_run_variant(a.tiles[j], true)); out += word; }
+    out += "\n";
+    if (check_tiles && 0 < a.ntiles) {
+      std::string log;
+      const std::string src = gen_smm_grouped_source_for(a.tiles, a.ntiles, true);
+      if ((src.empty() || 0 != jit_check_source(src, &log)) && nullptr != failed) ++*failed;
+    }
+  }
+  return out;
 }
 
 // Code objects ahead of time (no device needed): every kernel the plans of a fixed set of batches per shape name -- strided
