@@ -2,9 +2,9 @@
  * tensor handles that link caller memory (reference: include/libxsmm_dnn.h:47-263 and :359-390, include/libxsmm_typedefs.h:
  * 311-346, src/libxsmm_dnn.c:70-189, :330-360, :1000-1570), and the producers of low-precision GEMM inputs: fp32 -> int16
  * quantisation, its inverse and the fp32 <-> bf16 converters (:331-357 and :414-426, src/libxsmm_dnn.c:2394-2907). The layer
- * that uses the tensor handles is the fully-connected one (libxsmm_dnn_fullyconnected.h). The convolution, pooling, fused
- * batch-norm and RNN entry points of the reference are not provided, nor are the descriptors and enumerations
- * only they use. The common part lies in libxsmm_dnn_tensor.h, a file of this project's that this header includes (the
+ * that uses the tensor handles is the fully-connected one (libxsmm_dnn_fullyconnected.h); the pooling layer and the fused
+ * batch-norm layer have headers of their own (libxsmm_dnn_pooling.h, libxsmm_dnn_fusedbatchnorm.h). The convolution and RNN
+ * entry points of the reference are not provided, nor are the descriptors and enumerations only they use. The common part lies in libxsmm_dnn_tensor.h, a file of this project's that this header includes (the
  * reference keeps it in libxsmm_dnn.h itself); the quantisation and conversion functions are declared below. Line numbers
  * refer to the reference's include/libxsmm_dnn.h unless a file is named.
  *

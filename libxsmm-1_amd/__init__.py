@@ -93,6 +93,11 @@ class PoolingDesc(C.Structure):  # libxsmm_dnn_pooling_desc
                                        "threads", "datatype_in", "datatype_out", "datatype_mask", "buffer_format", "pooling_type")]
 
 
+class FusedBatchnormDesc(C.Structure):  # libxsmm_dnn_fusedbatchnorm_desc
+    _fields_ = [(n, C.c_int) for n in ("N", "C", "H", "W", "u", "v", "pad_h_in", "pad_w_in", "pad_h_out", "pad_w_out", "threads", "datatype_in",
+                                       "datatype_out", "datatype_stats", "buffer_format", "fuse_order", "fuse_ops")]
+
+
 def build(verbose=False):
     """Compile csrc/ into lib/libxsmm.so for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
@@ -401,6 +406,17 @@ def _declare(L):
     sig("libxsmm_dnn_pooling_get_tensor", vp, vp, i, up)
     sig("libxsmm_dnn_pooling_release_tensor", u, vp, i)
     sig("libxsmm_dnn_pooling_execute_st", u, vp, i, i, i)
+    # the fused batch-norm layer (include/libxsmm_dnn_fusedbatchnorm.h)
+    sig("libxsmm_dnn_create_fusedbatchnorm", vp, FusedBatchnormDesc, up)
+    sig("libxsmm_dnn_destroy_fusedbatchnorm", u, vp)
+    sig("libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout", lp, vp, i, up)
+    sig("libxsmm_dnn_fusedbatchnorm_get_scratch_size", C.c_size_t, vp, up)
+    sig("libxsmm_dnn_fusedbatchnorm_bind_scratch", u, vp, vp)
+    sig("libxsmm_dnn_fusedbatchnorm_release_scratch", u, vp)
+    sig("libxsmm_dnn_fusedbatchnorm_bind_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_fusedbatchnorm_get_tensor", vp, vp, i, up)
+    sig("libxsmm_dnn_fusedbatchnorm_release_tensor", u, vp, i)
+    sig("libxsmm_dnn_fusedbatchnorm_execute_st", u, vp, i, i, i)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -974,3 +990,46 @@ def pool_bind_new(handle, ttype, data):
 def pool_execute(handle, kind, start_thread=0, tid=0):
     """libxsmm_dnn_pooling_execute_st; returns the status"""
     return lib().libxsmm_dnn_pooling_execute_st(handle, kind, start_thread, tid)
+
+
+# ---- the fused batch-norm layer (include/libxsmm_dnn_fusedbatchnorm.h) -------------------------------------------------------------
+DNN_FUSEDBN_ORDER_BN_ELTWISE_RELU = 0
+DNN_FUSEDBN_OPS_BN, DNN_FUSEDBN_OPS_BNSCALE, DNN_FUSEDBN_OPS_ELTWISE, DNN_FUSEDBN_OPS_RELU = 1, 2, 4, 8
+
+
+def bn_create(N, Cc, H, W, u=1, v=1, pad_h_in=0, pad_w_in=0, pad_h_out=0, pad_w_out=0, threads=1, datatype_in=DNN_F32, datatype_out=DNN_F32,
+              datatype_stats=DNN_F32, buffer_format=DNN_FORMAT_LIBXSMM, fuse_order=DNN_FUSEDBN_ORDER_BN_ELTWISE_RELU, fuse_ops=DNN_FUSEDBN_OPS_BN):
+    """libxsmm_dnn_create_fusedbatchnorm; returns (handle or None, status)"""
+    st = C.c_uint(0xdead)
+    desc = FusedBatchnormDesc(N, Cc, H, W, u, v, pad_h_in, pad_w_in, pad_h_out, pad_w_out, threads, datatype_in, datatype_out, datatype_stats,
+                              buffer_format, fuse_order, fuse_ops)
+    h = lib().libxsmm_dnn_create_fusedbatchnorm(desc, C.byref(st))
+    return h, st.value
+
+
+def bn_layout(handle, ttype):
+    """libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout; returns (pointer or None, status). The caller destroys the layout."""
+    st = C.c_uint(0xdead)
+    l = lib().libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout(handle, ttype, C.byref(st))
+    return (l if l else None), st.value
+
+
+def bn_bind_new(handle, ttype, data):
+    """layout of ttype, a tensor linked to data, bound to the handle; returns the tensor handle (the caller destroys it)"""
+    L = lib()
+    l, st = bn_layout(handle, ttype)
+    if l is None:
+        raise RuntimeError("no layout: status %d" % st)
+    t, st = dnn_link_tensor(l, data)
+    L.libxsmm_dnn_destroy_tensor_datalayout(l)
+    if not t:
+        raise RuntimeError("link failed: status %d" % st)
+    st = L.libxsmm_dnn_fusedbatchnorm_bind_tensor(handle, t, ttype)
+    if 0 != st:
+        raise RuntimeError("bind failed: status %d" % st)
+    return t
+
+
+def bn_execute(handle, kind, start_thread=0, tid=0):
+    """libxsmm_dnn_fusedbatchnorm_execute_st; returns the status"""
+    return lib().libxsmm_dnn_fusedbatchnorm_execute_st(handle, kind, start_thread, tid)
