@@ -11,8 +11,8 @@
 //              dgamma += ((x - mean) * dout) * rstd, dbeta += dout from +0.0; per channel the images in order from +0.0.
 //   BWD apply  strided pixels: din = ((gamma * rstd) * recp_nhw) * (nhw * dout - (dbeta + ((x - mean) * dgamma) * rstd)).
 //   bf16       widened by a shift, computed in fp32, stored by truncation.
-// Every add, subtract and multiply goes through add_rn / sub_rn / mul_rn below, compiled with fp contraction off (as in
-// pool.hip: the compiler's default would fuse them). No instantiation may hold an fp32 fma.
+// Every add, subtract and multiply goes through add_rn / sub_rn / mul_rn of dnn_pixel.cuh, compiled with fp contraction off
+// (the compiler's default would fuse them: see there). No instantiation may hold an fp32 fma.
 //
 // Partial sums. The sums are ordered: per item there are 2 x 16 chains, each as long as the plane, and nothing may be
 // reassociated. So moving the bytes is separated from adding them. One work-group owns one plane. All 256 threads fetch
@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../xsmm_dnn_internal.hpp"
+#include "dnn_pixel.cuh"
 
 namespace {
 
@@ -43,40 +44,10 @@ constexpr int CH = 128; // pixels of a chunk of the partial sums: 8 KiB of fp32 
 
 // one rounding each, never fused (the pragma covers what is defined from here to the end of the file)
 #pragma clang fp contract(off)
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-
-template<bool BF16> struct Piece;
-template<> struct Piece<false> {      // four fp32 lanes
-  static constexpr int LANES = 4;
-  static __device__ __forceinline__ void load(const void* base, long long elem, float (&f)[4])
-  {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(base) + elem);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-  }
-  static __device__ __forceinline__ void store(void* base, long long elem, const float (&f)[4])
-  {
-    *reinterpret_cast<float4*>(static_cast<float*>(base) + elem) = make_float4(f[0], f[1], f[2], f[3]);
-  }
-};
-template<> struct Piece<true> {       // eight bf16 lanes
-  static constexpr int LANES = 8;
-  static __device__ __forceinline__ void load(const void* base, long long elem, float (&f)[8])
-  {
-    const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(base) + elem);
-    const unsigned int w[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-  }
-  static __device__ __forceinline__ void store(void* base, long long elem, const float (&f)[8])
-  {
-    unsigned int w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (__float_as_uint(f[2 * i]) >> 16) | (__float_as_uint(f[2 * i + 1]) & 0xffff0000u);
-    *reinterpret_cast<uint4*>(static_cast<unsigned short*>(base) + elem) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
+using pixel::Piece;
+using pixel::add_rn;
+using pixel::sub_rn;
+using pixel::mul_rn;
 
 // LANES channel scalars of a block, from lane0 on
 template<int L>

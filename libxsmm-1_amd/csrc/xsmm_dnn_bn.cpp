@@ -22,31 +22,15 @@ struct libxsmm_dnn_fusedbatchnorm { // the fields of src/libxsmm_main.h's libxsm
   libxsmm_dnn_tensor* reg_add; libxsmm_dnn_tensor* grad_add;
   libxsmm_dnn_tensor* reg_beta; libxsmm_dnn_tensor* reg_gamma; libxsmm_dnn_tensor* grad_beta; libxsmm_dnn_tensor* grad_gamma;
   libxsmm_dnn_tensor* expvalue; libxsmm_dnn_tensor* rcpstddev; libxsmm_dnn_tensor* variance;
-  int ifmblock, ifmblock_hp, ofmblock, ofmblock_lp, blocksifm, blocksofm, fm_lp_block;
+  FmBlocks fm;
   size_t scratch_size;
   void* scratch;
   float* partials; // device memory of this handle: per logical thread 2 * 16 * blocks * N floats; allocated by the first execute_st
 };
 
-namespace {
-
-std::mutex partials_lock; // the first execute_st of a handle may come from several threads at once
-
-bool dt_pair(const libxsmm_dnn_fusedbatchnorm_desc& d, libxsmm_dnn_datatype in, libxsmm_dnn_datatype out) { return d.datatype_in == in && d.datatype_out == out; }
-bool is_input(libxsmm_dnn_tensor_type t)
-{
-  return LIBXSMM_DNN_REGULAR_INPUT == t || LIBXSMM_DNN_GRADIENT_INPUT == t || LIBXSMM_DNN_INPUT == t || LIBXSMM_DNN_REGULAR_INPUT_ADD == t
-      || LIBXSMM_DNN_GRADIENT_INPUT_ADD == t;
-}
-bool is_output(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_OUTPUT == t || LIBXSMM_DNN_GRADIENT_OUTPUT == t || LIBXSMM_DNN_OUTPUT == t; }
-bool is_channel(libxsmm_dnn_tensor_type t)
-{
-  return LIBXSMM_DNN_REGULAR_CHANNEL_BETA == t || LIBXSMM_DNN_GRADIENT_CHANNEL_BETA == t || LIBXSMM_DNN_CHANNEL_BETA == t
-      || LIBXSMM_DNN_REGULAR_CHANNEL_GAMMA == t || LIBXSMM_DNN_GRADIENT_CHANNEL_GAMMA == t || LIBXSMM_DNN_CHANNEL_GAMMA == t
-      || LIBXSMM_DNN_CHANNEL_EXPECTVAL == t || LIBXSMM_DNN_CHANNEL_RCPSTDDEV == t || LIBXSMM_DNN_CHANNEL_VARIANCE == t;
-}
-
-libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fusedbatchnorm* h, libxsmm_dnn_tensor_type t) // nullptr: not one of the thirteen bindable types
+// the tensor a type binds; nullptr: not one of the thirteen bindable types (at global scope: the templates of
+// xsmm_dnn_internal.hpp find it by its argument)
+static libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fusedbatchnorm* h, libxsmm_dnn_tensor_type t)
 {
   switch (t) {
     case LIBXSMM_DNN_REGULAR_INPUT: return &h->reg_input;
@@ -65,52 +49,19 @@ libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fusedbatchnorm* h, libxsmm_dnn_tensor_t
     default: return nullptr;
   }
 }
-bool bindable(libxsmm_dnn_tensor_type t) { libxsmm_dnn_fusedbatchnorm none; return nullptr != slot_of(&none, t); }
 
-// a layout of n dimensions; false: out of memory
-bool layout_dims(libxsmm_dnn_tensor_datalayout* l, unsigned int n, const libxsmm_dnn_tensor_dimtype* types, const unsigned int* sizes)
+namespace {
+
+std::mutex partials_lock; // the first execute_st of a handle may come from several threads at once
+
+bool dt_pair(const libxsmm_dnn_fusedbatchnorm_desc& d, libxsmm_dnn_datatype in, libxsmm_dnn_datatype out) { return d.datatype_in == in && d.datatype_out == out; }
+bool is_add(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_INPUT_ADD == t || LIBXSMM_DNN_GRADIENT_INPUT_ADD == t; } // laid out as the input
+bool is_channel(libxsmm_dnn_tensor_type t)
 {
-  l->dim_type = static_cast<libxsmm_dnn_tensor_dimtype*>(malloc(n * sizeof(libxsmm_dnn_tensor_dimtype)));
-  l->dim_size = static_cast<unsigned int*>(malloc(n * sizeof(unsigned int)));
-  if (nullptr == l->dim_type || nullptr == l->dim_size) { free(l->dim_type); free(l->dim_size); l->dim_type = nullptr; l->dim_size = nullptr; return false; }
-  l->num_dims = n;
-  for (unsigned int i = 0; i < n; ++i) { l->dim_type[i] = types[i]; l->dim_size[i] = sizes[i]; }
-  return true;
+  return LIBXSMM_DNN_REGULAR_CHANNEL_BETA == t || LIBXSMM_DNN_GRADIENT_CHANNEL_BETA == t || LIBXSMM_DNN_CHANNEL_BETA == t
+      || LIBXSMM_DNN_REGULAR_CHANNEL_GAMMA == t || LIBXSMM_DNN_GRADIENT_CHANNEL_GAMMA == t || LIBXSMM_DNN_CHANNEL_GAMMA == t
+      || LIBXSMM_DNN_CHANNEL_EXPECTVAL == t || LIBXSMM_DNN_CHANNEL_RCPSTDDEV == t || LIBXSMM_DNN_CHANNEL_VARIANCE == t;
 }
-
-// The tensors of a pass where the kernels can reach them. Those in pageable host memory share one block of device scratch
-// (slot 6 of the calling thread), carved up in the order in which they are asked for.
-struct Operand {
-  void* dev; void* host; size_t bytes; size_t offset; bool upload;
-};
-struct Staging {
-  Operand op[12]; int n = 0; size_t total = 0; bool wait = false;
-  Operand* add(const libxsmm_dnn_tensor* t, bool upload)
-  {
-    Operand* const o = &op[n++];
-    libxsmm_dnn_err_t st;
-    o->bytes = (size_t)libxsmm_dnn_get_tensor_elements(t->layout, &st) * libxsmm_dnn_typesize(t->layout->datatype);
-    const int kind = pointer_kind(t->data);
-    o->dev = t->data; o->host = nullptr; o->offset = 0; o->upload = upload;
-    if (0 != (kind & 2)) wait = true;
-    if (0 == (kind & 1)) { o->host = t->data; o->dev = nullptr; o->offset = total; total += (o->bytes + 255) & ~(size_t)255; wait = true; }
-    return o;
-  }
-  bool place() // false: no memory, or a copy failed
-  {
-    if (0 == total) return true;
-    char* const base = static_cast<char*>(scratch(6, total));
-    if (nullptr == base) return false;
-    for (int i = 0; i < n; ++i) {
-      if (nullptr == op[i].host) continue;
-      op[i].dev = base + op[i].offset;
-      if (op[i].upload && 0 != h2d(op[i].dev, op[i].host, op[i].bytes)) return false;
-    }
-    return true;
-  }
-};
-bool back(const Operand* o) { return nullptr == o || nullptr == o->host || 0 == d2h(o->host, o->dev, o->bytes); }
-bool aligned16(const Operand* o) { return nullptr == o || 0 == reinterpret_cast<uintptr_t>(o->dev) % 16; }
 
 } // namespace
 
@@ -123,19 +74,7 @@ LIBXSMM_API libxsmm_dnn_fusedbatchnorm* libxsmm_dnn_create_fusedbatchnorm(libxsm
   *status = LIBXSMM_DNN_SUCCESS;
   memset(h, 0, sizeof(*h));
   h->desc = desc;
-  // libxsmm_dnn_get_feature_map_blocks(C, C) (src/libxsmm_dnn_setup.c:197-252): the output block is 16 whatever C is
-  if (f32) { h->ifmblock = desc.C >= 16 ? 16 : desc.C; h->fm_lp_block = 1; }
-  else {
-    h->ifmblock = desc.C >= 16 ? 8 : desc.C / 2; h->fm_lp_block = 2;
-    if (3 == desc.C) { h->ifmblock = 3; h->fm_lp_block = 1; }
-  }
-  h->ofmblock = 16;
-  h->ifmblock_hp = h->ifmblock * h->fm_lp_block;
-  h->ofmblock_lp = h->ofmblock / h->fm_lp_block;
-  // (a block of zero divides nothing: the reference would trap; here there are no blocks)
-  const int iblock = f32 ? h->ifmblock : h->ifmblock_hp;
-  h->blocksifm = 0 < iblock ? desc.C / iblock : 0;
-  h->blocksofm = desc.C / h->ofmblock;
+  h->fm = feature_map_blocks(desc.C, f32);
   h->scratch_size = sizeof(float) * 2 * (size_t)desc.C * (size_t)desc.N; // :80
   return h;
 }
@@ -151,52 +90,28 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_destroy_fusedbatchnorm(const libxsmm_d
 LIBXSMM_API libxsmm_dnn_tensor_datalayout* libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout(const libxsmm_dnn_fusedbatchnorm* h, const libxsmm_dnn_tensor_type type, libxsmm_dnn_err_t* status)
 { // :108-314
   typedef libxsmm_dnn_tensor_dimtype D;
-  const D dN = LIBXSMM_DNN_TENSOR_DIMTYPE_N, dH = LIBXSMM_DNN_TENSOR_DIMTYPE_H, dW = LIBXSMM_DNN_TENSOR_DIMTYPE_W, dC = LIBXSMM_DNN_TENSOR_DIMTYPE_C;
+  const D dC = LIBXSMM_DNN_TENSOR_DIMTYPE_C;
   *status = LIBXSMM_DNN_SUCCESS;
   if (nullptr == h) { *status = LIBXSMM_DNN_ERR_INVALID_HANDLE; return nullptr; }
-  libxsmm_dnn_tensor_datalayout* l = static_cast<libxsmm_dnn_tensor_datalayout*>(malloc(sizeof(*l)));
-  if (nullptr == l) { *status = LIBXSMM_DNN_ERR_CREATE_LAYOUT; return nullptr; }
-  memset(l, 0, sizeof(*l));
+  libxsmm_dnn_tensor_datalayout* const l = layout_begin(status);
+  if (nullptr == l) return nullptr;
   const libxsmm_dnn_fusedbatchnorm_desc& d = h->desc;
   l->format = d.buffer_format;
   l->custom_format = LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM_1;
-  const bool f32 = dt_pair(d, LIBXSMM_DNN_DATATYPE_F32, LIBXSMM_DNN_DATATYPE_F32);
-  const unsigned int N = (unsigned int)d.N;
-  const unsigned int ifwp = (unsigned int)(d.W + 2 * d.pad_w_in), ifhp = (unsigned int)(d.H + 2 * d.pad_h_in);
-  // (a stride of zero divides nothing: the reference would trap; here the output has its padding only)
-  const unsigned int ofwp = (unsigned int)((0 != d.v ? d.W / d.v : 0) + 2 * d.pad_w_out), ofhp = (unsigned int)((0 != d.u ? d.H / d.u : 0) + 2 * d.pad_h_out);
+  const bool input = is_input(type) || is_add(type);
   bool ok = true; // false: the arrays could not be allocated
-  if (is_input(type) || is_output(type)) {
-    if (0 != (d.buffer_format & LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM)) {
-      if (f32) {
-        const D t[5] = { dC, dW, dH, dC, dN };
-        const unsigned int in[5] = { (unsigned int)h->ifmblock, ifwp, ifhp, (unsigned int)h->blocksifm, N };
-        const unsigned int out[5] = { (unsigned int)h->ofmblock, ofwp, ofhp, (unsigned int)h->blocksofm, N };
-        l->datatype = LIBXSMM_DNN_DATATYPE_F32;
-        ok = layout_dims(l, 5, t, is_input(type) ? in : out);
-      }
-      else {
-        const D t[6] = { dC, dC, dW, dH, dC, dN };
-        const unsigned int in[6] = { (unsigned int)h->fm_lp_block, (unsigned int)h->ifmblock, ifwp, ifhp, (unsigned int)h->blocksifm, N };
-        const unsigned int out[6] = { (unsigned int)h->fm_lp_block, (unsigned int)h->ofmblock_lp, ofwp, ofhp, (unsigned int)h->blocksofm, N };
-        l->datatype = LIBXSMM_DNN_DATATYPE_BF16;
-        ok = layout_dims(l, 6, t, is_input(type) ? in : out);
-      }
-    }
-    else if (0 != (d.buffer_format & LIBXSMM_DNN_TENSOR_FORMAT_NHWC)) {
-      const D t[4] = { dC, dW, dH, dN };
-      const unsigned int in[4] = { (unsigned int)d.C, ifwp, ifhp, N }, out[4] = { (unsigned int)d.C, ofwp, ofhp, N };
-      l->datatype = d.datatype_in;
-      ok = layout_dims(l, 4, t, is_input(type) ? in : out);
-    }
-    else *status = LIBXSMM_DNN_ERR_INVALID_FORMAT_GENERAL;
+  if (input || is_output(type)) {
+    // (a stride of zero divides nothing: the reference would trap; here the output has its padding only)
+    ok = activation_layout(l, d.buffer_format, d.datatype_in, d.datatype_out, h->fm, d.N, d.C, input, (unsigned int)(d.H + 2 * d.pad_h_in),
+                           (unsigned int)(d.W + 2 * d.pad_w_in), (unsigned int)((0 != d.u ? d.H / d.u : 0) + 2 * d.pad_h_out),
+                           (unsigned int)((0 != d.v ? d.W / d.v : 0) + 2 * d.pad_w_out), status);
   }
   else if (is_channel(type)) {
     l->tensor_type = LIBXSMM_DNN_CHANNEL_SCALAR;
     if (0 != (d.buffer_format & LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM)) {
       if (LIBXSMM_DNN_DATATYPE_F32 == d.datatype_stats) {
         const D t[2] = { dC, dC };
-        const unsigned int s[2] = { (unsigned int)(h->ifmblock * h->fm_lp_block), (unsigned int)h->blocksifm };
+        const unsigned int s[2] = { (unsigned int)(h->fm.ifmblock * h->fm.fm_lp_block), (unsigned int)h->fm.blocksifm };
         l->datatype = d.datatype_stats;
         ok = layout_dims(l, 2, t, s);
       }
@@ -214,62 +129,22 @@ LIBXSMM_API libxsmm_dnn_tensor_datalayout* libxsmm_dnn_fusedbatchnorm_create_ten
     else *status = LIBXSMM_DNN_ERR_INVALID_FORMAT_GENERAL;
   }
   else *status = LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (!ok) *status = LIBXSMM_DNN_ERR_CREATE_LAYOUT_ARRAYS;
-  if (LIBXSMM_DNN_SUCCESS != *status) { free(l->dim_type); free(l->dim_size); free(l); return nullptr; }
-  return l;
+  return layout_end(l, ok, status);
 }
 
-LIBXSMM_API size_t libxsmm_dnn_fusedbatchnorm_get_scratch_size(const libxsmm_dnn_fusedbatchnorm* handle, libxsmm_dnn_err_t* status)
-{ // :316-327 (64 bytes more for a caller that does not align)
-  *status = LIBXSMM_DNN_SUCCESS;
-  if (nullptr != handle) return handle->scratch_size + 64;
-  *status = LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  return 0;
-}
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_bind_scratch(libxsmm_dnn_fusedbatchnorm* handle, const void* scratch)
-{ // :330-353 (the pointer is kept, aligned as there, and never dereferenced)
-  const uintptr_t address = reinterpret_cast<uintptr_t>(scratch);
-  if (nullptr == scratch) return LIBXSMM_DNN_ERR_SCRATCH_NOT_ALLOCED;
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  handle->scratch = reinterpret_cast<void*>(0 == address % 64 ? address : address + (64 - address % 64));
-  return LIBXSMM_DNN_SUCCESS;
-}
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_release_scratch(libxsmm_dnn_fusedbatchnorm* handle)
-{ // :356-365
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  handle->scratch = nullptr;
-  return LIBXSMM_DNN_SUCCESS;
-}
-
+// scratch :316-365 (kept, aligned as there, and never dereferenced) and binding :369-536
+LIBXSMM_API size_t libxsmm_dnn_fusedbatchnorm_get_scratch_size(const libxsmm_dnn_fusedbatchnorm* handle, libxsmm_dnn_err_t* status) { return scratch_size_of(handle, status); }
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_bind_scratch(libxsmm_dnn_fusedbatchnorm* handle, const void* scratch) { return bind_scratch(handle, scratch); }
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_release_scratch(libxsmm_dnn_fusedbatchnorm* handle) { return release_scratch(handle); }
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_bind_tensor(libxsmm_dnn_fusedbatchnorm* handle, const libxsmm_dnn_tensor* tensor, const libxsmm_dnn_tensor_type type)
-{ // :369-428
-  libxsmm_dnn_err_t status = LIBXSMM_DNN_SUCCESS;
-  if (!bindable(type)) return LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (nullptr == handle || nullptr == tensor) return LIBXSMM_DNN_ERR_INVALID_HANDLE_TENSOR;
-  libxsmm_dnn_tensor_datalayout* const want = libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout(handle, type, &status);
-  if (0 == libxsmm_dnn_compare_tensor_datalayout(want, tensor->layout, &status)) *slot_of(handle, type) = const_cast<libxsmm_dnn_tensor*>(tensor);
-  else status = LIBXSMM_DNN_ERR_MISMATCH_TENSOR;
-  if (nullptr != want) libxsmm_dnn_destroy_tensor_datalayout(want);
-  return status;
+{
+  return bind_tensor(handle, tensor, type, libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout);
 }
-
 LIBXSMM_API libxsmm_dnn_tensor* libxsmm_dnn_fusedbatchnorm_get_tensor(libxsmm_dnn_fusedbatchnorm* handle, const libxsmm_dnn_tensor_type type, libxsmm_dnn_err_t* status)
-{ // :431-483
-  *status = LIBXSMM_DNN_SUCCESS;
-  if (!bindable(type)) { *status = LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE; return nullptr; }
-  if (nullptr == handle) { *status = LIBXSMM_DNN_ERR_INVALID_HANDLE; return nullptr; }
-  return *slot_of(handle, type);
+{
+  return get_tensor(handle, type, status);
 }
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_release_tensor(libxsmm_dnn_fusedbatchnorm* handle, const libxsmm_dnn_tensor_type type)
-{ // :486-536
-  if (!bindable(type)) return LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  *slot_of(handle, type) = nullptr;
-  return LIBXSMM_DNN_SUCCESS;
-}
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_release_tensor(libxsmm_dnn_fusedbatchnorm* handle, const libxsmm_dnn_tensor_type type) { return release_tensor(handle, type); }
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_fusedbatchnorm* h, libxsmm_dnn_compute_kind kind, int start_thread, int tid)
 { // :539-575 and the drivers of the two passes (src/libxsmm_dnn_fusedbatchnorm_forward.c:132-233, _backward.c:131-239)
@@ -299,19 +174,16 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_
   const int ltid = tid - start_thread;
   if (ltid < 0 || d.threads < 1) return LIBXSMM_DNN_ERR_GENERAL;
   // the kernels address pixels of 16 channels, with 32-bit indices inside a plane
-  if (16 != h->ifmblock_hp || h->blocksifm != h->blocksofm) return LIBXSMM_DNN_ERR_GENERAL;
+  if (16 != h->fm.ifmblock_hp || h->fm.blocksifm != h->fm.blocksofm) return LIBXSMM_DNN_ERR_GENERAL;
   if (d.N < 1 || d.H < 1 || d.W < 1 || d.u < 1 || d.v < 1 || d.pad_h_in < 0 || d.pad_w_in < 0 || d.pad_h_out < 0 || d.pad_w_out < 0
     || 0 != d.H % d.u || 0 != d.W % d.v || (long long)d.H * d.W >= (1LL << 27))
   {
     return LIBXSMM_DNN_ERR_GENERAL;
   }
 
-  // the share of ltid (the templates' chunksize, thr_begin, thr_end)
-  const long long blocks = h->blocksifm, work = (long long)d.N * blocks;
-  const long long chunk = (0 == work % d.threads) ? (work / d.threads) : (work / d.threads + 1);
-  const long long b0 = (ltid * chunk < work) ? ltid * chunk : work;
-  const long long b1 = ((ltid + 1LL) * chunk < work) ? (ltid + 1LL) * chunk : work;
-  if (ltid >= d.threads || b0 >= b1) return LIBXSMM_DNN_SUCCESS;
+  const long long blocks = h->fm.blocksifm, work = (long long)d.N * blocks;
+  long long b0, b1;
+  if (!thread_share(work, d.threads, ltid, &b0, &b1)) return LIBXSMM_DNN_SUCCESS;
   if (work > 0x7fffffffLL / 32) return LIBXSMM_DNN_ERR_GENERAL;
 
   if (!device_ready()) { fail_no_device("libxsmm_dnn_fusedbatchnorm_execute_st"); return LIBXSMM_DNN_ERR_GENERAL; }
@@ -324,20 +196,20 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_
   }
   // (a staged destination starts from the caller's bytes: only the share's interior is written, and the whole image travels back)
   Staging s;
-  Operand* const ox = s.add(h->reg_input, true);
-  Operand* const ogamma = s.add(h->reg_gamma, true);
-  Operand* const omean = s.add(h->expvalue, true);
-  Operand* const orstd = s.add(h->rcpstddev, true);
-  Operand *obeta = nullptr, *ovar = nullptr, *oout = nullptr, *oadd = nullptr, *odout = nullptr, *odin = nullptr, *odgamma = nullptr, *odbeta = nullptr;
+  const Operand* const ox = s.add(h->reg_input);
+  const Operand* const ogamma = s.add(h->reg_gamma);
+  const Operand* const omean = s.add(h->expvalue);
+  const Operand* const orstd = s.add(h->rcpstddev);
+  const Operand *obeta = nullptr, *ovar = nullptr, *oout = nullptr, *oadd = nullptr, *odout = nullptr, *odin = nullptr, *odgamma = nullptr, *odbeta = nullptr;
   if (!bwd) {
-    obeta = s.add(h->reg_beta, true); ovar = s.add(h->variance, true); oout = s.add(h->reg_output, true);
-    if (eltwise) oadd = s.add(h->reg_add, true);
+    obeta = s.add(h->reg_beta); ovar = s.add(h->variance); oout = s.add(h->reg_output);
+    if (eltwise) oadd = s.add(h->reg_add);
   }
   else {
-    odout = s.add(h->grad_output, true); odin = s.add(h->grad_input, true);
-    odgamma = s.add(h->grad_gamma, true); odbeta = s.add(h->grad_beta, true);
-    if (eltwise) oadd = s.add(h->grad_add, true);
-    if (relu) oout = s.add(h->reg_output, true);
+    odout = s.add(h->grad_output); odin = s.add(h->grad_input);
+    odgamma = s.add(h->grad_gamma); odbeta = s.add(h->grad_beta);
+    if (eltwise) oadd = s.add(h->grad_add);
+    if (relu) oout = s.add(h->reg_output);
   }
   if (!s.place()) return LIBXSMM_DNN_ERR_GENERAL;
   if (!aligned16(ox) || !aligned16(oout) || !aligned16(oadd) || !aligned16(odout) || !aligned16(odin) || !aligned16(ogamma) || !aligned16(obeta)
@@ -346,11 +218,10 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_
     return LIBXSMM_DNN_ERR_GENERAL;
   }
   BnArgs g; memset(&g, 0, sizeof(g));
-  g.in = ox->dev; g.add = nullptr != oadd ? oadd->dev : nullptr; g.out = nullptr != oout ? oout->dev : nullptr;
-  g.dout = nullptr != odout ? odout->dev : nullptr; g.din = nullptr != odin ? odin->dev : nullptr;
-  g.gamma = static_cast<float*>(ogamma->dev); g.beta = nullptr != obeta ? static_cast<float*>(obeta->dev) : nullptr;
-  g.mean = static_cast<float*>(omean->dev); g.rstd = static_cast<float*>(orstd->dev); g.var = nullptr != ovar ? static_cast<float*>(ovar->dev) : nullptr;
-  g.dgamma = nullptr != odgamma ? static_cast<float*>(odgamma->dev) : nullptr; g.dbeta = nullptr != odbeta ? static_cast<float*>(odbeta->dev) : nullptr;
+  g.in = ox->dev; g.add = dev_of(oadd); g.out = dev_of(oout); g.dout = dev_of(odout); g.din = dev_of(odin);
+  g.gamma = static_cast<float*>(ogamma->dev); g.beta = static_cast<float*>(dev_of(obeta));
+  g.mean = static_cast<float*>(omean->dev); g.rstd = static_cast<float*>(orstd->dev); g.var = static_cast<float*>(dev_of(ovar));
+  g.dgamma = static_cast<float*>(dev_of(odgamma)); g.dbeta = static_cast<float*>(dev_of(odbeta));
   g.part = stats ? h->partials + region * (size_t)ltid : nullptr;
   g.N = d.N; g.H = d.H; g.W = d.W; g.u = d.u; g.v = d.v; g.blocks = (int)blocks;
   g.iph = d.pad_h_in; g.ipw = d.pad_w_in; g.oph = d.pad_h_out; g.opw = d.pad_w_out;
@@ -364,23 +235,11 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_
   for (int step = stats ? 0 : 2; step < 3; ++step) {
     const char* name = "";
     const int e = 0 == step ? launch_bn_partial(g, stream, &name) : (1 == step ? launch_bn_finish(g, stream, &name) : launch_bn_apply(g, stream, &name));
-    note_launch(name);
-    if (0 != e) {
-      fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-      return LIBXSMM_DNN_ERR_GENERAL;
-    }
+    if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
   }
   // what the pass wrote travels back if it was staged
-  bool ok = true;
-  if (!bwd) {
-    ok = back(oout);
-    if (stats) ok = ok && back(omean) && back(orstd) && back(ovar);
-  }
-  else {
-    ok = back(odin);
-    if (stats) ok = ok && back(odgamma) && back(odbeta) && (!relu || back(odout)) && (!eltwise || back(oadd));
-  }
-  if (!ok) return LIBXSMM_DNN_ERR_GENERAL;
-  if (s.wait) return 0 == stream_sync() ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
-  return LIBXSMM_DNN_SUCCESS;
+  bool ok;
+  if (!bwd) ok = stats ? s.finish({ oout, omean, orstd, ovar }) : s.finish({ oout });
+  else ok = stats ? s.finish({ odin, odgamma, odbeta, relu ? odout : nullptr, eltwise ? oadd : nullptr }) : s.finish({ odin });
+  return ok ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

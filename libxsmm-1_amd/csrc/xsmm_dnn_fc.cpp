@@ -27,22 +27,9 @@ struct libxsmm_dnn_fullyconnected { // the fields of src/libxsmm_main.h:574-597 
   void* scratch;
 };
 
-namespace {
-
-bool dt_pair(const libxsmm_dnn_fullyconnected_desc& d, libxsmm_dnn_datatype in, libxsmm_dnn_datatype out) { return d.datatype_in == in && d.datatype_out == out; }
-bool format_packed(const libxsmm_dnn_fullyconnected_desc& d) { return LIBXSMM_DNN_TENSOR_FORMAT_NCPACKED == d.buffer_format && LIBXSMM_DNN_TENSOR_FORMAT_CKPACKED == d.filter_format; }
-bool format_custom(const libxsmm_dnn_fullyconnected_desc& d) { return LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM == d.buffer_format && LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM == d.filter_format; }
-
-bool is_input(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_INPUT == t || LIBXSMM_DNN_GRADIENT_INPUT == t || LIBXSMM_DNN_INPUT == t; }
-bool is_output(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_OUTPUT == t || LIBXSMM_DNN_GRADIENT_OUTPUT == t || LIBXSMM_DNN_OUTPUT == t; }
-bool is_filter(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_FILTER == t || LIBXSMM_DNN_GRADIENT_FILTER == t || LIBXSMM_DNN_FILTER == t; }
-bool bindable(libxsmm_dnn_tensor_type t)
-{
-  return LIBXSMM_DNN_REGULAR_INPUT == t || LIBXSMM_DNN_GRADIENT_INPUT == t || LIBXSMM_DNN_REGULAR_OUTPUT == t || LIBXSMM_DNN_GRADIENT_OUTPUT == t
-      || LIBXSMM_DNN_REGULAR_FILTER == t || LIBXSMM_DNN_GRADIENT_FILTER == t;
-}
-
-libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fullyconnected* h, libxsmm_dnn_tensor_type t)
+// the tensor a type binds; nullptr: not one of the six bindable types (at global scope: the templates of xsmm_dnn_internal.hpp
+// find it by its argument)
+static libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fullyconnected* h, libxsmm_dnn_tensor_type t)
 {
   switch (t) {
     case LIBXSMM_DNN_REGULAR_INPUT: return &h->reg_input;
@@ -50,20 +37,17 @@ libxsmm_dnn_tensor** slot_of(libxsmm_dnn_fullyconnected* h, libxsmm_dnn_tensor_t
     case LIBXSMM_DNN_REGULAR_OUTPUT: return &h->reg_output;
     case LIBXSMM_DNN_GRADIENT_OUTPUT: return &h->grad_output;
     case LIBXSMM_DNN_REGULAR_FILTER: return &h->reg_filter;
-    default: return &h->grad_filter;
+    case LIBXSMM_DNN_GRADIENT_FILTER: return &h->grad_filter;
+    default: return nullptr;
   }
 }
 
-// a layout of n dimensions; false: out of memory
-bool layout_dims(libxsmm_dnn_tensor_datalayout* l, unsigned int n, const libxsmm_dnn_tensor_dimtype* types, const unsigned int* sizes)
-{
-  l->dim_type = static_cast<libxsmm_dnn_tensor_dimtype*>(malloc(n * sizeof(libxsmm_dnn_tensor_dimtype)));
-  l->dim_size = static_cast<unsigned int*>(malloc(n * sizeof(unsigned int)));
-  if (nullptr == l->dim_type || nullptr == l->dim_size) { free(l->dim_type); free(l->dim_size); l->dim_type = nullptr; l->dim_size = nullptr; return false; }
-  l->num_dims = n;
-  for (unsigned int i = 0; i < n; ++i) { l->dim_type[i] = types[i]; l->dim_size[i] = sizes[i]; }
-  return true;
-}
+namespace {
+
+bool dt_pair(const libxsmm_dnn_fullyconnected_desc& d, libxsmm_dnn_datatype in, libxsmm_dnn_datatype out) { return d.datatype_in == in && d.datatype_out == out; }
+bool format_packed(const libxsmm_dnn_fullyconnected_desc& d) { return LIBXSMM_DNN_TENSOR_FORMAT_NCPACKED == d.buffer_format && LIBXSMM_DNN_TENSOR_FORMAT_CKPACKED == d.filter_format; }
+bool format_custom(const libxsmm_dnn_fullyconnected_desc& d) { return LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM == d.buffer_format && LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM == d.filter_format; }
+bool is_filter(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_FILTER == t || LIBXSMM_DNN_GRADIENT_FILTER == t || LIBXSMM_DNN_FILTER == t; }
 
 FcDim plain(long long stride) { FcDim d; d.blk = FC_PLAIN; d.outer = 0; d.inner = stride; return d; }
 FcDim blocked(int blk, long long outer, long long inner) { FcDim d; d.blk = blk; d.outer = outer; d.inner = inner; return d; }
@@ -82,24 +66,6 @@ int tile_for(long long mi, long long mj)
   }();
   const long long big = ((mi + 127) / 128) * ((mj + 127) / 128);
   return big >= cus ? 128 : 64;
-}
-
-// One operand tensor where the kernel can reach it.
-struct Operand {
-  void* dev; void* host; size_t bytes; bool wait;
-};
-bool operand_in(Operand* o, const libxsmm_dnn_tensor* t, int slot, bool upload)
-{
-  libxsmm_dnn_err_t st;
-  o->bytes = (size_t)libxsmm_dnn_get_tensor_elements(t->layout, &st) * libxsmm_dnn_typesize(t->layout->datatype);
-  const int kind = pointer_kind(t->data);
-  o->dev = t->data; o->host = nullptr; o->wait = (0 != (kind & 2));
-  if (0 == (kind & 1)) {
-    o->dev = scratch(slot, o->bytes);
-    if (nullptr == o->dev || (upload && 0 != h2d(o->dev, t->data, o->bytes))) return false;
-    o->host = t->data; o->wait = true;
-  }
-  return true;
 }
 
 } // namespace
@@ -168,14 +134,13 @@ LIBXSMM_API libxsmm_dnn_tensor_datalayout* libxsmm_dnn_fullyconnected_create_ten
           dK = LIBXSMM_DNN_TENSOR_DIMTYPE_K, dR = LIBXSMM_DNN_TENSOR_DIMTYPE_R, dS = LIBXSMM_DNN_TENSOR_DIMTYPE_S;
   *status = LIBXSMM_DNN_SUCCESS;
   if (nullptr == h) { *status = LIBXSMM_DNN_ERR_INVALID_HANDLE; return nullptr; }
-  libxsmm_dnn_tensor_datalayout* l = static_cast<libxsmm_dnn_tensor_datalayout*>(malloc(sizeof(*l)));
-  if (nullptr == l) { *status = LIBXSMM_DNN_ERR_CREATE_LAYOUT; return nullptr; }
-  memset(l, 0, sizeof(*l));
+  libxsmm_dnn_tensor_datalayout* const l = layout_begin(status);
+  if (nullptr == l) return nullptr;
   l->custom_format = LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM_1;
   const libxsmm_dnn_fullyconnected_desc& d = h->desc;
   const bool f32 = dt_pair(d, LIBXSMM_DNN_DATATYPE_F32, LIBXSMM_DNN_DATATYPE_F32), mixed = dt_pair(d, LIBXSMM_DNN_DATATYPE_BF16, LIBXSMM_DNN_DATATYPE_F32),
              lowp = dt_pair(d, LIBXSMM_DNN_DATATYPE_BF16, LIBXSMM_DNN_DATATYPE_BF16);
-  const unsigned int N = (unsigned int)d.N, Cc = (unsigned int)d.C, K = (unsigned int)d.K;
+  const unsigned int N = (unsigned int)d.N, Cc = (unsigned int)d.C;
   bool ok = true; // false: the arrays could not be allocated
   if (is_input(type) || is_output(type)) {
     l->format = d.buffer_format;
@@ -255,63 +220,22 @@ LIBXSMM_API libxsmm_dnn_tensor_datalayout* libxsmm_dnn_fullyconnected_create_ten
     else *status = LIBXSMM_DNN_ERR_INVALID_FORMAT_GENERAL;
   }
   else *status = LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (!ok) *status = LIBXSMM_DNN_ERR_CREATE_LAYOUT_ARRAYS;
-  if (LIBXSMM_DNN_SUCCESS != *status) { free(l->dim_type); free(l->dim_size); free(l); return nullptr; }
-  (void)K;
-  return l;
+  return layout_end(l, ok, status);
 }
 
-LIBXSMM_API size_t libxsmm_dnn_fullyconnected_get_scratch_size(const libxsmm_dnn_fullyconnected* handle, libxsmm_dnn_err_t* status)
-{ // :494-505 (64 bytes more for a caller that does not align)
-  *status = LIBXSMM_DNN_SUCCESS;
-  if (nullptr != handle) return handle->scratch_size + 64;
-  *status = LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  return 0;
-}
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_bind_scratch(libxsmm_dnn_fullyconnected* handle, const void* scratch)
-{ // :508-531 (the pointer is kept, aligned as there, and never dereferenced)
-  const uintptr_t address = reinterpret_cast<uintptr_t>(scratch);
-  if (nullptr == scratch) return LIBXSMM_DNN_ERR_SCRATCH_NOT_ALLOCED;
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  handle->scratch = reinterpret_cast<void*>(0 == address % 64 ? address : address + (64 - address % 64));
-  return LIBXSMM_DNN_SUCCESS;
-}
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_release_scratch(libxsmm_dnn_fullyconnected* handle)
-{ // :534-544
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  handle->scratch = nullptr;
-  return LIBXSMM_DNN_SUCCESS;
-}
-
+// scratch :494-544 (kept, aligned as there, and never dereferenced) and binding :547-660
+LIBXSMM_API size_t libxsmm_dnn_fullyconnected_get_scratch_size(const libxsmm_dnn_fullyconnected* handle, libxsmm_dnn_err_t* status) { return scratch_size_of(handle, status); }
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_bind_scratch(libxsmm_dnn_fullyconnected* handle, const void* scratch) { return bind_scratch(handle, scratch); }
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_release_scratch(libxsmm_dnn_fullyconnected* handle) { return release_scratch(handle); }
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_bind_tensor(libxsmm_dnn_fullyconnected* handle, const libxsmm_dnn_tensor* tensor, const libxsmm_dnn_tensor_type type)
-{ // :547-588
-  libxsmm_dnn_err_t status = LIBXSMM_DNN_SUCCESS;
-  if (!bindable(type)) return LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (nullptr == handle || nullptr == tensor) return LIBXSMM_DNN_ERR_INVALID_HANDLE_TENSOR;
-  libxsmm_dnn_tensor_datalayout* const want = libxsmm_dnn_fullyconnected_create_tensor_datalayout(handle, type, &status);
-  if (0 == libxsmm_dnn_compare_tensor_datalayout(want, tensor->layout, &status)) *slot_of(handle, type) = const_cast<libxsmm_dnn_tensor*>(tensor);
-  else status = LIBXSMM_DNN_ERR_MISMATCH_TENSOR;
-  if (nullptr != want) libxsmm_dnn_destroy_tensor_datalayout(want);
-  return status;
+{
+  return bind_tensor(handle, tensor, type, libxsmm_dnn_fullyconnected_create_tensor_datalayout);
 }
-
 LIBXSMM_API libxsmm_dnn_tensor* libxsmm_dnn_fullyconnected_get_tensor(libxsmm_dnn_fullyconnected* handle, const libxsmm_dnn_tensor_type type, libxsmm_dnn_err_t* status)
-{ // :591-625
-  *status = LIBXSMM_DNN_SUCCESS;
-  if (!bindable(type)) { *status = LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE; return nullptr; }
-  if (nullptr == handle) { *status = LIBXSMM_DNN_ERR_INVALID_HANDLE; return nullptr; }
-  return *slot_of(handle, type);
+{
+  return get_tensor(handle, type, status);
 }
-
-LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_release_tensor(libxsmm_dnn_fullyconnected* handle, const libxsmm_dnn_tensor_type type)
-{ // :628-660
-  if (!bindable(type)) return LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE;
-  if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  *slot_of(handle, type) = nullptr;
-  return LIBXSMM_DNN_SUCCESS;
-}
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_release_tensor(libxsmm_dnn_fullyconnected* handle, const libxsmm_dnn_tensor_type type) { return release_tensor(handle, type); }
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_execute_st(libxsmm_dnn_fullyconnected* h, libxsmm_dnn_compute_kind kind, int start_thread, int tid)
 { // :663-708 and the drivers of the three passes
@@ -366,11 +290,8 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_execute_st(libxsmm_dnn_
     work = nbc * nbk; bmi = nbc; bmj = 1; i_major = true; // ofm1 * nBlocksIFm + ifm1
   }
 
-  // the share of ltid (the templates' chunksize, thr_begin, thr_end)
-  const int chunk = (0 == work % d.threads) ? (work / d.threads) : (work / d.threads + 1);
-  const long long b0 = ((long long)ltid * chunk < work) ? (long long)ltid * chunk : work;
-  const long long b1 = (((long long)ltid + 1) * chunk < work) ? ((long long)ltid + 1) * chunk : work;
-  if (ltid >= d.threads || b0 >= b1) return LIBXSMM_DNN_SUCCESS;
+  long long b0, b1;
+  if (!thread_share(work, d.threads, ltid, &b0, &b1)) return LIBXSMM_DNN_SUCCESS;
   g.i0 = 0; g.i1 = (int)mi; g.j0 = 0; g.j1 = (int)mj;
   g.masked = 0; g.sbi = sbi; g.mi = bmi; g.sbj = sbj; g.mj = bmj; g.w0 = (int)b0; g.w1 = (int)b1;
   if (0 != b0 || work != b1) { // the bounding rectangle of the blocks b0 .. b1-1; masked: the range is no rectangle
@@ -389,19 +310,16 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_execute_st(libxsmm_dnn_
 
   if (!device_ready()) { fail_no_device("libxsmm_dnn_fullyconnected_execute_st"); return LIBXSMM_DNN_ERR_GENERAL; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  Operand op, oq, od;
   // (a staged destination starts from the caller's bytes: only the share is written, and the whole image travels back)
-  if (!operand_in(&op, tp, 3, true) || !operand_in(&oq, tq, 4, true) || !operand_in(&od, td, 5, true)) return LIBXSMM_DNN_ERR_GENERAL;
-  g.p = op.dev; g.q = oq.dev; g.d = od.dev;
+  Staging s;
+  const Operand* const op = s.add(tp);
+  const Operand* const oq = s.add(tq);
+  const Operand* const od = s.add(td);
+  if (!s.place()) return LIBXSMM_DNN_ERR_GENERAL;
+  g.p = op->dev; g.q = oq->dev; g.d = od->dev;
   g.tile = tile_for(g.i1 - g.i0, g.j1 - g.j0);
   const char* name = "";
   const int e = launch_fc(g, stream, &name);
-  note_launch(name);
-  if (0 != e) {
-    fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-    return LIBXSMM_DNN_ERR_GENERAL;
-  }
-  if (nullptr != od.host) return 0 == d2h(od.host, od.dev, od.bytes) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
-  if (op.wait || oq.wait || od.wait) return 0 == stream_sync() ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
-  return LIBXSMM_DNN_SUCCESS;
+  if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
+  return s.finish({ od }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

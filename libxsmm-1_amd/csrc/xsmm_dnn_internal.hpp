@@ -1,10 +1,13 @@
-// xsmm_dnn_internal.hpp -- what the DNN sources share: the tensor behind the opaque handle of include/libxsmm_dnn.h.
+// xsmm_dnn_internal.hpp -- what the DNN sources share: the tensor behind the opaque handle of include/libxsmm_dnn.h, the
+// arguments of the layers' kernels, and the host plumbing that every layer has (xsmm_dnn_layer.cpp).
 #ifndef XSMM_DNN_INTERNAL_HPP
 #define XSMM_DNN_INTERNAL_HPP
 
 #include "xsmm_internal.hpp"
 #include "../../include/libxsmm_amd.h"
 #include "../../include/libxsmm_dnn.h"
+
+#include <initializer_list>
 
 struct libxsmm_dnn_tensor { // src/libxsmm_main.h:339-343
   libxsmm_dnn_tensor_datalayout* layout;
@@ -43,6 +46,99 @@ struct BnArgs {
 int launch_bn_partial(const BnArgs& args, void* stream, const char** name); // stats only: per (touched block, image) the ordered sums
 int launch_bn_finish(const BnArgs& args, void* stream, const char** name);  // stats only: images in order; mean / rstd / var or dgamma / dbeta
 int launch_bn_apply(const BnArgs& args, void* stream, const char** name);   // the items [w0, w1)
+
+// ---- what the layers share on the host (xsmm_dnn_layer.cpp) ---------------------------------------------------------------
+// A layer provides slot_of(handle*, type) at global scope (the tensor pointer a type binds; nullptr for a type it does not
+// bind), its create_tensor_datalayout and its execute_st; the rest of its API forwards to the templates below.
+
+// layouts: begin allocates and zeroes (nullptr: *status = ERR_CREATE_LAYOUT); layout_dims gives n dimensions (false: out of
+// memory); end turns !ok into ERR_CREATE_LAYOUT_ARRAYS, frees everything on any status but SUCCESS and returns l or nullptr
+libxsmm_dnn_tensor_datalayout* layout_begin(libxsmm_dnn_err_t* status);
+bool layout_dims(libxsmm_dnn_tensor_datalayout* l, unsigned int n, const libxsmm_dnn_tensor_dimtype* types, const unsigned int* sizes);
+libxsmm_dnn_tensor_datalayout* layout_end(libxsmm_dnn_tensor_datalayout* l, bool ok, libxsmm_dnn_err_t* status);
+
+bool is_input(libxsmm_dnn_tensor_type t);   // REGULAR_INPUT, GRADIENT_INPUT, INPUT
+bool is_output(libxsmm_dnn_tensor_type t);  // REGULAR_OUTPUT, GRADIENT_OUTPUT, OUTPUT
+
+// the blocking of C feature maps on both sides of a layer without a filter (pooling, batch-norm)
+struct FmBlocks { int ifmblock, ifmblock_hp, ofmblock, ofmblock_lp, blocksifm, blocksofm, fm_lp_block; };
+FmBlocks feature_map_blocks(int C, bool f32);
+// the activation layouts of those layers: LIBXSMM in F32 (5 dimensions) or BF16 (6), NHWC (4), else *status =
+// ERR_INVALID_FORMAT_GENERAL; input: the input side's block and extents; false: out of memory
+bool activation_layout(libxsmm_dnn_tensor_datalayout* l, libxsmm_dnn_tensor_format format, libxsmm_dnn_datatype datatype_in, libxsmm_dnn_datatype datatype_out,
+                       const FmBlocks& b, int N, int C, bool input, unsigned int ifhp, unsigned int ifwp, unsigned int ofhp, unsigned int ofwp, libxsmm_dnn_err_t* status);
+
+// the share [b0, b1) of logical thread ltid of work items (the templates' chunksize, thr_begin, thr_end); false: it is empty
+// (ltid >= threads included). threads >= 1, ltid >= 0.
+bool thread_share(long long work, int threads, int ltid, long long* b0, long long* b1);
+
+// The tensors of a pass where the kernels can reach them. Those in pageable host memory share one block of device scratch
+// (slot 6 of the calling thread), carved up at 256-byte offsets in the order in which they are asked for, and are uploaded.
+struct Operand { void* dev; void* host; size_t bytes; size_t offset; }; // host: nullptr unless staged
+struct Staging {
+  Operand op[12]; int n = 0; size_t total = 0; bool wait = false;
+  const Operand* add(const libxsmm_dnn_tensor* t); // (dev is valid after place)
+  bool place();                                    // false: no memory, or a copy failed
+  // after the launches: the staged ones of the operands the pass wrote (nullptr: skipped) travel back, and the stream is idle on
+  // return if anything was staged or is host-visible; false: a copy or the wait failed
+  bool finish(std::initializer_list<const Operand*> written);
+};
+inline void* dev_of(const Operand* o) { return nullptr != o ? o->dev : nullptr; }
+inline bool aligned16(const Operand* o) { return 0 == reinterpret_cast<uintptr_t>(dev_of(o)) % 16; }
+
+bool launched(const char* name, int hip_error); // counts the launch; false: it failed (and says so on stderr)
+
+template<typename H> size_t scratch_size_of(const H* h, libxsmm_dnn_err_t* status)
+{ // (64 bytes more for a caller that does not align)
+  *status = nullptr != h ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_INVALID_HANDLE;
+  return nullptr != h ? h->scratch_size + 64 : 0;
+}
+template<typename H> libxsmm_dnn_err_t bind_scratch(H* h, const void* p)
+{
+  const uintptr_t address = reinterpret_cast<uintptr_t>(p);
+  if (nullptr == p) return LIBXSMM_DNN_ERR_SCRATCH_NOT_ALLOCED;
+  if (nullptr == h) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
+  h->scratch = reinterpret_cast<void*>(0 == address % 64 ? address : address + (64 - address % 64));
+  return LIBXSMM_DNN_SUCCESS;
+}
+template<typename H> libxsmm_dnn_err_t release_scratch(H* h)
+{
+  if (nullptr == h) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
+  h->scratch = nullptr;
+  return LIBXSMM_DNN_SUCCESS;
+}
+// the slot of a type, checked in the reference's order: the type first (on a stand-in where there is no handle), then the handle
+// and whatever else must be there (rest)
+template<typename H> libxsmm_dnn_tensor** checked_slot(H* h, libxsmm_dnn_tensor_type type, bool rest, libxsmm_dnn_err_t invalid, libxsmm_dnn_err_t* status)
+{
+  H none;
+  const bool known = nullptr != slot_of(nullptr != h ? h : &none, type);
+  *status = !known ? LIBXSMM_DNN_ERR_UNKNOWN_TENSOR_TYPE : (nullptr != h && rest ? LIBXSMM_DNN_SUCCESS : invalid);
+  return LIBXSMM_DNN_SUCCESS == *status ? slot_of(h, type) : nullptr;
+}
+template<typename H, typename F> libxsmm_dnn_err_t bind_tensor(H* h, const libxsmm_dnn_tensor* tensor, libxsmm_dnn_tensor_type type, F make_layout)
+{
+  libxsmm_dnn_err_t status;
+  libxsmm_dnn_tensor** const slot = checked_slot(h, type, nullptr != tensor, LIBXSMM_DNN_ERR_INVALID_HANDLE_TENSOR, &status);
+  if (nullptr == slot) return status;
+  libxsmm_dnn_tensor_datalayout* const want = make_layout(h, type, &status);
+  if (0 == libxsmm_dnn_compare_tensor_datalayout(want, tensor->layout, &status)) *slot = const_cast<libxsmm_dnn_tensor*>(tensor);
+  else status = LIBXSMM_DNN_ERR_MISMATCH_TENSOR;
+  if (nullptr != want) libxsmm_dnn_destroy_tensor_datalayout(want);
+  return status;
+}
+template<typename H> libxsmm_dnn_tensor* get_tensor(H* h, libxsmm_dnn_tensor_type type, libxsmm_dnn_err_t* status)
+{
+  libxsmm_dnn_tensor** const slot = checked_slot(h, type, true, LIBXSMM_DNN_ERR_INVALID_HANDLE, status);
+  return nullptr != slot ? *slot : nullptr;
+}
+template<typename H> libxsmm_dnn_err_t release_tensor(H* h, libxsmm_dnn_tensor_type type)
+{
+  libxsmm_dnn_err_t status;
+  libxsmm_dnn_tensor** const slot = checked_slot(h, type, true, LIBXSMM_DNN_ERR_INVALID_HANDLE, &status);
+  if (nullptr != slot) *slot = nullptr;
+  return status;
+}
 
 } // namespace xsmm
 

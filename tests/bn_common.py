@@ -8,24 +8,16 @@ import zlib
 
 import numpy as np
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+from dnn_common import *  # noqa: F401,F403 (re-exported: the tests reach every shared name through this module)
+from dnn_common import FmHandle, fma
 
-F32, BF16, I32 = 1, 2, 4
-FMT_LIBXSMM, FMT_NHWC, FMT_NCHW = 1, 2, 4
-FWD, BWD, UPD, BWDUPD, ALL = 0, 1, 2, 3, 4
 OPS_BN, OPS_BNSCALE, OPS_ELTWISE, OPS_RELU = 1, 2, 4, 8
 FUSE_COMBINATIONS = (1, 2, 5, 6, 9, 10, 13, 14)
-REG_IN, REG_ADD, GRAD_IN, GRAD_ADD, REG_OUT, GRAD_OUT, GEN_IN, GEN_OUT, REG_FIL = 0, 1, 3, 4, 5, 6, 7, 8, 10
+REG_ADD, GRAD_ADD = 1, 4
 REG_BETA, GRAD_BETA, GEN_BETA, REG_GAMMA, GRAD_GAMMA, GEN_GAMMA, MEAN, RSTD, VAR, CHANNEL_SCALAR = 17, 18, 19, 20, 21, 22, 23, 24, 25, 26
 BINDABLE = (REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, REG_ADD, GRAD_ADD, REG_BETA, GRAD_BETA, REG_GAMMA, GRAD_GAMMA, MEAN, RSTD, VAR)
 LAYOUT_TYPES = BINDABLE + (GEN_IN, GEN_OUT, GEN_BETA, GEN_GAMMA, REG_FIL)  # the layouts the capture asks for (the last one is no batch-norm tensor)
-DIM_N, DIM_H, DIM_W, DIM_C = 0, 1, 2, 3
-
-SUCCESS = 0
-ERR_GENERAL, ERR_UNSUPPORTED_DATATYPE, ERR_INVALID_HANDLE, ERR_DATA_NOT_BOUND = 100000, 100002, 100004, 100005
-ERR_MISMATCH_TENSOR, ERR_INVALID_HANDLE_TENSOR, ERR_INVALID_KIND, ERR_INVALID_FORMAT_GENERAL = 100008, 100009, 100010, 100016
-ERR_SCRATCH_NOT_ALLOCED, ERR_UNKNOWN_TENSOR_TYPE = 100020, 100021
-ERR_FUSEBN_UNSUPPORTED_ORDER, ERR_FUSEBN_UNSUPPORTED_FUSION, ERR_INVALID_FORMAT_FUSEDBN = 100030, 100031, 100032
+ERR_FUSEBN_UNSUPPORTED_ORDER, ERR_FUSEBN_UNSUPPORTED_FUSION = 100030, 100031
 
 DESC_FIELDS = ("N", "C", "H", "W", "u", "v", "pad_h_in", "pad_w_in", "pad_h_out", "pad_w_out", "threads", "datatype_in", "datatype_out",
                "datatype_stats", "buffer_format", "fuse_order", "fuse_ops")
@@ -92,35 +84,14 @@ def captured_cases():
 
 
 # ---- handle rules (src/libxsmm_dnn_fusedbatchnorm.c:45-89, src/libxsmm_dnn_setup.c:197-252) ----------------------------------------
-class Handle:
+class Handle(FmHandle):
     def __init__(self, d):
-        self.d = d
-        self.ok = False
-        pair = (d["datatype_in"], d["datatype_out"])
-        if pair not in ((F32, F32), (BF16, BF16)):
-            self.status = ERR_UNSUPPORTED_DATATYPE
+        super().__init__(d)
+        if self.status != SUCCESS:
             return
-        self.status = SUCCESS
-        self.f32 = pair == (F32, F32)
-        Cc = d["C"]
-        if self.f32:
-            self.ifmblock, self.fm_lp_block = (16 if Cc >= 16 else Cc), 1
-        else:
-            self.ifmblock, self.fm_lp_block = (8 if Cc >= 16 else Cc // 2), 2
-            if Cc == 3:
-                self.ifmblock, self.fm_lp_block = 3, 1
-        self.ofmblock = 16
-        self.ifmblock_hp, self.ofmblock_lp = self.ifmblock * self.fm_lp_block, self.ofmblock // self.fm_lp_block
-        self.blocksifm = Cc // (self.ifmblock if self.f32 else self.ifmblock_hp)
-        self.blocksofm = Cc // self.ofmblock
-        self.scratch_size = 4 * 2 * Cc * d["N"]
-        self.ofh, self.ofw = d["H"] // d["u"], d["W"] // d["v"]
-        self.ifhp, self.ifwp = d["H"] + 2 * d["pad_h_in"], d["W"] + 2 * d["pad_w_in"]
-        self.ofhp, self.ofwp = self.ofh + 2 * d["pad_h_out"], self.ofw + 2 * d["pad_w_out"]
+        self.set_output(d["H"] // d["u"], d["W"] // d["v"])
+        self.scratch_size = 4 * 2 * d["C"] * d["N"]
         self.ok = True
-
-    def scratch(self):
-        return self.scratch_size + 64
 
     def layout(self, t):
         """(status, None) or (0, dict) as libxsmm_dnn_fusedbatchnorm_create_tensor_datalayout (:108-314)"""
@@ -128,35 +99,17 @@ class Handle:
         inp, out = t in (REG_IN, GRAD_IN, GEN_IN, REG_ADD, GRAD_ADD), t in (REG_OUT, GRAD_OUT, GEN_OUT)
         chan = t in (REG_BETA, GRAD_BETA, GEN_BETA, REG_GAMMA, GRAD_GAMMA, GEN_GAMMA, MEAN, RSTD, VAR)
         fmt = d["buffer_format"]
-
-        def made(types, sizes, datatype, tensor_type=0):
-            return SUCCESS, dict(num_dims=len(types), dim_type=list(types), dim_size=[int(s) for s in sizes], datatype=datatype, format=fmt,
-                                 custom_format=1, tensor_type=tensor_type)
         if inp or out:
-            if fmt & FMT_LIBXSMM:
-                if self.f32:
-                    sizes = (self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp else (self.ofmblock, self.ofwp, self.ofhp, self.blocksofm, d["N"])
-                    return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, F32)
-                sizes = (self.fm_lp_block, self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp \
-                    else (self.fm_lp_block, self.ofmblock_lp, self.ofwp, self.ofhp, self.blocksofm, d["N"])
-                return made((DIM_C, DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, BF16)
-            if fmt & FMT_NHWC:
-                sizes = (d["C"], self.ifwp, self.ifhp, d["N"]) if inp else (d["C"], self.ofwp, self.ofhp, d["N"])
-                return made((DIM_C, DIM_W, DIM_H, DIM_N), sizes, d["datatype_in"])
-            return ERR_INVALID_FORMAT_GENERAL, None
+            return self.activation_layout(inp)
         if chan:
             if not fmt & (FMT_LIBXSMM | FMT_NHWC):
                 return ERR_INVALID_FORMAT_GENERAL, None
             if d["datatype_stats"] != F32:
                 return ERR_UNSUPPORTED_DATATYPE, None
             if fmt & FMT_LIBXSMM:
-                return made((DIM_C, DIM_C), (self.ifmblock * self.fm_lp_block, self.blocksifm), F32, CHANNEL_SCALAR)
-            return made((DIM_C,), (d["C"],), F32, CHANNEL_SCALAR)
+                return made((DIM_C, DIM_C), (self.ifmblock * self.fm_lp_block, self.blocksifm), F32, fmt, CHANNEL_SCALAR)
+            return made((DIM_C,), (d["C"],), F32, fmt, CHANNEL_SCALAR)
         return ERR_UNKNOWN_TENSOR_TYPE, None
-
-    def runnable(self):
-        """the channel block is the 16 the kernels are written for, on both sides"""
-        return self.ifmblock_hp == 16 and self.blocksifm == self.blocksofm
 
     def needed(self, kind):
         ops = self.d["fuse_ops"]
@@ -190,21 +143,7 @@ class Handle:
             return ERR_GENERAL
         return SUCCESS
 
-    def work(self):
-        return self.d["N"] * self.blocksifm
-
-    def share(self, ltid):
-        work, threads = self.work(), self.d["threads"]
-        chunk = work // threads if work % threads == 0 else work // threads + 1
-        return min(ltid * chunk, work), min((ltid + 1) * chunk, work)
-
-    # shapes of the tensors as arrays: [item][row][column][16] and [block][16]
-    def in_shape(self):
-        return (self.work(), self.ifhp, self.ifwp, 16)
-
-    def out_shape(self):
-        return (self.work(), self.ofhp, self.ofwp, 16)
-
+    # [block][16]
     def chan_shape(self):
         return (self.blocksifm, 16)
 
@@ -212,34 +151,6 @@ class Handle:
         if key in ("x", "add", "din", "dadd"):
             return self.in_shape()
         return self.out_shape() if key in ("out", "dout") else self.chan_shape()
-
-
-def layout_size(l):
-    n = 1
-    for s in l["dim_size"]:
-        n *= s
-    return n * {F32: 4, BF16: 2, I32: 4}[l["datatype"]], n
-
-
-# ---- 16-bit elements: widened by a shift, stored by truncation (the generic templates' union) -------------------------------------
-def widen(a):
-    return (np.asarray(a, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def truncate(a):
-    return (np.ascontiguousarray(a, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def as_f32(h, a):
-    return a if h.f32 else widen(a)
-
-
-def stored(h, a):
-    return a.astype(np.float32) if h.f32 else truncate(a)
-
-
-def elem_dtype(h):
-    return np.float32 if h.f32 else np.uint16
 
 
 ALPHABET = np.array([-2.0, -1.0, -0.0, 0.0, 0.5, 1.0, 3.0], dtype=np.float32)
@@ -281,12 +192,6 @@ def inputs(name, d):
 
 
 # ---- the arithmetic contract -------------------------------------------------------------------------------------------------------
-def _fma(a, b, c):
-    """fp32 fma of arrays through float64: the product is exact there; the sum is rounded twice (to 53, then 24 bits), which
-    differs from one rounding only in rare halfway cases -- good enough to tell the fused form from the separate one"""
-    return (np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64) + np.asarray(c, dtype=np.float64)).astype(np.float32)
-
-
 def _nhw(d):
     nhw = np.float32(d["N"] * d["H"] * d["W"])
     return nhw, np.float32(1.0) / nhw
@@ -314,7 +219,7 @@ def forward(h, t, fused=False):
                 for wi in range(W):
                     v = xin[:, hi, wi, :]
                     s = s + v
-                    sq = _fma(v, v, sq) if fused else sq + v * v
+                    sq = fma(v, v, sq) if fused else sq + v * v
             s, sq = s.reshape(d["N"], h.blocksifm, 16), sq.reshape(d["N"], h.blocksifm, 16)
             ts = np.zeros(h.chan_shape(), dtype=np.float32)
             tq = np.zeros(h.chan_shape(), dtype=np.float32)
@@ -328,7 +233,7 @@ def forward(h, t, fused=False):
         xs = xin[:, ::d["u"], ::d["v"], :]
         gamma, beta, mean, rstd = (_by_block(h, t[k]) for k in ("gamma", "beta", "mean", "rstd"))
         part = gamma * (xs - mean)
-        o = _fma(part, rstd, beta) if fused else part * rstd + beta
+        o = fma(part, rstd, beta) if fused else part * rstd + beta
         if ops & OPS_ELTWISE:
             o = o + as_f32(h, t["add"])[:, iph:iph + H:d["u"], ipw:ipw + W:d["v"], :]
         if ops & OPS_RELU:
@@ -411,10 +316,6 @@ def written(d, kind):
     if not ops & OPS_BN:
         return ["din"]
     return ["din", "dgamma", "dbeta"] + (["dout"] if ops & OPS_RELU else []) + (["dadd"] if ops & OPS_ELTWISE else [])
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
 def load_golden():

@@ -8,22 +8,17 @@ import numpy as np
 
 import oracle_binding as orc
 import quant_common as qc
+from dnn_common import *  # noqa: F401,F403 (re-exported: the tests reach every shared name through this module)
+from dnn_common import share
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-F32, BF16 = 1, 2
-FMT_LIBXSMM, FMT_NHWC, FMT_NCHW, FMT_RSCK, FMT_KCRS, FMT_CKPACKED, FMT_NCPACKED = 1, 2, 4, 8, 16, 64, 128
-FWD, BWD, UPD, BWDUPD, ALL = 0, 1, 2, 3, 4
-REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, REG_FIL, GRAD_FIL = 0, 3, 5, 6, 10, 12
+FMT_RSCK, FMT_KCRS, FMT_CKPACKED, FMT_NCPACKED = 8, 16, 64, 128
+GRAD_FIL = 12
 TENSOR_TYPES = (REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, REG_FIL, GRAD_FIL)
-DIM_N, DIM_H, DIM_W, DIM_C, DIM_K, DIM_R, DIM_S = 0, 1, 2, 3, 4, 5, 6
+DIM_K, DIM_R, DIM_S = 4, 5, 6
 TENSOR_FILTER = 13  # LIBXSMM_DNN_FILTER: what a filter layout's tensor_type says
 
-SUCCESS = 0
 WARN_N, WARN_C, WARN_K = 90004, 90005, 90006
-ERR_GENERAL, ERR_CREATE_HANDLE, ERR_UNSUPPORTED_DATATYPE, ERR_INVALID_HANDLE, ERR_DATA_NOT_BOUND = 100000, 100001, 100002, 100004, 100005
-ERR_MISMATCH_TENSOR, ERR_INVALID_KIND, ERR_UNSUPPORTED_DST_FORMAT, ERR_UNSUPPORTED_SRC_FORMAT = 100008, 100010, 100012, 100013
-ERR_INVALID_FORMAT_GENERAL, ERR_SCRATCH_NOT_ALLOCED, ERR_UNKNOWN_TENSOR_TYPE, ERR_FUSION, ERR_INVALID_FORMAT_FC = 100016, 100020, 100021, 100031, 100034
+ERR_CREATE_HANDLE, ERR_UNSUPPORTED_DST_FORMAT, ERR_UNSUPPORTED_SRC_FORMAT, ERR_FUSION, ERR_INVALID_FORMAT_FC = 100001, 100012, 100013, 100031, 100034
 
 
 def desc(N, C, K, fmt="L", dt="f32", bn=0, bk=0, bc=0, threads=1, fuse=0):
@@ -106,9 +101,6 @@ class Handle:
         N, C, K = d["N"], d["C"], d["K"]
         inp, out, fil = t in (REG_IN, GRAD_IN), t in (REG_OUT, GRAD_OUT), t in (REG_FIL, GRAD_FIL)
 
-        def made(types, sizes, datatype, fmt, ttype=0):
-            return SUCCESS, dict(num_dims=len(types), dim_type=list(types), dim_size=[int(s) for s in sizes], datatype=datatype, format=fmt,
-                                 custom_format=1, tensor_type=ttype)
         if inp or out:
             fmt = d["buffer_format"]
             if fmt & FMT_LIBXSMM:
@@ -173,16 +165,7 @@ class Handle:
         return {FWD: K // bk, BWD: C // bc, UPD: (C // bc) * (K // bk)}[kind]
 
     def share(self, kind, ltid):
-        work, threads = self.work(kind), self.d["threads"]
-        chunk = work // threads if work % threads == 0 else work // threads + 1
-        return min(ltid * chunk, work), min((ltid + 1) * chunk, work)
-
-
-def layout_size(l):
-    n = 1
-    for s in l["dim_size"]:
-        n *= s
-    return n * {F32: 4, BF16: 2}[l["datatype"]], n
+        return share(self.work(kind), self.d["threads"], ltid)
 
 
 # ---- blocking: plain [N][C], [N][K], [K][C] <-> the tensors' layouts ---------------------------------------------------------------

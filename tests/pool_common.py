@@ -7,21 +7,14 @@ import zlib
 
 import numpy as np
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+from dnn_common import *  # noqa: F401,F403 (re-exported: the tests reach every shared name through this module)
+from dnn_common import FmHandle, fma
 
-F32, BF16, I32, I16 = 1, 2, 4, 5
-FMT_LIBXSMM, FMT_NHWC, FMT_NCHW = 1, 2, 4
-FWD, BWD, UPD, BWDUPD, ALL = 0, 1, 2, 3, 4
 MAX, AVG = 1, 2
-REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, GEN_IN, GEN_OUT, REG_FIL, MASK = 0, 3, 5, 6, 7, 8, 10, 31
+MASK = 31
 BINDABLE = (REG_IN, GRAD_IN, REG_OUT, GRAD_OUT, MASK)
 LAYOUT_TYPES = BINDABLE + (GEN_IN, GEN_OUT, REG_FIL)  # the layouts the capture asks for (the last one is no pooling tensor)
-DIM_N, DIM_H, DIM_W, DIM_C = 0, 1, 2, 3
-
-SUCCESS = 0
-ERR_GENERAL, ERR_UNSUPPORTED_DATATYPE, ERR_INVALID_HANDLE, ERR_DATA_NOT_BOUND = 100000, 100002, 100004, 100005
-ERR_MISMATCH_TENSOR, ERR_INVALID_HANDLE_TENSOR, ERR_INVALID_KIND, ERR_INVALID_FORMAT_GENERAL = 100008, 100009, 100010, 100016
-ERR_SCRATCH_NOT_ALLOCED, ERR_UNKNOWN_TENSOR_TYPE, ERR_INVALID_FORMAT_FUSEDBN, ERR_UNSUPPORTED_POOLING = 100020, 100021, 100032, 100033
+ERR_UNSUPPORTED_POOLING = 100033
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 SENTINEL = -1  # what the mask is pre-filled with: FWD leaves it where no input exceeded -FLT_MAX
@@ -104,68 +97,29 @@ def _cdiv(a, b):
 
 
 # ---- handle rules (src/libxsmm_dnn_pooling.c:44-95, src/libxsmm_dnn_setup.c:197-252) -------------------------------------------
-class Handle:
+class Handle(FmHandle):
     def __init__(self, d):
-        self.d = d
-        self.ok = False
-        pair = (d["datatype_in"], d["datatype_out"])
-        if pair not in ((F32, F32), (BF16, BF16)):
-            self.status = ERR_UNSUPPORTED_DATATYPE
+        super().__init__(d)
+        if self.status != SUCCESS:
             return
-        self.status = SUCCESS
-        self.f32 = pair == (F32, F32)
-        Cc = d["C"]
-        if self.f32:
-            self.ifmblock, self.fm_lp_block = (16 if Cc >= 16 else Cc), 1
-        else:
-            self.ifmblock, self.fm_lp_block = (8 if Cc >= 16 else Cc // 2), 2
-            if Cc == 3:
-                self.ifmblock, self.fm_lp_block = 3, 1
-        self.ofmblock = 16
-        self.ifmblock_hp, self.ofmblock_lp = self.ifmblock * self.fm_lp_block, self.ofmblock // self.fm_lp_block
-        self.blocksifm = Cc // (self.ifmblock if self.f32 else self.ifmblock_hp)
-        self.blocksofm = Cc // self.ofmblock
-        self.ofh = _cdiv(d["H"] + 2 * d["pad_h"] - d["R"], d["u"]) + 1
-        self.ofw = _cdiv(d["W"] + 2 * d["pad_w"] - d["S"], d["v"]) + 1
+        self.set_output(_cdiv(d["H"] + 2 * d["pad_h"] - d["R"], d["u"]) + 1, _cdiv(d["W"] + 2 * d["pad_w"] - d["S"], d["v"]) + 1)
         self.scratch_size = 4 * (d["H"] + 2 * max(d["pad_h_in"], d["pad_h_out"])) * (d["W"] + 2 * max(d["pad_w_in"], d["pad_w_out"])) \
             * max(self.ofmblock, self.ifmblock) * d["threads"]
-        self.ifhp, self.ifwp = d["H"] + 2 * d["pad_h_in"], d["W"] + 2 * d["pad_w_in"]
-        self.ofhp, self.ofwp = self.ofh + 2 * d["pad_h_out"], self.ofw + 2 * d["pad_w_out"]
         self.ok = True
-
-    def scratch(self):
-        return self.scratch_size + 64
 
     def layout(self, t):
         """(status, None) or (0, dict) as libxsmm_dnn_pooling_create_tensor_datalayout (:114-291)"""
         d = self.d
-        inp, out, mask = t in (REG_IN, GRAD_IN, GEN_IN), t in (REG_OUT, GRAD_OUT, GEN_OUT), t == MASK
-        fmt = d["buffer_format"]
-
-        def made(types, sizes, datatype):
-            return SUCCESS, dict(num_dims=len(types), dim_type=list(types), dim_size=[int(s) for s in sizes], datatype=datatype, format=fmt,
-                                 custom_format=1, tensor_type=0)
-        if not (inp or out or mask):
+        inp, out, fmt = t in (REG_IN, GRAD_IN, GEN_IN), t in (REG_OUT, GRAD_OUT, GEN_OUT), d["buffer_format"]
+        if inp or out:
+            return self.activation_layout(inp)
+        if t != MASK:
             return ERR_UNKNOWN_TENSOR_TYPE, None
-        if fmt & FMT_LIBXSMM:
-            if mask:  # always five dimensions over (ofw, ofh), without physical padding
-                return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), (self.ofmblock, self.ofw, self.ofh, self.blocksofm, d["N"]), d["datatype_mask"])
-            if self.f32:
-                sizes = (self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp else (self.ofmblock, self.ofwp, self.ofhp, self.blocksofm, d["N"])
-                return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, F32)
-            sizes = (self.fm_lp_block, self.ifmblock, self.ifwp, self.ifhp, self.blocksifm, d["N"]) if inp \
-                else (self.fm_lp_block, self.ofmblock_lp, self.ofwp, self.ofhp, self.blocksofm, d["N"])
-            return made((DIM_C, DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), sizes, BF16)
-        if fmt & FMT_NHWC:
-            if mask:  # (the reference sets the mask's datatype to datatype_in and then has no sizes for it)
-                return ERR_UNKNOWN_TENSOR_TYPE, None
-            sizes = (d["C"], self.ifwp, self.ifhp, d["N"]) if inp else (d["C"], self.ofwp, self.ofhp, d["N"])
-            return made((DIM_C, DIM_W, DIM_H, DIM_N), sizes, d["datatype_in"])
+        if fmt & FMT_LIBXSMM:  # always five dimensions over (ofw, ofh), without physical padding
+            return made((DIM_C, DIM_W, DIM_H, DIM_C, DIM_N), (self.ofmblock, self.ofw, self.ofh, self.blocksofm, d["N"]), d["datatype_mask"], fmt)
+        if fmt & FMT_NHWC:     # (the reference sets the mask's datatype to datatype_in and then has no sizes for it)
+            return ERR_UNKNOWN_TENSOR_TYPE, None
         return ERR_INVALID_FORMAT_GENERAL, None
-
-    def runnable(self):
-        """the channel block is the 16 the kernels are written for, on both sides"""
-        return self.ifmblock_hp == 16 and self.blocksifm == self.blocksofm
 
     def execute_status(self, kind, bound, ltid=0):
         """what execute_st returns before anything is computed (bound: the tensor types that are bound). Up to
@@ -188,51 +142,8 @@ class Handle:
             return ERR_GENERAL
         return SUCCESS
 
-    def work(self):
-        return self.d["N"] * self.blocksifm
-
-    def share(self, ltid):
-        work, threads = self.work(), self.d["threads"]
-        chunk = work // threads if work % threads == 0 else work // threads + 1
-        return min(ltid * chunk, work), min((ltid + 1) * chunk, work)
-
-    # shapes of the blocked tensors as arrays [item][row][column][16]
-    def in_shape(self):
-        return (self.work(), self.ifhp, self.ifwp, 16)
-
-    def out_shape(self):
-        return (self.work(), self.ofhp, self.ofwp, 16)
-
     def mask_shape(self):
         return (self.work(), self.ofh, self.ofw, 16)
-
-
-def layout_size(l):
-    n = 1
-    for s in l["dim_size"]:
-        n *= s
-    return n * {F32: 4, BF16: 2, I32: 4, I16: 2}[l["datatype"]], n
-
-
-# ---- 16-bit elements: widened by a shift, stored by truncation (the generic templates' union) -------------------------------------
-def widen(a):
-    return (np.asarray(a, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def truncate(a):
-    return (np.ascontiguousarray(a, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def as_f32(h, a):
-    return a if h.f32 else widen(a)
-
-
-def stored(h, a):
-    return a.astype(np.float32) if h.f32 else truncate(a)
-
-
-def elem_dtype(h):
-    return np.float32 if h.f32 else np.uint16
 
 
 # ---- inputs: seeded, in the tensors' own layout (physical padding included: it is never read) -----------------------------------
@@ -299,12 +210,6 @@ def forward(h, x, out, mask=None):
     out[:, oph:oph + h.ofh, opw:opw + h.ofw, :] = stored(h, res)
 
 
-def _fma(a, b, c):
-    """fp32 fma of arrays through float64: the product is exact there; the sum is rounded twice (to 53, then 24 bits), which
-    differs from one rounding only in rare halfway cases -- good enough to tell the fused form from the separate one"""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-
-
 def backward(h, dout, mask, din, fused=False):
     """BWD into the interior of the pre-filled din (element type), in place. Per input element the contributions arrive with ho
     ascending, then wo ascending -- the order of the reference's scatter and of the engine's gather -- from +0.0.
@@ -333,7 +238,7 @@ def backward(h, dout, mask, din, fused=False):
                 if a0 < a1 and b0 < b1:
                     t = g[:, ho, wo, :][:, None, None, :]
                     part = acc[:, a0:a1, b0:b1, :]
-                    acc[:, a0:a1, b0:b1, :] = _fma(np.broadcast_to(t, part.shape), recp, part) if fused else part + t * recp
+                    acc[:, a0:a1, b0:b1, :] = fma(np.broadcast_to(t, part.shape), recp, part) if fused else part + t * recp
     din[:, iph:iph + H, ipw:ipw + W, :] = stored(h, acc)
 
 
@@ -352,10 +257,6 @@ def expected(name, d, fused=False):
     forward(h, x, out, mask)
     backward(h, dout, mask, din, fused)
     return dict(x=x, dout=dout, out=out, mask=mask, din=din)
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
 def load_golden():

@@ -260,3 +260,24 @@ def test_pageable_tensors_complete_on_return(xs, torch_gpu, name):
     assert 0 == layer.run(bc.BWD)
     layer.check(ALL_KEYS)
     layer.close()
+
+
+@pytest.mark.parametrize("name", ("pad_f32_n", "fuse13_bf16_n"))
+def test_mixed_residency_complete_on_return(xs, torch_gpu, name):
+    """only what a pass writes in pageable host memory and what it reads on the device, then the reverse: the one staging block
+    skips the device-resident operands and still places the others"""
+    L = xs.lib()
+    d = bc.COMPUTE_CASES[name]
+    h, want = bc.Handle(d), case_data(name)
+    key_of = {t: key for key, t in bc.KEYS.items()}
+    between = after_fwd(want)
+    start = dict(between, **{key: bc.filled(want[key].shape, want[key].dtype) for key in bc.written(d, bc.FWD)})
+    for kind, before, after in ((bc.FWD, start, between), (bc.BWD, between, want)):
+        roles = {key_of[t]: (before[key_of[t]], after[key_of[t]], key_of[t] in bc.written(d, kind)) for t in h.needed(kind)}
+        for host_written in (True, False):
+            handle, _ = xs.bn_create(*[d[k] for k in bc.DESC_FIELDS])
+            tensors = bc.check_mixed_residency(torch_gpu, roles, host_written, lambda key, m: xs.bn_bind_new(handle, bc.KEYS[key], m),
+                                               lambda: xs.bn_execute(handle, kind))
+            for t in tensors:
+                L.libxsmm_dnn_destroy_tensor(t)
+            assert 0 == L.libxsmm_dnn_destroy_fusedbatchnorm(handle)

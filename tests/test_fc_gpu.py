@@ -225,6 +225,30 @@ def test_pageable_tensors_complete_on_return(xs, orc, torch_gpu, tile_env):
         L.libxsmm_dnn_destroy_fullyconnected(handle)
 
 
+def test_mixed_residency_complete_on_return(xs, orc, torch_gpu, tile_env):
+    """only what a pass writes in pageable host memory and what it reads on the device, then the reverse: the one staging block
+    skips the device-resident operands and still places the others"""
+    L = xs.lib()
+    reads = {fc.FWD: (fc.REG_FIL, fc.REG_IN), fc.BWD: (fc.REG_FIL, fc.GRAD_OUT), fc.UPD: (fc.GRAD_OUT, fc.REG_IN)}
+    for name in ("l_5_32_48", "b_7_10_9"):
+        h, _, want = case_data(name)
+        d = fc.COMPUTE_CASES[name]
+        scratch = np.zeros(h.scratch(), dtype=np.uint8)
+        for kind in (fc.FWD, fc.BWD, fc.UPD):
+            after = {t: want[t].astype(fc.dtype_of(h, t)) for t in reads[kind] + (DEST[kind],)}
+            roles = {t: (after[t], after[t], False) for t in reads[kind]}
+            roles[DEST[kind]] = (np.full_like(after[DEST[kind]], 0xffff if after[DEST[kind]].dtype == np.uint16 else np.nan), after[DEST[kind]], True)
+            for host_written in (True, False):
+                handle, _ = xs.fc_create(d["N"], d["C"], d["K"], d["bn"], d["bk"], d["bc"], 1, d["datatype_in"], d["datatype_out"], d["buffer_format"], d["filter_format"])
+                assert 0 == L.libxsmm_dnn_fullyconnected_bind_scratch(handle, xs.dptr(scratch))
+                tensors = fc.check_mixed_residency(torch_gpu, roles, host_written, lambda t, m: xs.fc_bind_new(handle, t, m),
+                                                   lambda: xs.fc_execute(handle, kind))
+                for t in tensors:
+                    L.libxsmm_dnn_destroy_tensor(t)
+                L.libxsmm_dnn_destroy_fullyconnected(handle)
+        assert not scratch.any()
+
+
 def test_copyin_copyout_round_trip_on_a_device_tensor(xs, orc, torch_gpu, tile_env):
     torch = torch_gpu
     L = xs.lib()

@@ -250,3 +250,28 @@ def test_pageable_tensors_complete_on_return(xs, torch_gpu):
         for t in tensors:
             L.libxsmm_dnn_destroy_tensor(t)
         L.libxsmm_dnn_destroy_pooling(handle)
+
+
+def test_mixed_residency_complete_on_return(xs, torch_gpu):
+    """only what a pass writes in pageable host memory and what it reads on the device, then the reverse: the one staging block
+    skips the device-resident operands and still places the others"""
+    L = xs.lib()
+    for name in ("a_max_f32_n", "a_avg_bf16_n"):
+        d = pc.COMPUTE_CASES[name]
+        h, want = pc.Handle(d), case_data(name)
+        ones = {k: np.full_like(want[k], 0) for k in ("out", "din")}
+        for a in ones.values():
+            a.view(np.uint8)[...] = 0xff
+        fwd = {pc.REG_IN: (want["x"], want["x"], False), pc.REG_OUT: (ones["out"], want["out"], True)}
+        bwd = {pc.GRAD_OUT: (want["dout"], want["dout"], False), pc.GRAD_IN: (ones["din"], want["din"], True)}
+        if d["pooling_type"] == pc.MAX:
+            fwd[pc.MASK] = (np.full(h.mask_shape(), pc.SENTINEL, dtype=np.int32), want["mask"], True)
+            bwd[pc.MASK] = (want["mask"], want["mask"], False)
+        for kind, roles in ((pc.FWD, fwd), (pc.BWD, bwd)):
+            for host_written in (True, False):
+                handle, _ = xs.pool_create(*[d[k] for k in pc.DESC_FIELDS])
+                tensors = pc.check_mixed_residency(torch_gpu, roles, host_written, lambda t, m: xs.pool_bind_new(handle, t, m),
+                                                   lambda: xs.pool_execute(handle, kind))
+                for t in tensors:
+                    L.libxsmm_dnn_destroy_tensor(t)
+                L.libxsmm_dnn_destroy_pooling(handle)
