@@ -3,10 +3,12 @@
  * 311-346, src/libxsmm_dnn.c:70-189, :330-360, :1000-1570), and the producers of low-precision GEMM inputs: fp32 -> int16
  * quantisation, its inverse and the fp32 <-> bf16 converters (:331-357 and :414-426, src/libxsmm_dnn.c:2394-2907). The layer
  * that uses the tensor handles is the fully-connected one (libxsmm_dnn_fullyconnected.h); the pooling layer and the fused
- * batch-norm layer have headers of their own (libxsmm_dnn_pooling.h, libxsmm_dnn_fusedbatchnorm.h). The convolution and RNN
- * entry points of the reference are not provided, nor are the descriptors and enumerations only they use. The common part lies in libxsmm_dnn_tensor.h, a file of this project's that this header includes (the
- * reference keeps it in libxsmm_dnn.h itself); the quantisation and conversion functions are declared below. Line numbers
- * refer to the reference's include/libxsmm_dnn.h unless a file is named.
+ * batch-norm layer have headers of their own (libxsmm_dnn_pooling.h, libxsmm_dnn_fusedbatchnorm.h). The convolution layer
+ * (:265-329 and :364-412) is declared in libxsmm_dnn_convolution.h, a file of this project's that this header includes. The RNN
+ * entry points of the reference are not provided, nor are the descriptors and enumerations only they use. The
+ * common part lies in libxsmm_dnn_tensor.h, another file of this project's that this header includes (the reference keeps both
+ * in libxsmm_dnn.h itself); the quantisation and conversion functions are declared below. Line numbers refer to the
+ * reference's include/libxsmm_dnn.h unless a file is named.
  *
  * Where operands may live: memory the GPU reaches (device, pinned, managed) is processed in place on the calling thread's
  * stream (libxsmm_amd_set_stream); host-visible memory (pinned, managed) is complete on return; pageable host memory is
@@ -18,6 +20,7 @@
 #include "libxsmm.h"
 
 #include "libxsmm_dnn_tensor.h" /* error codes, data types, formats, datalayouts and tensor handles */
+#include "libxsmm_dnn_convolution.h" /* the convolution layer */
 
 typedef union libxsmm_intfloat { unsigned int ui; float f; } libxsmm_intfloat; /* :334-337 */
 

@@ -98,6 +98,12 @@ class FusedBatchnormDesc(C.Structure):  # libxsmm_dnn_fusedbatchnorm_desc
                                        "datatype_out", "datatype_stats", "buffer_format", "fuse_order", "fuse_ops")]
 
 
+class ConvDesc(C.Structure):  # libxsmm_dnn_conv_desc
+    _fields_ = [(n, C.c_int) for n in ("N", "C", "H", "W", "K", "R", "S", "u", "v", "pad_h", "pad_w", "pad_h_in", "pad_w_in", "pad_h_out", "pad_w_out",
+                                       "threads", "datatype_in", "datatype_out", "buffer_format", "filter_format", "algo", "options", "fuse_ops")] \
+        + [("pre_bn", C.c_void_p), ("post_bn", C.c_void_p)]
+
+
 def build(verbose=False):
     """Compile csrc/ into lib/libxsmm.so for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
@@ -417,6 +423,23 @@ def _declare(L):
     sig("libxsmm_dnn_fusedbatchnorm_get_tensor", vp, vp, i, up)
     sig("libxsmm_dnn_fusedbatchnorm_release_tensor", u, vp, i)
     sig("libxsmm_dnn_fusedbatchnorm_execute_st", u, vp, i, i, i)
+    # the convolution layer (include/libxsmm_dnn_convolution.h)
+    sig("libxsmm_dnn_create_conv_layer", vp, ConvDesc, up)
+    sig("libxsmm_dnn_destroy_conv_layer", u, vp)
+    sig("libxsmm_dnn_create_tensor_datalayout", lp, vp, i, up)
+    sig("libxsmm_dnn_trans_reg_filter", u, vp)
+    sig("libxsmm_dnn_get_scratch_size", C.c_size_t, vp, i, up)
+    sig("libxsmm_dnn_bind_scratch", u, vp, i, vp)
+    sig("libxsmm_dnn_release_scratch", u, vp, i)
+    sig("libxsmm_dnn_bind_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_get_tensor", vp, vp, i, up)
+    sig("libxsmm_dnn_release_tensor", u, vp, i)
+    sig("libxsmm_dnn_execute", None, vp, i)
+    sig("libxsmm_dnn_execute_st", u, vp, i, i, i)
+    sig("libxsmm_dnn_transpose_filter", u, vp, i)
+    sig("libxsmm_dnn_reduce_wu_filters", u, vp, i)
+    sig("libxsmm_dnn_get_codegen_success", u, vp, i)
+    sig("libxsmm_dnn_get_parallel_tasks", u, vp, i, up)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -1033,3 +1056,49 @@ def bn_bind_new(handle, ttype, data):
 def bn_execute(handle, kind, start_thread=0, tid=0):
     """libxsmm_dnn_fusedbatchnorm_execute_st; returns the status"""
     return lib().libxsmm_dnn_fusedbatchnorm_execute_st(handle, kind, start_thread, tid)
+
+
+# ---- the convolution layer (include/libxsmm_dnn_convolution.h) ---------------------------------------------------------------------
+DNN_REGULAR_FILTER_TRANS, DNN_REGULAR_CHANNEL_BIAS, DNN_GRADIENT_CHANNEL_BIAS = 11, 14, 15
+DNN_CONV_FUSE_BIAS, DNN_CONV_FUSE_RELU_FWD, DNN_CONV_FUSE_RELU_BWD, DNN_CONV_FUSE_RELU = 1, 2, 4, 6
+DNN_CONV_OPTION_OVERWRITE, DNN_CONV_OPTION_BWD_NO_FILTER_TRANSPOSE = 1, 8
+DNN_CONV_ALGO_AUTO, DNN_CONV_ALGO_DIRECT = 0, 1
+
+
+def conv_create(N, Cc, H, W, K, R, S, u=1, v=1, pad_h=0, pad_w=0, pad_h_in=0, pad_w_in=0, pad_h_out=0, pad_w_out=0, threads=1, datatype_in=DNN_F32,
+                datatype_out=DNN_F32, buffer_format=DNN_FORMAT_LIBXSMM, filter_format=DNN_FORMAT_LIBXSMM, algo=DNN_CONV_ALGO_DIRECT, options=0,
+                fuse_ops=0, pre_bn=None, post_bn=None):
+    """libxsmm_dnn_create_conv_layer; returns (handle or None, status)"""
+    st = C.c_uint(0xdead)
+    desc = ConvDesc(N, Cc, H, W, K, R, S, u, v, pad_h, pad_w, pad_h_in, pad_w_in, pad_h_out, pad_w_out, threads, datatype_in, datatype_out,
+                    buffer_format, filter_format, algo, options, fuse_ops, pre_bn, post_bn)
+    h = lib().libxsmm_dnn_create_conv_layer(desc, C.byref(st))
+    return h, st.value
+
+
+def conv_layout(handle, ttype):
+    """libxsmm_dnn_create_tensor_datalayout; returns (pointer or None, status). The caller destroys the layout."""
+    st = C.c_uint(0xdead)
+    l = lib().libxsmm_dnn_create_tensor_datalayout(handle, ttype, C.byref(st))
+    return (l if l else None), st.value
+
+
+def conv_bind_new(handle, ttype, data):
+    """layout of ttype, a tensor linked to data, bound to the handle; returns the tensor handle (the caller destroys it)"""
+    L = lib()
+    l, st = conv_layout(handle, ttype)
+    if l is None:
+        raise RuntimeError("no layout: status %d" % st)
+    t, st = dnn_link_tensor(l, data)
+    L.libxsmm_dnn_destroy_tensor_datalayout(l)
+    if not t:
+        raise RuntimeError("link failed: status %d" % st)
+    st = L.libxsmm_dnn_bind_tensor(handle, t, ttype)
+    if 0 != st:
+        raise RuntimeError("bind failed: status %d" % st)
+    return t
+
+
+def conv_execute(handle, kind, start_thread=0, tid=0):
+    """libxsmm_dnn_execute_st; returns the status"""
+    return lib().libxsmm_dnn_execute_st(handle, kind, start_thread, tid)

@@ -47,6 +47,27 @@ int launch_bn_partial(const BnArgs& args, void* stream, const char** name); // s
 int launch_bn_finish(const BnArgs& args, void* stream, const char** name);  // stats only: images in order; mean / rstd / var or dgamma / dbeta
 int launch_bn_apply(const BnArgs& args, void* stream, const char** name);   // the items [w0, w1)
 
+// convolution layer (xsmm_dnn_conv.cpp, kernels/conv.hip): activations [image][block][row][column][block size], filter
+// [ofm1][ifm1][kj][ki][ifm2][ofm2] (trans: [ifm1][ofm1][R-1-kj][S-1-ki][ofm2][ifm2]); every tensor has fewer than 2^31 elements
+struct ConvArgs {
+  void* in; void* out; void* flt; void* bias; // input / dinput, output / doutput, filter / dfilter, bias (FWD with bias_on)
+  int N, C, K, H, W, R, S, u, v, pad_h, pad_w;
+  int ifmblock, ofmblock, blocksifm, blocksofm;
+  int ifhp, ifwp, ofh, ofw, ofhp, ofwp, oph, opw; // padded extents; physical padding of the output
+  int logical;                            // pad_*_in == 0 with a pad_* > 0: the rim is not in memory
+  int w0, w1;                             // the share: items img * blocksofm + ofm1 (FWD), img * blocksifm + ifm1 (BWD), ofm1 * blocksifm + ifm1 (UPD)
+  int overwrite, bias_on, relu;           // OPTION_OVERWRITE; FWD: FUSE_BIAS, fuse_ops & FUSE_RELU
+  int flt_trans;                          // BWD: flt is REGULAR_FILTER_TRANS
+  int per_image;                          // UPD: the form with one chain per image and ordered adds
+  int tile;                               // FWD: 64 or 128
+};
+// one pass over the share, or the transposition of the whole filter (in: REGULAR_FILTER, out: REGULAR_FILTER_TRANS in g.flt / g.out);
+// each returns hipError_t as int
+int launch_conv_fwd(const ConvArgs& args, void* stream, const char** name);
+int launch_conv_bwd(const ConvArgs& args, void* stream, const char** name);
+int launch_conv_upd(const ConvArgs& args, void* stream, const char** name);
+int launch_conv_trans_filter(const ConvArgs& args, void* stream, const char** name);
+
 // ---- what the layers share on the host (xsmm_dnn_layer.cpp) ---------------------------------------------------------------
 // A layer provides slot_of(handle*, type) at global scope (the tensor pointer a type binds; nullptr for a type it does not
 // bind), its create_tensor_datalayout and its execute_st; the rest of its API forwards to the templates below.
