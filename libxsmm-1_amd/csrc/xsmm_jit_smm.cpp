@@ -8,6 +8,7 @@
 //     size allows) one item ahead of the arithmetic, parked in wave-private LDS, and C leaves the same way;
 //   * 8x8 lanes, TM x TN register tile, v_fma in ascending k: the reference's per-element chain, bit for bit.
 #include "xsmm_internal.hpp"
+#include "kernels/smm_jit_geom.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -22,6 +23,7 @@
 namespace xsmm {
 
 extern const char* const SMM_MFMA_WG_SOURCE; // kernels/smm_mfma_wg.inc as text (Makefile)
+extern const char* const SMM_JIT_GEOM_SOURCE; // kernels/smm_jit_geom.h as text: DevAddr and the LDS geometry, in front of every generated kernel
 
 namespace {
 
@@ -31,14 +33,7 @@ const char* const SMM_JIT_PRELUDE = R"XSMM(
 #else
 #define XGLOBAL __attribute__((address_space(1)))
 #endif
-// ---- batch addressing (same structure and meaning as kernels/smm_common.cuh) ----
-struct DevAddr {
-  const char* a; const char* b; char* c;
-  const char* ia; const char* ib; const char* ic;
-  long long sa, sb, sc;
-  int index_base, index_stride, mode;
-  const int* flags; // device-side verdict on how C blocks repeat: [0] equal neighbours, [1] out-of-order repeats (or null)
-};
+// ---- batch addressing (DevAddr: kernels/smm_jit_geom.h) ----
 template<typename P> __device__ __forceinline__ P* resolve(const char* base, const char* idx, long long stride, const DevAddr& ad, long long i)
 {
   if (0 == ad.mode) return (P*)base + i * stride;
@@ -75,40 +70,28 @@ constexpr int AE1 = LDA * (K - 1) + M, BE1 = XTRANSB ? (LDB * (K - 1) + N) : (LD
 constexpr int CT1 = M * N;                                          // tight C image of one item
 constexpr int AE = G * AE1, BE = G * BE1, CE = G * CE1;            // ... of what a wave handles at a time (G > 1: tight only)
 constexpr int TS = (int)sizeof(T);
+// lane tiles and LDS images: geom::tiled (kernels/smm_jit_geom.h), the numbers the host sizes the launch with
+constexpr geom::Tiled GEO = geom::tiled(TS, M, N, K, 0 != XTRANSB, G, XRUNS);
 #if (2 == XRUNS)
 // work-group form: 4 waves share one product; a wave owns NQ = ceil(N/4) columns of C, its 64 lanes are 16 (along m) x 4
 constexpr int UT = 256;                                            // threads that stream one item's operands
-constexpr int TGM = 16, TGN = 4;
-constexpr int NQ = (N + 3) / 4;
-constexpr int TM = (M + TGM - 1) / TGM, TN = (NQ + TGN - 1) / TGN;
-constexpr int NPAD = 3 * NQ + TGN * TN;                            // highest column index a lane may touch, plus one
+constexpr int NQ = GEO.nq;
 #else
 // wave form: one wave per item, 8 x 8 lanes (XPACK items: 64 / XPACK lanes each)
 constexpr int UT = 64;
-constexpr int TGM = (G >= 4) ? ((G >= 16) ? 2 : 4) : 8, TGN = 64 / (G * TGM);
-constexpr int TM = (M + TGM - 1) / TGM, TN = (N + TGN - 1) / TGN;
-constexpr int NPAD = TGN * TN;
 #endif
+constexpr int TGM = GEO.tgm, TGN = GEO.tgn, TM = GEO.tm, TN = GEO.tn, NPAD = GEO.npad;
 // widest access (in elements) that every item of a strided batch is aligned for
 constexpr int vw(int elems) { return (0 == (elems * TS) % 16) ? 16 / TS : ((0 == (elems * TS) % 8) ? 8 / TS : 1); }
 // XSCALAR: index/pointer batches guarantee element alignment only
 constexpr int VA = XSCALAR ? 1 : vw(AE), VB = XSCALAR ? 1 : vw(BE), VC = (XSCALAR || !TIGHT_C) ? 1 : vw(CE);
 constexpr int NLA = (AE + UT * VA - 1) / (UT * VA), NLB = (BE + UT * VB - 1) / (UT * VB), NLC = (CE + UT * VC - 1) / (UT * VC);
-// LDS strides: A as [k][M] (lanes with equal ty read the same words, lanes with different tx adjacent ones);
-// B as [n][KP] (TRANS_B: [k][N]) with KP chosen so that the column groups of one instruction fall into different banks
-// (TN * TS / 4 a multiple of 16 -- fp64, eight columns per lane -- has no such stride: an odd one then)
-constexpr int pick_kp() { if (0 == (TN * (TS / 4)) % 16) return K | 1; int kp = K; while (0 == (TN * kp * (TS / 4)) % 16) ++kp; return kp; }
-constexpr int KP = pick_kp();
-constexpr int AS1 = ((K * M + TGM * TM + 3) / 4) * 4;                 // per item
-constexpr int BS1 = XTRANSB ? (((K * N + NPAD + 3) / 4) * 4) : ((NPAD * KP + 3) / 4) * 4;
+constexpr int KP = GEO.kp, AS1 = GEO.as1, BS1 = GEO.bs1;             // LDS, per item: A as [k][M], B as [n][KP] (TRANS_B: [k][N])
 constexpr int AS_SIZE = G * AS1, BS_SIZE = G * BS1;
-constexpr int CS_SIZE = ((G * CT1 + 3) / 4) * 4;                     // the items' C blocks stay contiguous (flat copy in and out)
-// (wave run form: C is in LDS only while a run is opened or closed, when no operand image is alive -- its image lies over theirs;
-// a third less LDS per wave is a third more chains resident per CU)
-constexpr bool C_OVER_AB = (1 == XRUNS);
-constexpr int WAVE_LDS = C_OVER_AB ? ((AS_SIZE + BS_SIZE > CS_SIZE) ? (AS_SIZE + BS_SIZE) : CS_SIZE) : (AS_SIZE + BS_SIZE + CS_SIZE); // elements (wave form)
-constexpr int WG_BUF = AS_SIZE + BS_SIZE;                            // elements per operand buffer (work-group form)
-constexpr int WG_NBUF = (2 * WG_BUF * TS <= 65536) ? 2 : 1;          // double-buffered when 64 KiB allow
+constexpr int CS_SIZE = GEO.cs;                                      // the items' C blocks stay contiguous (flat copy in and out)
+constexpr bool C_OVER_AB = (1 == XRUNS);                             // wave run form: C's image lies over the operands'
+constexpr int WAVE_LDS = GEO.wave_lds;                               // elements (wave form)
+constexpr int WG_BUF = GEO.wg_buf, WG_NBUF = GEO.wg_nbuf;            // elements per operand buffer (work-group form); two when 64 KiB allow
 
 template<int V> struct Vec { typedef T type __attribute__((ext_vector_type(V))); };
 template<> struct Vec<1> { typedef T type; };
@@ -809,19 +792,13 @@ __device__ __forceinline__ ACC64 xmfma(double a, double b, ACC64 c) { return __b
 constexpr bool F64 = (8 == TS);
 // K is padded to a multiple of four with A = -0 and B = +0: the product -0 is the identity of the addition for every sum,
 // signs of zeros included, so the chain stays the reference's bit for bit (as in kernels/smm_mfma_wg.inc)
-constexpr int MI = (M + 15) / 16, NI = (N + 15) / 16, KS = (K + 3) / 4, KP4 = 4 * KS;
-constexpr int MS = (M <= 16) ? 16 : (M <= 48 ? 48 : 64);
-constexpr bool ASWZ = (64 == MS);
-constexpr int kstride() { int s = ((KP4 + VEC - 1) / VEC); if (0 == (s & 1)) ++s; return s * VEC; }
-constexpr int KSD = kstride();
+constexpr int MI = (M + 15) / 16, NI = (N + 15) / 16, KP4 = geom::kp4(K), KS = KP4 / 4;
+// the LDS images: geom::mfma_wave (kernels/smm_jit_geom.h) -- the host passes its lds_bytes as the dynamic LDS of the launch
+constexpr geom::MfmaWave GEO = geom::mfma_wave(TS, M, N, K, VEC, 0 != XTRANSB);
 // TRANS_B (memory holds B^T: element (k, n) at k * ldb + n): the image is k-major like A's, [k][NS], fetched the same way
-constexpr int NS = (N <= 16) ? 16 : (N <= 48 ? 48 : 64);
-constexpr bool BSWZ = (64 == NS);
-// image of C: column stride such that the four column groups of a tile access fall into different banks
-constexpr int cstride() { int s = M; for (;; s += VEC) { if (F64 ? (16 == s % 32) : (4 == s % 16 || 12 == s % 16)) break; } return s; }
-constexpr int CSD = cstride();
-constexpr int C_ELEMS = N * CSD;
-constexpr int A_ELEMS = (C_ELEMS > KP4 * MS) ? C_ELEMS : KP4 * MS, B_ELEMS = XTRANSB ? KP4 * NS : N * KSD;
+constexpr int MS = GEO.ms, NS = GEO.ns, KSD = GEO.ksd, CSD = GEO.csd;
+constexpr bool ASWZ = (64 == MS), BSWZ = (64 == NS);
+constexpr int C_ELEMS = GEO.c_elems, A_ELEMS = GEO.a_elems, B_ELEMS = GEO.b_elems;
 #if XLOWP
 // bf16 inputs (XLOWP 3: fp32 result, 2: bf16 result) as the reference's low-precision kernels store them: A in pairs of k
 // (a[(k/2)*M*2 + m*2 + k%2]), B column-major -- both sequences of 32-bit k pairs. A 16-byte chunk is four pairs (A: four
@@ -849,7 +826,7 @@ constexpr int LDA = XLDA, LDB = XLDB, LDC = XLDC;
 constexpr bool TIGHT = (LDA == M && LDB == (XTRANSB ? N : K) && LDC == M);
 constexpr int NCA = (LDA * (K - 1) + M) / VEC, NCB = (XTRANSB ? (LDB * (K - 1) + N) : (LDB * (N - 1) + K)) / VEC, NCC = (LDC * (N - 1) + M) / VEC;
 typedef V UV;
-static_assert(1 == VEC || (TIGHT && 0 == M % VEC && 0 == K % 4 && (!XTRANSB || 0 == N % VEC)), "shape");
+static_assert((1 == VEC || TIGHT) && geom::mfma_wave_served(M, N, K, VEC, 0 != XTRANSB), "shape");
 #endif
 constexpr int CA = (NCA + 63) / 64, CB = (NCB + 63) / 64, CC = (NCC + 63) / 64;
 __device__ __forceinline__ int clampi(int v, int hi) { return v < hi ? v : hi; }
@@ -1031,12 +1008,13 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X
 // image into the accumulators, B is parked there, after the arithmetic the result waits there for the deferred stores. The
 // operands of the next half -- or the next item's A and first half -- are in flight meanwhile. A's image is tight (stride M:
 // two-way bank conflicts on its fetches, irrelevant next to 64-cycle fp64 matrix instructions).
+constexpr geom::MfmaWave2 GEO2 = geom::mfma_wave2(TS, M, N, K);
 constexpr int AMS = M;
 constexpr int NH = N / 2, NIH = (NH + 15) / 16;
 constexpr int CSH = M;
-constexpr int BH_ELEMS = (NH * KSD > NH * CSH) ? NH * KSD : NH * CSH;
+constexpr int BH_ELEMS = GEO2.bh_elems;
 constexpr int CBH = (K * NH / VEC + 63) / 64, CCH = (M * NH / VEC + 63) / 64;
-static_assert(0 == N % 2 && 0 == (K * NH) % VEC && 0 == (M * NH) % VEC && 0 == XLOWP, "shape");
+static_assert(geom::mfma_wave2_served(TS, M, N, K) && 16 == VEC * TS && K * AMS == GEO2.a_elems && 0 == XLOWP, "shape");
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(XWPE))) void xsmm_smm_op(DevAddr ad, long long batch, int runlen)
 {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -1180,18 +1158,14 @@ typedef float ACC32 __attribute__((ext_vector_type(4)));
 typedef double ACC64 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ ACC32 xmfma(float a, float b, ACC32 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ ACC64 xmfma(double a, double b, ACC64 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-// K goes through the registers and B's image in NCH chunks of KC (a multiple of four) -- one chunk up to K = 64; beyond that only the
-// streaming form (the run form keeps a whole product's fragments of A in flight)
-// (beyond 64 in chunks of at most 32: two chunk variants of fragments and address arithmetic alive at once cost registers)
-constexpr int NCH = (XSTREAM && K > 64) ? (K + 31) / 32 : 1;
-constexpr int KC = 4 * (((K + NCH - 1) / NCH + 3) / 4);
+// K goes through the registers and B's image in NCH chunks of KC (a multiple of four): geom::mfma_runs
+constexpr geom::MfmaRuns GEO = geom::mfma_runs(TS, N, K, 0 != XSTREAM); // (kernels/smm_jit_geom.h)
+constexpr int NCH = GEO.nch, KC = GEO.kc;
 constexpr int MI = (M + 15) / 16, NI = (N + 15) / 16, KS = KC / 4, KP4 = KC;
-// row stride of B's image: fp64 fragments are fetched sixteen lanes (one k, sixteen n) at a time -- an odd stride spreads them
-// over all bank pairs; fp32 fragments thirty-two lanes (two k) at a time -- a stride of 2 mod 4 keeps the two k apart as well
-constexpr int KSD = F64 ? (KP4 + 1) : (KP4 + 2);
+constexpr int KSD = GEO.ksd;                           // row stride of B's image
 constexpr int BE = LDB * (N - 1) + K;                  // span of B in memory
 constexpr int NLB = (1 == NCH) ? (BE + 63) / 64 : (N * KC + 63) / 64; // one chunk: the flat span; several: N x KC elements per chunk
-constexpr int WAVE_LDS = ((N * KSD + 3) / 4) * 4;      // elements
+constexpr int WAVE_LDS = GEO.wave_lds;                 // elements
 #define XNROW(r) (F64 ? (lq + 4 * (r)) : (4 * lq + (r)))
 __device__ __forceinline__ int clampi(int v, int hi) { return v < hi ? v : hi; }
 __device__ __forceinline__ void xatomic_add(double* p, double v) { (void)__builtin_amdgcn_global_atomic_fadd_f64((__attribute__((address_space(1))) double*)p, v); }
@@ -1537,32 +1511,11 @@ static long long knob(const char* name, long long dflt)
   return (nullptr != e && 0 != *e) ? atoll(e) : dflt;
 }
 
-// LDS bytes of a wave of that kernel (mirrors the constexpr arithmetic of the source); 0: the shape is not served
-static size_t smm_mfma_wave_lds(int typesize, int m, int n, int k, int vec = 0, bool transb = false)
-{ // vec: elements per memory access (0: a 16-byte chunk)
-  if (0 == vec) vec = 16 / typesize;
-  if (m > 64 || n > 64 || k > 64 || m < 1 || n < 1 || k < 1) return 0;
-  if (1 != vec && (0 != m % vec || 0 != k % 4)) return 0;
-  const int kp4 = 4 * ((k + 3) / 4);
-  const int ms = (m <= 16) ? 16 : (m <= 48 ? 48 : 64);
-  int ksd = (kp4 + vec - 1) / vec; if (0 == (ksd & 1)) ++ksd; ksd *= vec;
-  int csd = m; for (;; csd += vec) { if (8 == typesize ? (16 == csd % 32) : (4 == csd % 16 || 12 == csd % 16)) break; }
-  const int a_elems = (n * csd > kp4 * ms) ? n * csd : kp4 * ms;
-  const int ns = (n <= 16) ? 16 : (n <= 48 ? 48 : 64);
-  if (transb && 1 != vec && 0 != n % vec) return 0;
-  return (size_t)(a_elems + (transb ? kp4 * ns : n * ksd) + 64) * typesize;
-}
+// LDS bytes of a wave of that kernel (geom::mfma_wave, as the kernel lays them out); 0: the shape is not served
+static size_t smm_mfma_wave_lds(int typesize, int m, int n, int k, int vec = 0, bool transb = false) // vec: elements per memory access (0: a 16-byte chunk)
+{ return (size_t)geom::mfma_wave(typesize, m, n, k, (0 == vec) ? 16 / typesize : vec, transb).lds_bytes; }
 // ... of the form that works on the columns of C in two halves (0: not served)
-static size_t smm_mfma_wave2_lds(int typesize, int m, int n, int k)
-{
-  const int vec = 16 / typesize;
-  if (0 != m % vec || 0 != k % 4 || m > 64 || n > 64 || k > 64 || k < 4 || 0 != (n & 1)) return 0;
-  const int nh = n / 2;
-  if (0 != (k * nh) % vec || 0 != (m * nh) % vec) return 0;
-  int ksd = (k + vec - 1) / vec; if (0 == (ksd & 1)) ++ksd; ksd *= vec;
-  const int bh = (nh * ksd > nh * m) ? nh * ksd : nh * m;
-  return (size_t)(k * m + bh + 64) * typesize;
-}
+static size_t smm_mfma_wave2_lds(int typesize, int m, int n, int k) { return (size_t)geom::mfma_wave2(typesize, m, n, k).lds_bytes; }
 // waves per SIMD the kernel is compiled for: two where LDS leaves room for eight waves per CU, else one (the register file
 // then holds an item's operands, the next item's and the accumulators without spilling)
 static int smm_mfma_wave_wpe(size_t lds, int typesize = 0, int m = 0, int n = 0, int k = 0, int vec = 0, int lda = 0, int ldb = 0, int ldc = 0)
@@ -1580,16 +1533,9 @@ static int smm_mfma_wave_wpe(size_t lds, int typesize = 0, int m = 0, int n = 0,
   return 2;
 }
 
-// ---- the run form on the matrix cores (SMM_JIT_MFMA_RUNS_*): LDS bytes of a wave (mirrors the source); 0: shape not served
-static size_t smm_mfma_runs_lds(int typesize, int m, int n, int k, int ldb, bool stream = false)
-{ // stream: the streaming form (every item owns its C), which takes K beyond 64 in chunks
-  if (m < 1 || n < 1 || k < 1 || m > 32 || n > 32 || k > (stream ? 256 : 64) || (4 != typesize && 8 != typesize)) return 0;
-  if (ldb < k) ldb = k;
-  const int nch = (stream && k > 64) ? (k + 31) / 32 : 1;
-  if (1 == nch && (long long)ldb * (n - 1) + k > 64 * 40) return 0; // B's span travels through registers, an element per lane and load
-  const int kc = 4 * (((k + nch - 1) / nch + 3) / 4), ksd = (8 == typesize) ? kc + 1 : kc + 2;
-  return (size_t)(((n * ksd + 3) / 4) * 4) * typesize;
-}
+// ---- the run form on the matrix cores (SMM_JIT_MFMA_RUNS_*): LDS bytes of a wave (geom::mfma_runs); 0: shape not served
+static size_t smm_mfma_runs_lds(int typesize, int m, int n, int k, int ldb, bool stream = false) // stream: the streaming form (every item owns its C)
+{ return (size_t)geom::mfma_runs_lds_bytes(typesize, m, n, k, ldb, stream); }
 // products in flight per wave (register sets): as many as fit ~80 registers, four at most
 static int smm_mfma_runs_depth(int typesize, int m, int n, int k, int ldb, bool deep = false)
 { // deep: the tiles of a batch of few runs (smm_tile_split) -- a wave or two per SIMD, the registers are there
@@ -1624,38 +1570,19 @@ static bool smm_mfma_runs_ok(const SmmBatch& s, bool stream = false)
 }
 
 // ---- shapes with 32 < M or N <= 64: one work-group (256 threads, 16 x 16) per item, K in chunks of KC through LDS ------
+// (built behind SMM_JIT_PRELUDE with XFLAT 0: DevAddr, resolve, xfma)
 const char* const SMM_JIT_BIG_BODY = R"XSMM(
-#define XGLOBAL __attribute__((address_space(1)))
-struct DevAddr {
-  const char* a; const char* b; char* c;
-  const char* ia; const char* ib; const char* ic;
-  long long sa, sb, sc;
-  int index_base, index_stride, mode;
-  const int* flags;
-};
-template<typename P> __device__ __forceinline__ P* resolve(const char* base, const char* idx, long long stride, const DevAddr& ad, long long i)
-{
-  if (0 == ad.mode) return (P*)base + i * stride;
-  if (1 == ad.mode) { if (nullptr == idx) return (P*)base; const int v = *(const XGLOBAL int*)(idx + i * (long long)ad.index_stride); return (P*)base + ((long long)v - ad.index_base); }
-  return *(P* const XGLOBAL*)(base + i * stride);
-}
-__device__ __forceinline__ float xfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double xfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 // barrier that orders LDS traffic only (a work-group-scope fence would drain the prefetched global loads as well)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int M = XM, N = XN, K = XK, KC = XKC;
-constexpr int TM = (M + 15) / 16, TN = (N + 15) / 16;             // register tile of a thread (tx = t & 15 along m, ty = t >> 4 along n)
+constexpr geom::Big GEO = geom::big((int)sizeof(T), M, N, KC);    // (kernels/smm_jit_geom.h)
+constexpr int TM = GEO.tm, TN = GEO.tn;                            // register tile of a thread (tx = t & 15 along m, ty = t >> 4 along n)
 constexpr int NCH = (K + KC - 1) / KC;                             // k-chunks per item
 constexpr int AEL = KC * M, BEL = KC * N;                          // elements of one chunk
 constexpr int NLA = (AEL + 255) / 256, NLB = (BEL + 255) / 256;    // per thread
-constexpr int MP = 16 * TM, NP = 16 * TN;
-// LDS images of a chunk: A as [kk][MP], B as [kk][NPP]: a thread's TM resp. TN operands of one k are contiguous (one or two
-// 16-byte reads each). B arrives k-contiguous unless TRANS_B, so its LDS writes stride by a row; the 16-byte row padding
-// keeps that at a 4-way bank conflict on the (16x rarer) writes while the reads stay aligned.
-constexpr int NPP = NP + 16 / (int)sizeof(T);
-constexpr int AS = KC * MP, BS = KC * NPP;
-constexpr int BUF = ((AS + BS + 3) / 4) * 4;
+// LDS images of a chunk: A as [kk][MP], B as [kk][NPP] (a row padded by 16 bytes), two buffers of BUF elements
+constexpr int MP = GEO.mp, NP = GEO.np, NPP = GEO.npp, AS = GEO.as, BS = GEO.bs, BUF = GEO.buf;
 
 // chunk ch of one item: A rows k0..k0+KC (contiguous KC*M elements), B rows k0..k0+KC of every column (TRANS_B: contiguous)
 __device__ __forceinline__ void load_chunk(const T* pa, const T* pb, int ch, int t, T (&ra)[NLA], T (&rb)[NLB])
@@ -1820,12 +1747,7 @@ JitKernel* jit_resolve(MAP& table, const KEY& key, const char* fname, bool wait,
 static int smm_jit_waves(int typesize, int m, int n, int k, int flags, int pack = 1, bool runs = false);
 
 // k-chunk of the work-group-per-item form: the largest of 32/16/8 whose two LDS buffers fit 64 KiB (0: none does)
-static size_t smm_jit_big_buf(int typesize, int m, int n, int kc)
-{
-  const size_t mp = 16 * (size_t)((m + 15) / 16), np = 16 * (size_t)((n + 15) / 16);
-  const size_t as = (size_t)kc * mp, bs = (size_t)kc * (np + 16 / (size_t)typesize);
-  return ((as + bs + 3) / 4) * 4 * (size_t)typesize;
-}
+static size_t smm_jit_big_buf(int typesize, int m, int n, int kc) { return (size_t)geom::big(typesize, m, n, kc).buf * typesize; }
 static int smm_jit_big_kc(int typesize, int m, int n, int k)
 {
   for (int kc = 32; kc >= 8; kc /= 2) {
@@ -1873,13 +1795,13 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
     s += "#define XDEPTH " + std::to_string(smm_mfma_runs_depth(typesize, m, n, k, ldb)) + "\n";
     s += std::string("#define XSPLIT ") + ((variant & SMM_JIT_SPLIT) ? "1" : "0") + "\n";
     s += "#define XTILEWG 0\n";
-    s += SMM_JIT_PRELUDE; s += SMM_JIT_MFMA_RUNS_CONST; s += SMM_JIT_CHAIN; s += SMM_JIT_MFMA_RUNS_KERNEL;
+    s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE; s += SMM_JIT_MFMA_RUNS_CONST; s += SMM_JIT_CHAIN; s += SMM_JIT_MFMA_RUNS_KERNEL;
     return s;
   }
   if (0 != (variant & SMM_JIT_MFMA_WAVE2)) { // ... the columns of C in two halves
     s += "#define XFLAT 0\n#define XWPE 1\n#define XNSPLIT 2\n#define XVEC " + std::to_string(16 / typesize) + "\n";
     s += "#define XLDA " + std::to_string(m) + "\n#define XLDB " + std::to_string(k) + "\n#define XLDC " + std::to_string(m) + "\n";
-    s += SMM_JIT_PRELUDE;
+    s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
     s += SMM_JIT_MFMA_WAVE_BODY;
     return s;
   }
@@ -1889,7 +1811,7 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
     const bool wtb = (0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_B));
     s += "#define XLDA " + std::to_string(1 == wvec ? lda : m) + "\n#define XLDB " + std::to_string(1 == wvec ? ldb : (wtb ? n : k)) + "\n#define XLDC " + std::to_string(1 == wvec ? ldc : m) + "\n";
     s += "#define XFLAT 0\n#define XWPE " + std::to_string(smm_mfma_wave_wpe(smm_mfma_wave_lds(typesize, m, n, k, wvec, wtb), typesize, m, n, k, wvec, lda, wtb ? 0 : ldb, ldc)) + "\n";
-    s += SMM_JIT_PRELUDE;
+    s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
     s += SMM_JIT_MFMA_WAVE_BODY;
     return s;
   }
@@ -1899,12 +1821,13 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
     s += std::string("#define XTIGHT ") + ((variant & SMM_JIT_MFMA_TIGHT) ? "1" : "0") + "\n";
     s += std::string("#define XTIGHTC ") + ((variant & SMM_JIT_MFMA_TIGHTC) ? "1" : "0") + "\n";
     s += "#define XMW_FORM " + std::to_string(8 == typesize ? (k > 32 ? 2 : 1) : 0) + "\n";
-    s += SMM_JIT_PRELUDE;
+    s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
     s += SMM_MFMA_WG_SOURCE;
     return s;
   }
   if (0 != (variant & SMM_JIT_BIG)) { // work-group per item, K chunked
-    s += "#define XKC " + std::to_string(smm_jit_big_kc(typesize, m, n, k)) + "\n";
+    s += "#define XFLAT 0\n#define XKC " + std::to_string(smm_jit_big_kc(typesize, m, n, k)) + "\n";
+    s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
     s += SMM_JIT_BIG_BODY;
     return s;
   }
@@ -1929,23 +1852,14 @@ std::string gen_smm_source(int typesize, int m, int n, int k, int flags, int var
   s += std::string("#define XHASWG ") + ((variant & SMM_JIT_HASWG) ? "1" : "0") + "\n";   // wave form: leave long runs to the work-group form
   s += "#define XGROUPED 0\n";
   s += std::string("#define XDEFER ") + (defer_env ? "1" : "0") + "\n";
-  s += SMM_JIT_PRELUDE;
+  s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
   s += SMM_JIT_SHAPE; s += SMM_JIT_CHAIN; s += SMM_JIT_SHAPE_KERNELS;
   return s;
 }
 
-// LDS bytes one wave of the generated kernel needs (mirrors the constexpr arithmetic of the source)
-static size_t smm_jit_wave_lds(int typesize, int m, int n, int k, int flags, int pack = 1, bool runs = false)
-{ // runs: the wave run form (XRUNS 1), where C's image lies over the operand images
-  const int tgm = (pack >= 4) ? ((pack >= 16) ? 2 : 4) : 8, tgn = 64 / (pack * tgm);
-  const int tm = (m + tgm - 1) / tgm, tn = (n + tgn - 1) / tgn;
-  int kp = k; if (0 == (tn * (typesize / 4)) % 16) kp = k | 1; else while (0 == (tn * kp * (typesize / 4)) % 16) ++kp;
-  const size_t as = ((size_t)(k * m + tgm * tm + 3) / 4) * 4;
-  const size_t bs = (flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (((size_t)(k * n + tgn * tn + 3) / 4) * 4) : ((((size_t)tgn * tn) * kp + 3) / 4) * 4;
-  const size_t cs = ((size_t)(pack * m * n + 3) / 4) * 4;
-  if (runs) return ((pack * (as + bs) > cs) ? pack * (as + bs) : cs) * typesize;
-  return (pack * (as + bs) + cs) * typesize;
-}
+// LDS bytes one wave of the generated kernel needs (geom::tiled)
+static size_t smm_jit_wave_lds(int typesize, int m, int n, int k, int flags, int pack = 1, bool runs = false) // runs: the wave run form (XRUNS 1)
+{ return (size_t)geom::tiled(typesize, m, n, k, 0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_B), pack, runs ? 1 : 0).wave_lds * typesize; }
 
 // wavefronts per work-group: as many (4, 2, 1) as fit 64 KiB of static LDS; 0 if even one wave does not fit
 static int smm_jit_waves(int typesize, int m, int n, int k, int flags, int pack, bool runs)
@@ -1993,15 +1907,8 @@ bool smm_jit_eligible(const SmmBatch& s)
   return s.batch >= smm_jit_min_batch() || 0 != s.jit_always;
 }
 
-// LDS bytes of one operand buffer of the work-group form (mirrors the constexpr arithmetic of the source)
-static size_t smm_jit_wg_buf(int typesize, int m, int n, int k, int flags)
-{
-  const int nq = (n + 3) / 4, tm = (m + 15) / 16, tn = (nq + 3) / 4, npad = 3 * nq + 4 * tn;
-  int kp = k; if (0 == (tn * (typesize / 4)) % 16) kp = k | 1; else while (0 == (tn * kp * (typesize / 4)) % 16) ++kp;
-  const size_t as = ((size_t)(k * m + 16 * tm + 3) / 4) * 4;
-  const size_t bs = (flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (((size_t)(k * n + npad + 3) / 4) * 4) : (((size_t)npad * kp + 3) / 4) * 4;
-  return (as + bs) * typesize;
-}
+// the work-group form (XRUNS 2) of a shape: wg_buf elements per operand buffer, wg_nbuf of them
+static geom::Tiled smm_jit_wg(int typesize, int m, int n, int k, int flags) { return geom::tiled(typesize, m, n, k, 0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_B), 1, 2); }
 
 // Which flavour of the generated kernel a batch needs: strided batches of tightly packed items whose bases are 16-byte
 // aligned use the widest loads the item size allows; index/pointer batches (and anything else) are only known to be
@@ -2025,12 +1932,10 @@ static JitKernel* smm_jit_get(const SmmKey& key, bool wait = false)
 }
 
 // ---- one launch of a generated kernel ----------------------------------------------------------------------------------
-// the host image of DevAddr (SMM_JIT_PRELUDE), the first argument of every generated kernel
-struct DevAddrH { const char* a; const char* b; char* c; const char* ia; const char* ib; const char* ic; long long sa, sb, sc; int index_base, index_stride, mode; const int* flags; };
-static_assert(sizeof(DevAddrH) == 96, "DevAddrH must have the layout of the device's DevAddr");
-static DevAddrH dev_addr(const SmmBatch& s)
+// DevAddr (kernels/smm_jit_geom.h: the one struct host and kernels compile), the first argument of every generated kernel
+static DevAddr dev_addr(const SmmBatch& s)
 {
-  DevAddrH ad;
+  DevAddr ad;
   memset(&ad, 0, sizeof(ad));
   ad.a = (const char*)s.a; ad.b = (const char*)s.b; ad.c = (char*)s.c; ad.ia = (const char*)s.ia; ad.ib = (const char*)s.ib; ad.ic = (const char*)s.ic;
   ad.sa = s.sa; ad.sb = s.sb; ad.sc = s.sc; ad.index_base = s.index_base; ad.index_stride = s.index_stride; ad.mode = s.mode;
@@ -2065,8 +1970,8 @@ static SmmGeom smm_jit_geometry(const SmmBatch& s, int variant, JitKernel* k)
     units = s.batch / g.runlen;
   }
   else if (0 != (variant & SMM_JIT_WGRUNS)) { // work-groups of 256 threads, dealt chunks of 64 items
-    const size_t buf = smm_jit_wg_buf(s.typesize, s.m, s.n, s.k, s.flags);
-    per_cu = smm_per_cu((2 * buf <= 65536 ? 2 : 1) * buf, 4);
+    const geom::Tiled wg = smm_jit_wg(s.typesize, s.m, s.n, s.k, s.flags);
+    per_cu = smm_per_cu((size_t)wg.wg_nbuf * wg.wg_buf * s.typesize, 4);
     if (0 < bpc_env) per_cu = bpc_env;
     units = (s.batch + 63) / 64;
   }
@@ -2137,7 +2042,7 @@ static SmmGeom smm_jit_geometry(const SmmBatch& s, int variant, JitKernel* k)
 // one launch of kernel k (the generated kernel `variant`) over batch s
 static int smm_jit_launch(const SmmBatch& s, int variant, JitKernel* k, void* stream)
 {
-  DevAddrH ad = dev_addr(s);
+  DevAddr ad = dev_addr(s);
   long long batch = s.batch;
   SmmGeom g = smm_jit_geometry(s, variant, k);
   int runlen = (int)g.runlen;
@@ -2202,7 +2107,7 @@ std::string gen_smm_grouped_source(int typesize, const std::vector<GroupedBody>&
   // pointer into the dispatcher's private copy of the table entry (FLAT loads from scratch, which retire out of order with the
   // other vector-memory operations) and spills through scratch: traffic the counts do not know (hand-counted waits).
   const int handwait = inlined ? smm_mfma_handwait() : 0;
-  s += SMM_JIT_PRELUDE;
+  s += SMM_JIT_GEOM_SOURCE; s += SMM_JIT_PRELUDE;
   for (size_t i = 0; i < bodies.size(); ++i) {
     const GroupedBody& b = bodies[i];
     s += "namespace xg" + std::to_string(i) + " {\n";
@@ -2352,7 +2257,7 @@ JitKernel* grouped_resolve(const SmmBatch* groups, int ngroups, bool check_eligi
 
 int grouped_launch(const SmmBatch* groups, const GroupedPlan& plan, JitKernel* kern, void* stream)
 {
-  struct GroupEntryH { DevAddrH ad; long long batch; unsigned block_begin, nblocks; int body, pad; };
+  struct GroupEntryH { DevAddr ad; long long batch; unsigned block_begin, nblocks; int body, pad; };
   struct GroupTabH { GroupEntryH e[GROUPED_BYVAL]; };
   static_assert(sizeof(GroupTabH) + 16 <= 4096, "kernel arguments of a launch");
   if (plan.entries.size() > (size_t)GROUPED_BYVAL) return -1; // (never: the callers fuse at most 32 batches per launch)
@@ -2600,7 +2505,7 @@ void plan_jit(const SmmBatch& s, SmmPlan& p)
   }
   // the work-group form pays off once a product's operands are large (measured on CP2K stacks: 32^3 f64 yes, 23^3 no)
   const bool tight = (s.lda == s.m && s.ldc == s.m && (0 != (s.flags & LIBXSMM_GEMM_FLAG_TRANS_B) ? (s.ldb == s.n) : (s.ldb == s.k)));
-  const bool wg_fits = (tight && 0 != wg_env && smm_jit_wg_buf(s.typesize, s.m, s.n, s.k, s.flags) <= 65536
+  const bool wg_fits = (tight && 0 != wg_env && smm_jit_wg(s.typesize, s.m, s.n, s.k, s.flags).wg_buf * s.typesize <= geom::LDS_STATIC
                      && (2 == wg_env || (size_t)s.typesize * ((size_t)s.m * s.k + (size_t)s.k * s.n) >= 12288));
   if (SYNC_RUNS == s.sync) { // the host knows that C repeats in runs (one C for the whole batch, batch-reduce): long runs
     if (wg_fits) plan_add(p, TIER_JIT, f64 ? "smm_f64_jit_shape_wgruns" : "smm_f32_jit_shape_wgruns", width | SMM_JIT_WGRUNS);

@@ -35,10 +35,10 @@ SETS = {
 }
 # sha256 of the generated text of the all-eligible sets (the fast path of the CP2K configuration): must not change silently
 ELIGIBLE_TEXT = {
-    ("eligible", 8): "c7e9b143546dfd94e1af619014cc67627742089880edc80fba8224b9bd5c7638",
-    ("eligible", 4): "fd0eebc3129093606d728a1111a30b197ffb9fcfe81293c74468b4751c226d57",
-    ("cp2k", 8): "97d90bdb8de97d5bd99e015f5f21e8aa0398f94496b1f984e8ea01b02f919aa0",
-    ("cp2k", 4): "d1dd0fed28b80c83dd6a68e7b598fbc9c08339c271f948e49805a9c8da57b1e3",
+    ("eligible", 8): "8a2096771e95e603d8f9cc8a8ce07436cb8e9e0db11c43bde07a02066d00f83d",
+    ("eligible", 4): "0e0b1a37b340ee00a7d813b4d010b21bff2d62a4dc7a193611ecbc8381757219",
+    ("cp2k", 8): "e034f77347f3d94e2727ad95f7ac5aac66dd466c6d39b97488a47769a9edccb3",
+    ("cp2k", 4): "13fe79c037238d01c741a6a09f9940856cd6f9ea5f0e14301e4717682aec0ec9",
 }
 # single-shape run / streaming forms (variant 1|2|65536 resp. 1|65536): [typesize, m, n, k, ldb]
 SINGLE = [[8, 32, 32, 64, 0], [8, 32, 32, 32, 0], [8, 32, 32, 64, 80], [8, 13, 13, 13, 0], [8, 32, 16, 64, 0], [8, 5, 7, 3, 0],
