@@ -292,7 +292,7 @@ bool item_grid(long long per_item, long long items, dim3* grid)
 }
 
 template<int BT>
-int launch_fwd(const ConvArgs& g, void* stream)
+int launch_fwd(const ConvArgs& g, void* stream, const char* name)
 {
   const int img0 = g.w0 / g.blocksofm, img1 = (g.w1 - 1) / g.blocksofm + 1;
   const long long npix = (long long)(img1 - img0) * g.ofh * g.ofw;
@@ -305,6 +305,7 @@ int launch_fwd(const ConvArgs& g, void* stream)
     hipLaunchKernelGGL((conv_fwd<BT>), dim3(tiles_i, ny), dim3(NTHREADS), 0, (hipStream_t)stream, g, img0, (int)npix, (int)j0);
     const int e = (int)hipGetLastError();
     if (0 != e) return e;
+    if (0 < j0) xsmm::note_launch(name); // (the caller counts one launch per pass: libxsmm_amd_launch_count is one per slab)
   }
   return 0;
 }
@@ -318,7 +319,7 @@ int launch_conv_fwd(const ConvArgs& g, void* stream, const char** name)
   *name = (128 == g.tile ? "conv_fwd_t128" : "conv_fwd_t64");
   if (64 != g.tile && 128 != g.tile) return (int)hipErrorInvalidValue;
   if (g.w1 <= g.w0) return 0;
-  return 128 == g.tile ? launch_fwd<128>(g, stream) : launch_fwd<64>(g, stream);
+  return 128 == g.tile ? launch_fwd<128>(g, stream, *name) : launch_fwd<64>(g, stream, *name);
 }
 
 int launch_conv_bwd(const ConvArgs& g, void* stream, const char** name)

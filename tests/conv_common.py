@@ -457,15 +457,92 @@ def upd(h, x, dout, dw0, ltid=0, arith=orc.FMA):
 def expected(name, arith=orc.FMA):
     """dict of the inputs of a compute case and of out, din, dw, wtr after the passes with threads = 1 (computed once, shared: read only)"""
     d = COMPUTE_CASES[name]
-    h = Handle(d)
-    t = inputs(name, d)
-    t["out"] = fwd(h, t["x"], t["w"], t["out0"], t["bias"], arith=arith)
-    t["din"] = bwd(h, t["dout"], t["w"], t["din0"], arith=arith)
-    t["dw"] = upd(h, t["x"], t["dout"], t["dw0"], arith=arith)
+    return _with_outputs(Handle(d), inputs(name, d), arith)
+
+
+def _with_outputs(h, t, arith):
+    """t with out, din, dw and wtr after the passes, the shares of the logical threads in turn (read only)"""
+    t["out"], t["din"], t["dw"] = t["out0"], t["din0"], t["dw0"]
+    for ltid in range(h.d["threads"]):
+        t["out"] = fwd(h, t["x"], t["w"], t["out"], t["bias"], ltid, arith)
+        t["din"] = bwd(h, t["dout"], t["w"], t["din"], ltid, arith)
+        t["dw"] = upd(h, t["x"], t["dout"], t["dw"], ltid, arith)
     t["wtr"] = trans_filter(h, t["w"])
     for a in t.values():
         a.setflags(write=False)
     return t
+
+
+# ---- the seeded sweep: descriptors nobody picked --------------------------------------------------------------------------------
+SWEEP_SEED, SWEEP_CASES = 1, 48
+SWEEP_FEATURES = (1, 3, 5, 8, 16, 17, 18, 24, 32, 40, 144)
+RELU_NEAR_ZERO = 0.02  # the share of a case's outputs that the float64 comparison may leave out because the ReLU's argument is within the bound of 0
+
+
+def _draw(rng):
+    pick = lambda lo, hi: int(rng.integers(lo, hi + 1))  # noqa: E731
+    H, W, R, S, u, v = pick(1, 9), pick(1, 9), pick(1, 4), pick(1, 4), pick(1, 3), pick(1, 3)
+    pad = (pick(0, 2), pick(0, 2))
+    pin = pad if pick(0, 1) else LOGICAL
+    pout = (pick(0, 2), pick(0, 2))
+    N, C, K = pick(1, 3), SWEEP_FEATURES[pick(0, 10)], SWEEP_FEATURES[pick(0, 10)]
+    options = (0, OVERWRITE, NO_FILTER_TRANSPOSE, OVERWRITE | NO_FILTER_TRANSPOSE)[pick(0, 3)]
+    return desc(H, W, R, S, u, v, pad=pad, pin=pin, pout=pout, N=N, C=C, K=K, threads=pick(1, 3), options=options, fuse=pick(0, 7))
+
+
+def contract64(h, t):
+    """key -> (value, bound, compared) for out, din and dw: naive64 with the chain's start value added where the pass accumulates
+    or has a bias, UPD's GEMM form as the reference has it, the ReLU applied in float64, and the bound terms * 2^-24 * (sum|a * b| +
+    |start|) of an fp32 chain (derived, as the guard of tools/golden/conv_capture.py). compared: False where the ReLU's argument
+    lies within the bound of 0, so that the two sides may be on either side of it. "unreached": the elements of dinput no term
+    reaches, which keep their start bits (overwrite: +0.0)."""
+    d = h.d
+    want, terms = naive64(h, t, gemm_form_copy=True)
+    res = {}
+    start = {"out": interior(h, "out", t["out0"]).astype(np.float64), "din": interior(h, "din", t["din0"]).astype(np.float64),
+             "dw": interior(h, "dw", t["dw0"]).astype(np.float64)}
+    if d["fuse_ops"] & FUSE_BIAS:
+        start["out"] = np.broadcast_to(np.asarray(t["bias"], dtype=np.float64).reshape(1, d["K"], 1, 1), start["out"].shape)
+    elif h.overwrite:
+        start["out"] = np.zeros_like(start["out"])
+    if h.overwrite:
+        start["din"], start["dw"] = np.zeros_like(start["din"]), np.zeros_like(start["dw"])
+    for key in ("out", "din", "dw"):
+        value, weight = want[key]
+        value, bound = value + start[key], terms[key] * 2.0 ** -24 * (weight + np.abs(start[key]))
+        compared = np.ones(value.shape, dtype=bool)
+        if key == "out" and d["fuse_ops"] & FUSE_RELU:
+            compared = np.abs(value) > bound
+            value = np.maximum(value, 0)
+        res[key] = (value, bound, compared)
+    res["unreached"] = want["din_terms"] == 0
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases():
+    """name -> desc: SWEEP_CASES descriptors drawn from SWEEP_SEED, those that create refuses left out, and those (none so far)
+    whose ReLU leaves more than RELU_NEAR_ZERO of the outputs uncompared replaced by the next draw. tests/test_conv_sweep_cpu.py
+    counts what the set holds; the seed is the first from 0 up that passes that census."""
+    rng = np.random.default_rng(SWEEP_SEED)
+    out = {}
+    while len(out) < SWEEP_CASES:
+        d = _draw(rng)
+        h = Handle(d)
+        if h.status != SUCCESS:
+            continue
+        name = "sweep_%02d" % len(out)
+        if d["fuse_ops"] & FUSE_RELU and np.mean(~contract64(h, inputs(name, d))["out"][2]) >= RELU_NEAR_ZERO:
+            continue
+        out[name] = d
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_expected(name):
+    """expected() of a sweep case: the shares of its logical threads in turn"""
+    d = sweep_cases()[name]
+    return _with_outputs(Handle(d), inputs(name, d), orc.FMA)
 
 
 def bits(a):
@@ -484,9 +561,13 @@ def same_bits(got, want, nan_class=False):
     return bool(np.array_equal(g[~both], w[~both]))
 
 
-def naive64(h, t):
+def naive64(h, t, gemm_form_copy=False):
     """(out, din, dw) of a plain float64 convolution of the inputs t with the chains' start values, and per element the number of
-    terms and the sum of |a * b|: the guard of tools/golden/conv_capture.py. Interior elements only ([N][C or K][rows][columns])."""
+    terms and the sum of |a * b|: the guard of tools/golden/conv_capture.py. Interior elements only ([N][C or K][rows][columns]).
+    "din_terms" counts the terms that reach an element of dinput. gemm_form_copy: UPD as the reference's GEMM form computes it
+    where that is no plain convolution (upd template :95-103): with a physical padding it reads a copy of the input
+    that holds rows below ifhp / u * u and columns below ifwp / v * v only, the rest is +0.0 (a stride above 1 means a 1 x 1 window
+    there, so ifhp % u rows at the bottom and ifwp % v columns at the right drop out of dW)."""
     d = h.d
     N, C, K, R, S, u, v = d["N"], d["C"], d["K"], d["R"], d["S"], d["u"], d["v"]
     ph, pw, qh, qw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
@@ -500,6 +581,12 @@ def naive64(h, t):
     out, out_abs = np.zeros((N, K, h.ofh, h.ofw)), np.zeros((N, K, h.ofh, h.ofw))
     din, din_abs = np.zeros((N, C, h.hp, h.wp)), np.zeros((N, C, h.hp, h.wp))
     dw, dw_abs = np.zeros((K, C, R, S)), np.zeros((K, C, R, S))
+    din_terms = np.zeros((N, C, h.hp, h.wp), dtype=np.int64)
+    x_upd = x
+    if gemm_form_copy and h.physical and not h.upd_per_image():
+        x_upd = x.copy()
+        x_upd[:, :, h.ifhp // u * u:, :] = 0
+        x_upd[:, :, :, h.ifwp // v * v:] = 0
     for kj in range(R):
         for ki in range(S):
             xs = x[:, :, kj:kj + (h.ofh - 1) * u + 1:u, ki:ki + (h.ofw - 1) * v + 1:v]
@@ -507,11 +594,13 @@ def naive64(h, t):
             out_abs += np.einsum("nchw,kc->nkhw", np.abs(xs), np.abs(w[:, :, kj, ki]))
             din[:, :, kj:kj + (h.ofh - 1) * u + 1:u, ki:ki + (h.ofw - 1) * v + 1:v] += np.einsum("nkhw,kc->nchw", dout, w[:, :, kj, ki])
             din_abs[:, :, kj:kj + (h.ofh - 1) * u + 1:u, ki:ki + (h.ofw - 1) * v + 1:v] += np.einsum("nkhw,kc->nchw", np.abs(dout), np.abs(w[:, :, kj, ki]))
+            din_terms[:, :, kj:kj + (h.ofh - 1) * u + 1:u, ki:ki + (h.ofw - 1) * v + 1:v] += K
+            xs = x_upd[:, :, kj:kj + (h.ofh - 1) * u + 1:u, ki:ki + (h.ofw - 1) * v + 1:v]
             dw[:, :, kj, ki] = np.einsum("nkhw,nchw->kc", dout, xs)
             dw_abs[:, :, kj, ki] = np.einsum("nkhw,nchw->kc", np.abs(dout), np.abs(xs))
     cut = (slice(None), slice(None), slice(d["pad_h"], d["pad_h"] + d["H"]), slice(d["pad_w"], d["pad_w"] + d["W"]))
     terms = dict(out=C * R * S, din=K * R * S, dw=N * h.ofh * h.ofw)
-    return dict(out=(out, out_abs), din=(din[cut], din_abs[cut]), dw=(dw, dw_abs)), terms
+    return dict(out=(out, out_abs), din=(din[cut], din_abs[cut]), dw=(dw, dw_abs), din_terms=din_terms[cut]), terms
 
 
 def interior(h, key, a):

@@ -14,6 +14,7 @@ CSRC = os.path.join(ROOT, "libxsmm-1_amd", "csrc")
 
 QUANT, MATDIFF, POOL, TILE, SPARSE, GENERIC, LOWP, XCOPY = ("kernels/quant.hip", "kernels/matdiff.hip", "kernels/pool.hip",
     "kernels/tile_gemm.cuh", "kernels/sparse.hip", "kernels/smm_generic.hip", "kernels/smm_lowp.hip", "kernels/xcopy.hip")
+CONV = "kernels/conv.hip"
 GRID_FOR = (SPARSE, r"if \(blocks > 256LL \* (\d+)\) blocks = 256LL \* \1;", 32)
 
 LIMITS = {
@@ -54,6 +55,19 @@ LIMITS = {
     "pool": dict(derive=lambda v: v[0], unit="items", per_trip=32768, source=[
         (POOL, r"gy = items < (\d+) \? items : \1, gz = \(items \+ gy - 1\) / gy", 32768),
         (POOL, r"\(long long\)g\.w0 \+ blockIdx\.y \+ \(long long\)blockIdx\.z \* gridDim\.y", None)]),
+    # convolution: FWD takes 65535 tiles of pixels per launch (gridDim.y) and hands the kernel the first tile of the slab; BWD and
+    # UPD take their items as pooling does; the filter transposition wraps its work-groups into rows of 65536
+    "conv_fwd_slab": dict(derive=lambda v: v[0], unit="tiles of pixels", per_trip=65535, tiles=(64, 128), source=[
+        (CONV, r"constexpr long long SLAB = (\d+);", 65535), (CONV, r"for \(long long j0 = 0; j0 < tiles_j; j0 \+= SLAB\)", None),
+        (CONV, r"\(long long\)BT \* \(\(long long\)jtile0 \+ blockIdx\.y\)", None)]),
+    "conv_items": dict(derive=lambda v: v[0], unit="items", per_trip=32768, source=[
+        (CONV, r"gy = items < (\d+) \? items : \1, gz = \(items \+ gy - 1\) / gy", 32768),
+        (CONV, r"void conv_bwd\(const ConvArgs g\)\s*\{\s*const long long item = \(long long\)g\.w0 \+ blockIdx\.y \+ \(long long\)blockIdx\.z \* gridDim\.y;", None),
+        (CONV, r"void conv_upd\(const ConvArgs g\)\s*\{\s*const long long item = \(long long\)g\.w0 \+ blockIdx\.y \+ \(long long\)blockIdx\.z \* gridDim\.y;", None)]),
+    "conv_trans_filter": dict(derive=lambda v: v[0] * v[1], unit="elements", per_trip=65536 * 256, source=[
+        (CONV, r"gx = blocks < (\d+) \? blocks : \1, gy = \(blocks \+ gx - 1\) / gx", 65536), (TILE, r"constexpr int NTHREADS = (\d+);", 256),
+        (CONV, r"blocks = \(total \+ NTHREADS - 1\) / NTHREADS", None),
+        (CONV, r"\(\(long long\)blockIdx\.x \+ \(long long\)blockIdx\.y \* gridDim\.x\) \* NTHREADS \+ threadIdx\.x", None)]),
     # tiled GEMM: one grid covers 65535 tiles of columns. A test asks libxsmm_amd_gemm_tile() for the tile; tile_cross_check is
     # only what that answer is held against
     "tgemm_band": dict(derive=lambda v: v[0], unit="tiles of columns", per_trip=65535, tile_cross_check=128, source=[

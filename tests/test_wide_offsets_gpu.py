@@ -1,6 +1,7 @@
 """Operands whose element offsets pass 2^31 (and whose byte offsets pass 2^32): the 64-bit instantiation of the quantise layout
 kernel, leading dimensions of 2^30 + 7 in the tiled GEMMs, a strided batch with a C stride of 2^20 elements, fsspmdm at the
-leading dimension of BASELINE config 3, and pooling over more than 2^31 elements.
+leading dimension of BASELINE config 3, and pooling over more than 2^31 elements. The convolution layer refuses tensors of 2^31
+elements (its offsets are 32-bit): it runs on the largest ones it accepts, an input and a filter just below 2^31 elements.
 
 The operands are built on the device and never travel whole. Each case checks (i) a sample gathered to the host against the
 family's host reference -- everywhere the call writes where that is small, otherwise at least 256 places that include the
@@ -14,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+import conv_common as cc
 import launch_limits as ll
 import lowp_gemm_common as lg
 import pool_common as pc
@@ -373,3 +375,165 @@ def test_pool_past_2_31_elements(xs, torch_gpu, kind):
     for t in bound:
         L.libxsmm_dnn_destroy_tensor(t)
     assert 0 == L.libxsmm_dnn_destroy_pooling(handle)
+
+
+# ---- convolution: tensors one image (one block) short of 2^31 elements --------------------------------------------------------------
+CONV_ACT = cc.desc(H=128, W=128, R=1, S=1, N=2047, C=64, K=1)      # the input: 2^31 elements less one image
+CONV_FIL = cc.desc(H=1, W=1, R=1, S=1, N=1, C=46336, K=46336)      # the filter: 2896 * 2896 items of 16 x 16
+POISON_BITS = -1  # conv_common.POISON as int32
+
+
+def poisoned(torch, n):
+    """n float32 elements of ones bits between bands: (whole tensor as int32, the elements as int32, the elements as float32)"""
+    whole, inner = banded(torch, n, torch.int32, POISON_BITS)
+    return whole, inner, inner.view(torch.float32)
+
+
+def seeded(torch, n, seed):
+    whole, inner = banded(torch, n, torch.float32, 0.0)
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
+    inner.normal_(generator=g)
+    return whole, inner
+
+
+def bit_sum(torch, t):
+    """the sum of the elements' bits, exact: what a tensor that must not be written is held against"""
+    total = 0
+    for s in range(0, t.numel(), SLAB):
+        total += int(t[s:s + SLAB].view(torch.int32).sum(dtype=torch.int64))
+    return total
+
+
+def only_these_written(torch, dest_i32, per_item, items):
+    """everything outside the given items (of per_item elements each) still holds ones bits"""
+    lo = 0
+    for i in sorted(items):
+        if not all_equal(torch, dest_i32, POISON_BITS, lo, i * per_item):
+            return False
+        lo = (i + 1) * per_item
+    return all_equal(torch, dest_i32, POISON_BITS, lo, dest_i32.numel())
+
+
+def conv_layer(xs, d, bind):
+    handle, st = xs.conv_create(*[d[k] for k in cc.DESC_FIELDS])
+    assert handle and 0 == st
+    scratch = np.zeros(64, dtype=np.uint8)  # (never read or written: host memory will do)
+    assert 0 == xs.lib().libxsmm_dnn_bind_scratch(handle, cc.ALL, xs.dptr(scratch))
+    return handle, [xs.conv_bind_new(handle, t, v) for t, v in bind], scratch
+
+
+def conv_close(xs, handle, tensors):
+    for t in tensors:
+        xs.lib().libxsmm_dnn_destroy_tensor(t)
+    assert 0 == xs.lib().libxsmm_dnn_destroy_conv_layer(handle)
+
+
+@pytest.mark.parametrize("kind", ["fwd", "bwd"])
+def test_conv_activations_below_2_31_elements(xs, torch_gpu, kind):
+    """FWD reads and BWD writes an input of 2^31 - 2^20 elements: as many logical threads as items, and only the shares of three
+    items run -- the first, the last (whose offsets end at 2^31 - 2^20 - 1, above 2^30) and one in the upper half. Each against
+    tests/conv_common.py on a layer of those three images alone (C and the blocks kept: the chain order depends on them)."""
+    torch = torch_gpu
+    h = cc.Handle(CONV_ACT)
+    n_in, n_out = int(np.prod(h.in_shape())), int(np.prod(h.out_shape()))
+    plane_in = 128 * 128 * 16
+    assert n_in == W31 - 64 * 128 * 128 == 2146435072 and n_out == 2047 * 128 * 128 and (h.ifmblock, h.blocksifm, h.ofmblock, h.blocksofm) == (16, 4, 1, 1)
+    need(torch, (n_in + n_out) * 4)
+    images = (0, 1024, 2046)
+    small = cc.Handle(dict(CONV_ACT, N=len(images)))
+    w = np.random.default_rng(5).standard_normal(h.fil_shape(), dtype=np.float32)
+    dw = torch.from_numpy(w).cuda()
+    dsel = torch.tensor(images, device="cuda")
+    if kind == "fwd":
+        d = dict(CONV_ACT, threads=h.work(cc.FWD))
+        assert d["threads"] == 2047 and [cc.Handle(d).share(cc.FWD, i) for i in images] == [(i, i + 1) for i in images]
+        bx, x = seeded(torch, n_in, 17)
+        bo, out_bits, out = poisoned(torch, n_out)
+        before = bit_sum(torch, x)
+        handle, tensors, scratch = conv_layer(xs, d, ((cc.REG_IN, x), (cc.REG_FIL, dw), (cc.REG_OUT, out)))
+        for i in reversed(images):
+            assert 0 == xs.conv_execute(handle, cc.FWD, 0, i)
+        torch.cuda.synchronize()
+        assert xs.last_kernel().startswith("conv_fwd_t")
+        hx = x.view(2047, -1)[dsel].cpu().numpy()
+        want = cc.fwd(small, hx, w, np.full(small.out_shape(), cc.POISON, dtype=np.float32), None)
+        got = out.view(2047, -1)[dsel].cpu().numpy()
+        assert cc.same_bits(got, want), int(np.sum(cc.bits(got) != cc.bits(want)))
+        assert only_these_written(torch, out_bits, 128 * 128, images)
+        assert bit_sum(torch, x) == before and np.array_equal(dw.cpu().numpy(), w)
+        assert bands_intact(bx) and bands_intact(bo)
+    else:
+        items = (0, 4 * 1500 + 1, 4 * 2047 - 1)  # (image, block): the first, one in the upper half, the last
+        d = dict(CONV_ACT, threads=h.work(cc.BWD))
+        assert d["threads"] == 8188 and [cc.Handle(d).share(cc.BWD, i) for i in items] == [(i, i + 1) for i in items]
+        assert items[1] * plane_in > W31 // 2 and (items[2] + 1) * plane_in == n_in
+        bi, din_bits, din = poisoned(torch, n_in)
+        bo, dout = seeded(torch, n_out, 19)
+        before = bit_sum(torch, dout)
+        handle, tensors, scratch = conv_layer(xs, d, ((cc.GRAD_IN, din), (cc.REG_FIL, dw), (cc.GRAD_OUT, dout)))
+        for i in reversed(items):
+            assert 0 == xs.conv_execute(handle, cc.BWD, 0, i)
+        torch.cuda.synchronize()
+        assert xs.last_kernel() == "conv_bwd"
+        of_images = torch.tensor([i // 4 for i in items], device="cuda")
+        hd = dout.view(2047, -1)[of_images].cpu().numpy()
+        want = cc.bwd(small, hd, w, np.full(small.in_shape(), cc.POISON, dtype=np.float32))  # all four blocks of the three images
+        got = din.view(2047 * 4, -1)[torch.tensor(items, device="cuda")].cpu().numpy()
+        for n, i in enumerate(items):
+            assert cc.same_bits(got[n], want[n, i % 4]), (i, int(np.sum(cc.bits(got[n]) != cc.bits(want[n, i % 4]))))
+        assert only_these_written(torch, din_bits, plane_in, items)
+        assert bit_sum(torch, dout) == before and np.array_equal(dw.cpu().numpy(), w)
+        assert bands_intact(bi) and bands_intact(bo)
+    assert np.all(scratch == 0)
+    conv_close(xs, handle, tensors)
+
+
+@pytest.mark.parametrize("part", ["upd", "trans"])
+def test_conv_filter_below_2_31_elements(xs, torch_gpu, part):
+    """a filter of 2896 * 2896 blocks of 16 x 16: 2^31 - 458752 elements. upd: the shares of the first item, the last (its offsets
+    end above 2^30, at the last element) and one in the middle, each against tests/conv_common.py on a layer of one block on either
+    side. trans: libxsmm_dnn_trans_reg_filter into a second tensor of that size, compared on the device with the permuted view of
+    the source (1 x 1: nothing to flip), 256 rows of blocks at a time."""
+    torch = torch_gpu
+    h = cc.Handle(CONV_FIL)
+    nb, total = 2896, int(np.prod(h.fil_shape()))
+    assert total == 2147024896 < W31 and (h.ifmblock, h.ofmblock, h.blocksifm, h.blocksofm) == (16, 16, nb, nb) and h.work(cc.UPD) == nb * nb
+    if part == "upd":
+        need(torch, total * 4)
+        items = (0, 1450 * nb + 77, nb * nb - 1)
+        d = dict(CONV_FIL, threads=h.work(cc.UPD))
+        assert [cc.Handle(d).share(cc.UPD, i) for i in items] == [(i, i + 1) for i in items] and (items[2] + 1) * 256 == total
+        rng = np.random.default_rng(23)
+        x, dout = rng.standard_normal(h.in_shape(), dtype=np.float32), rng.standard_normal(h.out_shape(), dtype=np.float32)
+        dx, ddout = torch.from_numpy(x).cuda(), torch.from_numpy(dout).cuda()
+        bw, dw_bits, dw = poisoned(torch, total)
+        handle, tensors, scratch = conv_layer(xs, d, ((cc.REG_IN, dx), (cc.GRAD_OUT, ddout), (cc.GRAD_FIL, dw)))
+        for i in reversed(items):
+            assert 0 == xs.conv_execute(handle, cc.UPD, 0, i)
+        torch.cuda.synchronize()
+        assert xs.last_kernel() == "conv_upd_gemm"
+        got = dw.view(nb * nb, 256)[torch.tensor(items, device="cuda")].cpu().numpy()
+        small = cc.Handle(dict(CONV_FIL, C=16, K=16))
+        for n, i in enumerate(items):
+            ofm1, ifm1 = divmod(i, nb)
+            want = cc.upd(small, x[:, ifm1:ifm1 + 1], dout[:, ofm1:ofm1 + 1], np.full(small.fil_shape(), cc.POISON, dtype=np.float32))
+            assert cc.same_bits(got[n], want), i
+        assert only_these_written(torch, dw_bits, 256, items) and bands_intact(bw)
+        assert np.array_equal(dx.cpu().numpy(), x) and np.array_equal(ddout.cpu().numpy(), dout)
+    else:
+        if torch.cuda.mem_get_info()[0] < 2 * total * 4 + GiB:
+            pytest.skip("the transposition needs a second tensor of 8 GiB: %.1f GiB free, it needs %.1f" % (torch.cuda.mem_get_info()[0] / GiB, 2 * total * 4 / GiB + 1))
+        need(torch, 2 * total * 4)
+        bw, w = seeded(torch, total, 29)
+        bt, wtr_bits, wtr = poisoned(torch, total)
+        before = bit_sum(torch, w)
+        handle, tensors, scratch = conv_layer(xs, CONV_FIL, ((cc.REG_FIL, w), (cc.REG_FIL_TR, wtr)))
+        assert 0 == xs.lib().libxsmm_dnn_trans_reg_filter(handle)
+        torch.cuda.synchronize()
+        assert xs.last_kernel() == "conv_trans_filter"
+        src, dst = w.view(nb, nb, 16, 16), wtr.view(nb, nb, 16, 16)  # [ofm1][ifm1][ifm2][ofm2] -> [ifm1][ofm1][ofm2][ifm2]
+        for i0 in range(0, nb, 256):
+            assert bool((dst[i0:i0 + 256] == src[:, i0:i0 + 256].permute(1, 0, 3, 2)).all()), i0
+        assert bit_sum(torch, w) == before and bands_intact(bw) and bands_intact(bt)
+    assert np.all(scratch == 0)
+    conv_close(xs, handle, tensors)
