@@ -55,8 +55,6 @@ void csr_panels_kernel(int M, long long ncols, int ldb, int ldc, int beta0, int 
 __global__ __launch_bounds__(256)
 void spmdm_create_kernel(long long nslices, int nrows_full, int ncols_full, int transa,
                          const float* __restrict__ a, long long a_slice_stride, int ld,
-                         // block decomposition of one matrix (mb_count > 0) or batch of whole matrices (mb_count == 0)
-                         int mb_count, int bm, int bk, int M, int K,
                          uint16_t* __restrict__ rowidx, uint16_t* __restrict__ colidx, float* __restrict__ values,
                          long long rowidx_stride, long long cap)
 {
@@ -64,14 +62,8 @@ void spmdm_create_kernel(long long nslices, int nrows_full, int ncols_full, int 
   const long long wave = (long long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // (uniform by construction; blockDim.x is a multiple of 64)
   const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
   for (long long s = wave; s < nslices; s += nwaves) {
-    const float* in; int nrows, ncols;
-    if (0 < mb_count) { // slice s = kb*mb_count + mb of one M x K matrix (reference: kb = id / mb, mb = id % mb)
-      const int kb = (int)(s / mb_count), mb = (int)(s % mb_count);
-      nrows = ((mb + 1) * bm > M) ? (M - mb * bm) : bm;
-      ncols = ((kb + 1) * bk > K) ? (K - kb * bk) : bk;
-      in = transa ? (a + (size_t)mb * bm + (size_t)kb * bk * M) : (a + (size_t)kb * bk + (size_t)mb * bm * K);
-    }
-    else { nrows = nrows_full; ncols = ncols_full; in = a + s * a_slice_stride; }
+    const int nrows = nrows_full, ncols = ncols_full; // every slice is a whole nrows x ncols matrix, a_slice_stride apart
+    const float* const in = a + s * a_slice_stride;
     uint16_t* const ri = rowidx + s * rowidx_stride;
     uint16_t* const ci = colidx + s * cap;
     float* const va = values + s * cap;
@@ -1092,7 +1084,7 @@ int launch_spmdm_create(const SpmdmGeom& g, int transa, const float* a, uint16_t
     return (int)hipGetLastError();
   }
   hipLaunchKernelGGL(spmdm_create_kernel, dim3(grid_for(g.batch, 4)), dim3(256), 0, st,
-    g.batch, g.m, g.k, transa, a, (long long)g.m * g.k, transa ? g.m : g.k, 0, g.m, g.k, g.m, g.k,
+    g.batch, g.m, g.k, transa, a, (long long)g.m * g.k, transa ? g.m : g.k,
     rowidx, colidx, values, (long long)g.rstride, (long long)g.cap);
   return (int)hipGetLastError();
 }
@@ -1118,7 +1110,7 @@ int launch_spmdm_create_blocks(int M, int K, int bm, int bk, int mb, int first_s
     const int ncols = ((kb + 1) * bk > K) ? (K - kb * bk) : bk;
     const float* in = transa ? (a + (size_t)imb * bm + (size_t)kb * bk * M) : (a + (size_t)kb * bk + (size_t)imb * bm * K);
     hipLaunchKernelGGL(spmdm_create_kernel, dim3(1), dim3(64), 0, st,
-      1LL, nrows, ncols, transa, in, 0LL, transa ? M : K, 0, bm, bk, M, K,
+      1LL, nrows, ncols, transa, in, 0LL, transa ? M : K,
       rowidx + s * rstride, colidx + s * cap, values + s * cap, rstride, cap);
   }
   return (int)hipGetLastError();

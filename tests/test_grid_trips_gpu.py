@@ -335,11 +335,10 @@ def slices_of(a, M, K):
     return rowidx, keep
 
 
-def test_spmdm_batch_create_past_its_grid(xs, orc, torch_gpu):
-    """2 * 32768 + 5 items of 16 x 16: every item's row starts and entries against numpy, by way of libxsmm_amd_spmdm_batch_get_slice
-    for items at both ends and around the trips, and for all items through the product computed from the slices"""
-    torch, L = torch_gpu, xs.lib()
-    M = K = N = 16
+def spmdm_create_past_its_grid(xs, orc, torch, M, N, K, create_kernel, compute_kernels):
+    """2 * 32768 + 5 items: every item's row starts and entries against numpy, by way of libxsmm_amd_spmdm_batch_get_slice for items
+    at both ends and around the trips, and for all items through the product computed from the slices, between canaries"""
+    L = xs.lib()
     batch = ll.sized("spmdm_create", 5)
     a, b = spmdm_operands(M, N, K, batch, 0.15, 1)
     a[7 * M * K + 3] = -0.0
@@ -347,7 +346,7 @@ def test_spmdm_batch_create_past_its_grid(xs, orc, torch_gpu):
     assert sb
     da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     assert 0 == L.libxsmm_amd_spmdm_batch_create_slices(sb, b"N", xs.dptr(da))
-    assert xs.last_kernel().startswith("spmdm_create_slices")
+    assert xs.last_kernel() == create_kernel, xs.last_kernel()
     rowidx, keep = slices_of(a, M, K)
     per = ll.per_trip("spmdm_create")
     ri = np.zeros(M + 1, dtype=np.uint16); ci = np.zeros(M * K, dtype=np.uint16); va = np.zeros(M * K, dtype=np.float32)
@@ -363,10 +362,22 @@ def test_spmdm_batch_create_past_its_grid(xs, orc, torch_gpu):
     be = C.c_float(0.0)
     assert 0 == L.libxsmm_amd_spmdm_batch_compute(sb, b"N", xs.dptr(db), b"N", C.byref(be), xs.dptr(dc[32:]))
     torch.cuda.synchronize()
+    assert xs.last_kernel() in compute_kernels, xs.last_kernel()
     got = dc.cpu().numpy()
     L.libxsmm_amd_spmdm_batch_destroy(sb)
     assert np.isnan(got[:32]).all() and np.isnan(got[-32:]).all()
     assert np.array_equal(bits32(got[32:-32]), bits32(ref))
+
+
+def test_spmdm_batch_create_past_its_grid(xs, orc, torch_gpu):
+    """items of 16 x 16 x 16: spmdm_create_staged_kernel (entries collected in LDS), then the pair of compute kernels"""
+    spmdm_create_past_its_grid(xs, orc, torch_gpu, 16, 16, 16, "spmdm_create_slices_staged", ("spmdm_compute_mfma|wg_lds", "spmdm_compute_wg_lds"))
+
+
+def test_spmdm_batch_create_wave_kernel_past_its_grid(xs, orc, torch_gpu):
+    """items of 1 x 4 x 65: more than 64 columns, so spmdm_create_kernel (a wavefront per slice, the loop over chunks of 64 columns)
+    walks its grid-stride loop over the items; the product comes from spmdm_compute_wg_kernel<1> alone (M is no multiple of 16)"""
+    spmdm_create_past_its_grid(xs, orc, torch_gpu, 1, 4, 65, "spmdm_create_slices_wave", ("spmdm_compute_wg_lds",))
 
 
 def spmdm_compute_case(xs, orc, torch, mfma, M, N, K, batch, tb, betas, kernels):
@@ -451,6 +462,63 @@ def test_spmdm_batch_compute_matrix_cores_alone(xs, orc, torch_gpu, tmp_path):
     assert res.returncode == 0, (res.stdout, res.stderr)
     assert "kernel: spmdm_compute_mfma\n" in res.stdout, res.stdout
     assert np.array_equal(bits32(np.load(base + "_out.npy")), bits32(ref))
+
+
+SPMDM_TILED16 = r"""
+import ctypes as C, importlib, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+xs = importlib.import_module("libxsmm-1_amd")
+L = xs.lib()
+base, M, K = sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
+a = np.load(base + "_a.npy")
+alpha, be = C.c_float(1.0), C.c_float(0.5)
+for tag in sys.argv[5:]:
+    N, tb = int(tag[:-1]), tag[-1]
+    b, c = np.load(base + "_b%s.npy" % tag), np.load(base + "_c%s.npy" % tag)
+    h = xs.SpmdmHandle(); slices = C.POINTER(xs.CSRSlice)()
+    L.libxsmm_spmdm_init(M, N, K, 1, C.byref(h), C.byref(slices))
+    assert 0 == L.libxsmm_amd_spmdm_createSparseSlice_all(C.byref(h), b"N", xs.dptr(a), slices)
+    assert 0 == L.libxsmm_amd_spmdm_compute_all(C.byref(h), b"N", tb.encode(), C.byref(alpha), slices, xs.dptr(b), b"N", C.byref(be), xs.dptr(c))
+    assert 0 == L.libxsmm_amd_synchronize()
+    print("kernel %s: %s" % (tag, xs.last_kernel()))
+    L.libxsmm_spmdm_destroy(C.byref(h))
+    np.save(base + "_out%s.npy" % tag, c)
+"""
+
+
+def test_spmdm_tiled_kernel_sixteen_row_tiles(xs, orc, torch_gpu, tmp_path):
+    """XSMM_SPMDM_TILE_ROWS=16 gives the whole-problem calls to spmdm_tiled_kernel<*, *, 4> (tiles of 16 rows, four waves): the
+    setting is read once per process, so the four instantiations run in one process of their own, on pageable host operands.
+    130 x N x 200 at 15 %, beta = 0.5: N = 516 takes 16-byte accesses, N = 515 element-wide ones, each with B plain and transposed;
+    ragged tiles in every direction (130 = 8 * 16 + 2 rows, 516 = 2 * 256 + 4 columns, 200 = 3 * 64 + 8)."""
+    M, K = 130, 200
+    rng = np.random.default_rng(16)
+    a = rng.uniform(-1, 1, M * K).astype(np.float32)
+    a[rng.random(M * K) >= 0.15] = 0.0
+    a[5 * K:6 * K] = 0.0                      # an empty row
+    a[17 * K:18 * K] = np.float32(0.75)       # a full one
+    base = str(tmp_path / "tiled16")
+    np.save(base + "_a.npy", a)
+    tags, refs = [], {}
+    for N in (516, 515):
+        for tb in "NT":
+            tag = "%d%s" % (N, tb)
+            b = rng.uniform(-1, 1, K * N).astype(np.float32)
+            c = rng.uniform(-1, 1, M * N).astype(np.float32)
+            ref = c.copy()
+            orc.spmdm_exec(orc.FMA, M, N, K, 48, "N", tb, "N", 0.5, a, b, ref)
+            np.save(base + "_b%s.npy" % tag, b); np.save(base + "_c%s.npy" % tag, c)
+            tags.append(tag); refs[tag] = ref
+    env = dict(os.environ, XSMM_SPMDM_TILE_ROWS="16")
+    res = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", SPMDM_TILED16, ROOT, base, str(M), str(K)] + tags,
+                         capture_output=True, text=True, env=env)
+    assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
+    for tag in tags:
+        assert "kernel %s: spmdm_compute_tiled16\n" % tag in res.stdout, res.stdout
+        got = np.load(base + "_out%s.npy" % tag)
+        bad = np.flatnonzero(bits32(got) != bits32(refs[tag]))
+        assert bad.size == 0, (tag, bad.size, int(bad[0]))
 
 
 def test_spmdm_batch_compute_element_kernel(xs, orc, torch_gpu):
