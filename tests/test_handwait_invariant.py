@@ -1,6 +1,6 @@
 """Hand-counted waits of the matrix-core run form: an invariant of the code objects, checked without a GPU.
 
-The run form (SMM_JIT_MFMA_RUNS_KERNEL, XHANDWAIT 1) issues its operand loads as inline assembly and waits for them with
+The run form (csrc/kernels/smm_jit_mfma_runs.inc, XHANDWAIT 1) issues its operand loads as inline assembly and waits for them with
 `s_waitcnt vmcnt(N)`, N a constant of the pipeline. Those counts hold only while the body's vector-memory traffic is exactly
 the loads the pipeline accounts for: no FLAT access (FLAT instructions retire out of order with the others), no scratch
 (spills, or a table entry kept in the private segment and read through a generic pointer). So: whenever the text the
@@ -35,10 +35,10 @@ SETS = {
 }
 # sha256 of the generated text of the all-eligible sets (the fast path of the CP2K configuration): must not change silently
 ELIGIBLE_TEXT = {
-    ("eligible", 8): "8a2096771e95e603d8f9cc8a8ce07436cb8e9e0db11c43bde07a02066d00f83d",
-    ("eligible", 4): "0e0b1a37b340ee00a7d813b4d010b21bff2d62a4dc7a193611ecbc8381757219",
-    ("cp2k", 8): "e034f77347f3d94e2727ad95f7ac5aac66dd466c6d39b97488a47769a9edccb3",
-    ("cp2k", 4): "13fe79c037238d01c741a6a09f9940856cd6f9ea5f0e14301e4717682aec0ec9",
+    ("eligible", 8): "e0ceebacd680c2ae54a123da2ed236b0420d64943e4b05813965a70f98f6379c",
+    ("eligible", 4): "fa2c7ca01e814b49e11b1ded4796df2d97da4f662bb1cb05d60026eb89ac03ac",
+    ("cp2k", 8): "0ccb1517e726b5ec8a2f1b6bc7a3af051542c3fb1e19d9ed7ec6d09740b6df1d",
+    ("cp2k", 4): "069b804152ac4dbc91c8a873dc7cfea89f47765db96e38ed4f026f5aa4511d01",
 }
 # single-shape run / streaming forms (variant 1|2|65536 resp. 1|65536): [typesize, m, n, k, ldb]
 SINGLE = [[8, 32, 32, 64, 0], [8, 32, 32, 32, 0], [8, 32, 32, 64, 80], [8, 13, 13, 13, 0], [8, 32, 16, 64, 0], [8, 5, 7, 3, 0],

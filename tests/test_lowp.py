@@ -267,7 +267,7 @@ def test_small_low_precision_items_several_per_wave(xs, orc, torch_gpu, kind, sh
 @pytest.mark.parametrize("kind", [2, 3])
 @pytest.mark.parametrize("shape", [(48, 48, 48), (64, 40, 56), (64, 64, 64), (16, 64, 8), (40, 33, 16), (45, 40, 26), (48, 50, 12)])
 def test_low_precision_wave_kernel(xs, orc, torch_gpu, kind, shape):
-    """bf16 inputs beyond 32 on the one-wave-per-item matrix-core kernel (csrc/xsmm_jit_smm.cpp, SMM_JIT_MFMA_WAVE_BODY with
+    """bf16 inputs beyond 32 on the one-wave-per-item matrix-core kernel (csrc/kernels/smm_jit_mfma_wave.inc with
     XLOWP): the fp32 instruction on the widened operands is the gold loop's product-then-add (samples/xgemm/kernel.c:1104-1123,
     1207-1229) bit for bit; a bf16 result is truncated once. Strided batches smaller and larger than the resident grid.
     Parity unpinned beyond the gold loops (no reference-held vector)."""

@@ -1,4 +1,4 @@
-"""The run form on the matrix cores (csrc/xsmm_jit_smm.cpp, SMM_JIT_MFMA_RUNS_*): batches whose consecutive products share a C
+"""The run form on the matrix cores (csrc/kernels/smm_jit_mfma_runs_const.inc, smm_jit_mfma_runs.inc): batches whose consecutive products share a C
 block -- CP2K stacks (samples/cp2k/cp2k.cpp:328-360), batch-reduce, blocked GEMM work lists -- with M, N <= 32. A wave owns a
 run and keeps C in the accumulators of v_mfma_{f32,f64}_16x16x4 across its products; both instructions are k-ordered fma
 chains, so C must equal the oracle's sequential chain (products in batch order, k ascending) BIT FOR BIT, exactly as the

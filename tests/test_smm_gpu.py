@@ -306,7 +306,7 @@ MFMA_WAVE_SHAPES = [(40, 40, 40), (48, 48, 48), (56, 56, 56), (36, 64, 8), (64, 
 @pytest.mark.parametrize("beta", [1.0, 0.0])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_smm_mfma_wave(xs, orc, torch_gpu, dtype, shape, beta):
-    """One wave per item on the matrix cores (csrc/xsmm_jit_smm.cpp, SMM_JIT_MFMA_WAVE_BODY: 16x16x4 tiles, operands and C as
+    """One wave per item on the matrix cores (csrc/kernels/smm_jit_mfma_wave.inc: 16x16x4 tiles, operands and C as
     whole lines through LDS, stores deferred behind the next item's wait): the oracle's fma chain bit for bit, for batches
     smaller than, equal to and larger than the resident grid (every wave then walks several items) and with C = -0 / A = 0."""
     torch = torch_gpu
