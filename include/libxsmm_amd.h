@@ -247,6 +247,12 @@ LIBXSMM_API void libxsmm_amd_spgemm_destroy(const libxsmm_amd_spgemm* handle);
 /** The text libxsmm_amd_spgemm_create compiles (buffer/compile/return conventions of libxsmm_amd_csr_kernel_source). */
 LIBXSMM_API int libxsmm_amd_spgemm_source(const libxsmm_gemm_descriptor* descriptor, int is_csr, const unsigned int* row_idx,
   const unsigned int* column_idx, int fma, char* buffer, size_t buffer_size, int compile);
+/** The text behind libxsmm_create_{xcsr,xcsc,rm_ac,rm_bc}_soa as a translation unit (kernel "xsmm_spgemm_op"), same conventions.
+ *  form: 0 = CSR (ptr = row pointers, idx = columns), 1 = CSC (ptr = column pointers, idx = rows), 2 = rm_ac, 3 = rm_bc (ptr, idx
+ *  ignored). The kernels the library launches are fused multiply-add (fma != 0); fma == 0 yields the same statements as multiply,
+ *  then add -- for checks of the text on another compiler. Returns -1 where libxsmm_create_*_soa would return no kernel. */
+LIBXSMM_API int libxsmm_amd_soa_source(const libxsmm_gemm_descriptor* descriptor, int form, const unsigned int* ptr, const unsigned int* idx,
+  int fma, char* buffer, size_t buffer_size, int compile);
 
 /** The MatrixMarket coordinate reader that libxsmm_generator_spgemm uses for its input file (reference:
  *  libxsmm_sparse_csr_reader / libxsmm_sparse_csc_reader, src/generator_spgemm_csr_reader.c:46-170 and

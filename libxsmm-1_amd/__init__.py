@@ -305,6 +305,7 @@ def _declare(L):
     sig("libxsmm_amd_spgemm_execute_batch", i, vp, vp, vp, vp, ll, ll, ll)
     sig("libxsmm_amd_spgemm_destroy", None, vp)
     sig("libxsmm_amd_spgemm_source", i, vp, i, vp, vp, i, vp, C.c_size_t, i)
+    sig("libxsmm_amd_soa_source", i, vp, i, vp, vp, i, vp, C.c_size_t, i)
     sig("libxsmm_amd_smm_kernel_source", i, vp, i, vp, C.c_size_t, i)
     sig("libxsmm_amd_device_malloc", vp, C.c_size_t)
     sig("libxsmm_amd_device_free", None, vp)

@@ -102,57 +102,68 @@ unsigned read_coordinate_file(const char* path, bool csr, std::vector<unsigned>&
 enum SpKind { SP_CSR_ASPARSE = 0, SP_CSC_BSPARSE = 1, SP_CSC_ASPARSE = 2,
               SP_SOA_ASPARSE = 3, SP_SOA_BSPARSE = 4, SP_SOA_RM_AC = 5, SP_SOA_RM_BC = 6 }; // SOA: [row][col][v] operands
 
-struct SpShape { int typesize, m, n, k, lda, ldb, ldc, beta0, v; }; // v: SOA width (0: plain matrices)
+// The leading dimensions are 64-bit: a descriptor holds them as unsigned int, and every element offset the text carries is a
+// product with one of them (row * ld, row * ld * v), which passes 2^31 long before the leading dimension itself does.
+struct SpShape { int typesize, m, n, k; long long lda, ldb, ldc; int beta0, v; }; // v: SOA width (0: plain matrices)
 
 const char* tname(int typesize) { return 8 == typesize ? "double" : "float"; }
 
 // threads per item
-int sp_lanes(SpKind kind, const SpShape& s)
+long long sp_lanes(SpKind kind, const SpShape& s)
 {
   switch (kind) {
-    case SP_CSR_ASPARSE: return (0 != s.beta0 ? s.ldc : s.n); // beta == 0 clears ldc (not n) entries per row (:79)
+    case SP_CSR_ASPARSE: return (0 != s.beta0 ? s.ldc : (long long)s.n); // beta == 0 clears ldc (not n) entries per row (:79)
     case SP_CSC_BSPARSE: return s.m;
     case SP_CSC_ASPARSE: return s.n;
-    case SP_SOA_ASPARSE: case SP_SOA_RM_BC: return s.n * s.v; // one thread per (column, run)
-    default: return s.m * s.v;                                 // SP_SOA_BSPARSE, SP_SOA_RM_AC: one thread per (row, run)
+    case SP_SOA_ASPARSE: case SP_SOA_RM_BC: return (long long)s.n * s.v; // one thread per (column, run)
+    default: return (long long)s.m * s.v;                                 // SP_SOA_BSPARSE, SP_SOA_RM_AC: one thread per (row, run)
   }
 }
+
+// An element offset as it stands in the text. span: the largest int the text adds to the literal within the same index
+// expression (`b[off + n]`: the item's last lane; 0 where the literal stands alone or is multiplied by a 64-bit index). A plain
+// literal where an int holds offset + span (the text of ordinary leading dimensions is what it always was), an LL literal
+// otherwise: the sum around it is then 64-bit as a whole, also for a row that begins a few lanes below 2^31.
+std::string off(long long v, long long span = 0) { return fmt(v + span > 0x7fffffffLL ? "%lldLL" : "%lld", v); }
+
+// the lane of a thread within its item is an int in the text (a descriptor's extents fit one, n * v or m * v of an SOA item may not)
+bool shape_fits(SpKind kind, const SpShape& s) { return sp_lanes(kind, s) <= 0x7fffffffLL; }
 
 // ---- SOA kernels (EDGE/SeisSol fused runs): element-wise in the innermost index v ---------------------------------------
 // reference: src/generator_spgemm_csr_asparse_soa.c:212-330 (rows of A without non-zeros are left alone),
 // src/generator_spgemm_csc_bsparse_soa.c:177-420 and src/generator_spgemm_csr_bsparse_soa.c:160-330 (every C column is
 // loaded or zeroed and stored; per k the first pattern entry (k, n) contributes), src/generator_gemm_rm_{ac,bc}_soa.c.
 // All of them: register accumulator seeded with C (or 0), fused multiply-add, k ascending.
-struct SoaEntry { unsigned k, p; }; // contribution of B(k, n): p indexes the shared operand (values array / plain matrix)
+struct SoaEntry { unsigned k; unsigned long long p; }; // contribution of B(k, n): p indexes the shared operand (values array / plain matrix)
 
 std::string soa_body(SpKind kind, const SpShape& s, const unsigned* ptr, const unsigned* idx, bool csr)
 {
   std::string t;
-  const int lanes = sp_lanes(kind, s), V = s.v;
+  const long long lanes = sp_lanes(kind, s), V = s.v;
   t += "  const long long xs_gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;\n";
-  t += fmt("  const long long xs_item = xs_gid / %d;\n  const int xs_l = (int)(xs_gid - xs_item * %d);\n", lanes, lanes);
+  t += fmt("  const long long xs_item = xs_gid / %lld;\n  const int xs_l = (int)(xs_gid - xs_item * %lld);\n", lanes, lanes);
   t += "  if (xs_item >= batch) return;\n";
   if (SP_SOA_ASPARSE == kind || SP_SOA_RM_BC == kind) { // C[m][n][v] (+)= A(m,k) * B[k][n][v]; thread = (n, v)
     t += "  const T* const b = B + xs_item * stride_dense + xs_l;\n  T* const c = C + xs_item * stride_c + xs_l;\n";
     std::vector<char> used(s.k > 0 ? s.k : 1, 0);
     if (SP_SOA_RM_BC == kind) used.assign(used.size(), 1);
     else for (int m = 0; m < s.m; ++m) for (unsigned p = ptr[m]; p < ptr[m + 1]; ++p) used[idx[p]] = 1;
-    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T b%d = b[%d];\n", k, k * s.ldb * V);
+    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T b%d = b[%s];\n", k, off(k * s.ldb * V).c_str());
     for (int m = 0; m < s.m; ++m) {
       if (SP_SOA_ASPARSE == kind && ptr[m] == ptr[m + 1]) continue; // untouched, also for beta == 0
-      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%d]", m * s.ldc * V).c_str());
+      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%s]", off(m * s.ldc * V).c_str()).c_str());
       if (SP_SOA_ASPARSE == kind) for (unsigned p = ptr[m]; p < ptr[m + 1]; ++p) t += fmt("    acc = XACC(A[%u], b%u, acc);\n", p, idx[p]);
-      else for (int k = 0; k < s.k; ++k) t += fmt("    acc = XACC(A[%d], b%d, acc);\n", m * s.lda + k, k);
-      t += fmt("    c[%d] = acc; }\n", m * s.ldc * V);
+      else for (int k = 0; k < s.k; ++k) t += fmt("    acc = XACC(A[%s], b%d, acc);\n", off(m * s.lda + k).c_str(), k);
+      t += fmt("    c[%s] = acc; }\n", off(m * s.ldc * V).c_str());
     }
   }
   else { // C[m][n][v] (+)= A[m][k][v] * B(k,n); thread = (m, v)
-    t += fmt("  const int xs_m = xs_l / %d, xs_v = xs_l - xs_m * %d;\n", V, V);
-    t += fmt("  const T* const a = A + xs_item * stride_dense + (long long)xs_m * %d + xs_v;\n", s.lda * V);
-    t += fmt("  T* const c = C + xs_item * stride_c + (long long)xs_m * %d + xs_v;\n", s.ldc * V);
+    t += fmt("  const int xs_m = xs_l / %d, xs_v = xs_l - xs_m * %d;\n", s.v, s.v);
+    t += fmt("  const T* const a = A + xs_item * stride_dense + (long long)xs_m * %s + xs_v;\n", off(s.lda * V).c_str());
+    t += fmt("  T* const c = C + xs_item * stride_c + (long long)xs_m * %s + xs_v;\n", off(s.ldc * V).c_str());
     std::vector<std::vector<SoaEntry>> cols(s.n > 0 ? s.n : 1);
     if (SP_SOA_RM_AC == kind) {
-      for (int n = 0; n < s.n; ++n) for (int k = 0; k < s.k; ++k) cols[n].push_back(SoaEntry{ (unsigned)k, (unsigned)(k * s.ldb + n) });
+      for (int n = 0; n < s.n; ++n) for (int k = 0; k < s.k; ++k) cols[n].push_back(SoaEntry{ (unsigned)k, (unsigned long long)(k * s.ldb + n) });
     }
     else if (csr) { // rows of B are k: entries arrive k-ascending per column by construction
       for (int k = 0; k < s.k; ++k) for (unsigned p = ptr[k]; p < ptr[k + 1]; ++p) {
@@ -167,11 +178,11 @@ std::string soa_body(SpKind kind, const SpShape& s, const unsigned* ptr, const u
     }
     std::vector<char> used(s.k > 0 ? s.k : 1, 0);
     for (int n = 0; n < s.n; ++n) for (const SoaEntry& e : cols[n]) used[e.k] = 1;
-    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T a%d = a[%d];\n", k, k * V);
+    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T a%d = a[%s];\n", k, off(k * V).c_str());
     for (int n = 0; n < s.n; ++n) {
-      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%d]", n * V).c_str());
-      for (const SoaEntry& e : cols[n]) t += fmt("    acc = XACC(a%u, B[%u], acc);\n", e.k, e.p);
-      t += fmt("    c[%d] = acc; }\n", n * V);
+      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%s]", off(n * V).c_str()).c_str());
+      for (const SoaEntry& e : cols[n]) t += fmt("    acc = XACC(a%u, B[%s], acc);\n", e.k, off((long long)e.p).c_str());
+      t += fmt("    c[%s] = acc; }\n", off(n * V).c_str());
     }
   }
   return t;
@@ -182,44 +193,46 @@ std::string soa_body(SpKind kind, const SpShape& s, const unsigned* ptr, const u
 std::string spgemm_body(SpKind kind, const SpShape& s, const unsigned* ptr, const unsigned* idx)
 {
   std::string t;
-  const int lanes = sp_lanes(kind, s);
+  const long long lanes = sp_lanes(kind, s);
   t += "  const long long xs_gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;\n";
-  t += fmt("  const long long xs_item = xs_gid / %d;\n  const int xs_l = (int)(xs_gid - xs_item * %d);\n", lanes, lanes);
+  t += fmt("  const long long xs_item = xs_gid / %lld;\n  const int xs_l = (int)(xs_gid - xs_item * %lld);\n", lanes, lanes);
   t += "  if (xs_item >= batch) return;\n";
   if (SP_CSR_ASPARSE == kind) { // row-major: C[m*ldc+n] += A[p] * B[col[p]*ldb+n]
     t += "  const T* const b = B + xs_item * stride_dense;\n  T* const c = C + xs_item * stride_c;\n  const int n = xs_l;\n";
     if (0 != s.beta0 && s.ldc > s.n) {
       t += fmt("  if (n >= %d) { /* beta == 0 clears the padding columns as well */\n", s.n);
-      t += fmt("    for (int m = 0; m < %d; ++m) c[m * %d + n] = (T)0;\n    return;\n  }\n", s.m, s.ldc);
+      t += fmt("    for (int m = 0; m < %d; ++m) c[(long long)m * %s + n] = (T)0;\n    return;\n  }\n", s.m, off(s.ldc).c_str());
     }
+    const long long span = s.n - 1; // what `+ n` adds at most below (the padding lanes have left)
     std::vector<char> used(s.k > 0 ? s.k : 1, 0);
     for (int m = 0; m < s.m; ++m) for (unsigned p = ptr[m]; p < ptr[m + 1]; ++p) if (idx[p] < (unsigned)s.k) used[idx[p]] = 1;
-    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T b%d = b[%d + n];\n", k, k * s.ldb);
+    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T b%d = b[%s + n];\n", k, off(k * s.ldb, span).c_str());
     for (int m = 0; m < s.m; ++m) {
       bool any = false;
       for (unsigned p = ptr[m]; p < ptr[m + 1]; ++p) any = any || (idx[p] < (unsigned)s.k);
       if (!any && 0 == s.beta0) continue;
-      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%d + n]", m * s.ldc).c_str());
+      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%s + n]", off(m * s.ldc, span).c_str()).c_str());
       for (unsigned p = ptr[m]; p < ptr[m + 1]; ++p) if (idx[p] < (unsigned)s.k) t += fmt("    acc = XACC(A[%u], b%u, acc);\n", p, idx[p]);
-      t += fmt("    c[%d + n] = acc; }\n", m * s.ldc);
+      t += fmt("    c[%s + n] = acc; }\n", off(m * s.ldc, span).c_str());
     }
   }
   else if (SP_CSC_BSPARSE == kind) { // column-major: C[n*ldc+m] += A[row[p]*lda+m] * B[p]
     t += "  const T* const a = A + xs_item * stride_dense;\n  T* const c = C + xs_item * stride_c;\n  const int m = xs_l;\n";
+    const long long span = s.m - 1; // what `+ m` adds at most
     std::vector<char> used(s.k > 0 ? s.k : 1, 0);
     for (int n = 0; n < s.n; ++n) for (unsigned p = ptr[n]; p < ptr[n + 1]; ++p) if (idx[p] < (unsigned)s.k) used[idx[p]] = 1;
-    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T a%d = a[%d + m];\n", k, k * s.lda);
+    for (int k = 0; k < s.k; ++k) if (used[k]) t += fmt("  const T a%d = a[%s + m];\n", k, off(k * s.lda, span).c_str());
     for (int n = 0; n < s.n; ++n) {
       bool any = false;
       for (unsigned p = ptr[n]; p < ptr[n + 1]; ++p) any = any || (idx[p] < (unsigned)s.k);
       if (!any && 0 == s.beta0) continue;
-      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%d + m]", n * s.ldc).c_str());
+      t += fmt("  { T acc = %s;\n", 0 != s.beta0 ? "(T)0" : fmt("c[%s + m]", off(n * s.ldc, span).c_str()).c_str());
       for (unsigned p = ptr[n]; p < ptr[n + 1]; ++p) if (idx[p] < (unsigned)s.k) t += fmt("    acc = XACC(a%u, B[%u], acc);\n", idx[p], p);
-      t += fmt("    c[%d + m] = acc; }\n", n * s.ldc);
+      t += fmt("    c[%s + m] = acc; }\n", off(n * s.ldc, span).c_str());
     }
   }
   else { // column-major, A sparse by columns: C[n*ldc+row[p]] += A[p] * B[n*ldb+k]
-    t += fmt("  const T* const b = B + xs_item * stride_dense + (long long)xs_l * %d;\n  T* const c = C + xs_item * stride_c + (long long)xs_l * %d;\n", s.ldb, s.ldc);
+    t += fmt("  const T* const b = B + xs_item * stride_dense + (long long)xs_l * %s;\n  T* const c = C + xs_item * stride_c + (long long)xs_l * %s;\n", off(s.ldb).c_str(), off(s.ldc).c_str());
     std::vector<char> touched(s.m > 0 ? s.m : 1, 0);
     for (int k = 0; k < s.k; ++k) for (unsigned p = ptr[k]; p < ptr[k + 1]; ++p) if (idx[p] < (unsigned)s.m) touched[idx[p]] = 1;
     for (int m = 0; m < s.m; ++m) {
@@ -276,7 +289,7 @@ SpShape shape_of(const libxsmm_gemm_descriptor& d)
 {
   SpShape s;
   s.typesize = (LIBXSMM_GEMM_PRECISION_F64 == LIBXSMM_GETENUM_INP(d.datatype)) ? 8 : 4;
-  s.m = (int)d.m; s.n = (int)d.n; s.k = (int)d.k; s.lda = (int)d.lda; s.ldb = (int)d.ldb; s.ldc = (int)d.ldc;
+  s.m = (int)d.m; s.n = (int)d.n; s.k = (int)d.k; s.lda = (long long)d.lda; s.ldb = (long long)d.ldb; s.ldc = (long long)d.ldc;
   s.beta0 = (0 != (d.flags & LIBXSMM_GEMM_FLAG_BETA_0)) ? 1 : 0;
   s.v = 0;
   return s;
@@ -302,6 +315,7 @@ void emit_sparse(libxsmm_generated_code* io, const libxsmm_gemm_descriptor* d, b
   SpKind kind = SP_CSR_ASPARSE;
   const unsigned e = classify(*d, csr, kind);
   if (0 != e) { fail(io, e); return; }
+  if (!shape_fits(kind, shape_of(*d))) { fail(io, ERR_SPGEMM_GEN); return; }
   // CSR: row_idx is the row-pointer array, column_idx the column of each entry; CSC: column_idx is the column-pointer
   // array, row_idx the row of each entry (argument naming of the reference, src/generator_spgemm.c:55-60)
   append(io, spgemm_body(kind, shape_of(*d), csr ? row_idx : column_idx, csr ? column_idx : row_idx));
@@ -521,8 +535,8 @@ struct libxsmm_amd_spgemm {
   JitKernel* kernel;
   SpKind kind;
   SpShape shape;
-  unsigned nnz;
-  int lanes;
+  size_t nnz;      // elements of the shared operand (0: a pattern without entries; nothing is staged for it)
+  long long lanes;
 };
 
 LIBXSMM_API libxsmm_amd_spgemm* libxsmm_amd_spgemm_create(const libxsmm_gemm_descriptor* descriptor, int is_csr,
@@ -531,8 +545,9 @@ LIBXSMM_API libxsmm_amd_spgemm* libxsmm_amd_spgemm_create(const libxsmm_gemm_des
   if (nullptr == descriptor || nullptr == row_idx || nullptr == column_idx || !supported_precision(*descriptor)) return nullptr;
   SpKind kind = SP_CSR_ASPARSE;
   if (0 != classify(*descriptor, 0 != is_csr, kind)) return nullptr;
-  if (!device_ready()) { fail_no_device("libxsmm_amd_spgemm_create"); return nullptr; }
   const SpShape s = shape_of(*descriptor);
+  if (!shape_fits(kind, s)) return nullptr;
+  if (!device_ready()) { fail_no_device("libxsmm_amd_spgemm_create"); return nullptr; }
   const unsigned* const ptr = (0 != is_csr ? row_idx : column_idx);
   const unsigned* const idx = (0 != is_csr ? column_idx : row_idx);
   const int nmajor = (SP_CSR_ASPARSE == kind ? s.m : (SP_CSC_BSPARSE == kind ? s.n : s.k));
@@ -576,7 +591,10 @@ LIBXSMM_API int libxsmm_amd_spgemm_execute_batch(const libxsmm_amd_spgemm* handl
   const size_t bytes_c = ((size_t)(batch - 1) * (size_t)stride_c + ext_c) * ts;
   const void* dv = sparse_values; const void* dd = dense; void* dc = c;
   const bool c_host = !is_device_ptr(c);
-  if (!is_device_ptr(sparse_values)) { void* t = scratch(0, (size_t)handle->nnz * ts); if (nullptr == t || 0 != h2d(t, sparse_values, (size_t)handle->nnz * ts)) return EXIT_FAILURE; dv = t; }
+  // (a pattern without entries has no values to stage: its kernel holds no statement that reads them, and a request for
+  // 0 bytes of scratch is answered with whatever the slot holds, a null pointer on a thread that never staged anything)
+  const bool stage_values = (0 != handle->nnz && !is_device_ptr(sparse_values));
+  if (stage_values) { void* t = scratch(0, handle->nnz * ts); if (nullptr == t || 0 != h2d(t, sparse_values, handle->nnz * ts)) return EXIT_FAILURE; dv = t; }
   if (!is_device_ptr(dense)) { void* t = scratch(3, bytes_dense); if (nullptr == t || 0 != h2d(t, dense, bytes_dense)) return EXIT_FAILURE; dd = t; }
   if (c_host) { void* t = scratch(5, bytes_c); if (nullptr == t || 0 != h2d(t, c, bytes_c)) return EXIT_FAILURE; dc = t; }
   // argument order of the emitted kernel: (A, B, C, ...) with the sparse operand's values in A (A sparse) or B (B sparse)
@@ -605,6 +623,7 @@ LIBXSMM_API int libxsmm_amd_spgemm_source(const libxsmm_gemm_descriptor* descrip
   SpKind kind = SP_CSR_ASPARSE;
   if (0 != classify(*descriptor, 0 != is_csr, kind)) return -1;
   const SpShape s = shape_of(*descriptor);
+  if (!shape_fits(kind, s)) return -1;
   const std::string src = spgemm_prologue(s.typesize, fma < 0 ? fma_default() : fma) + spgemm_signature("xsmm_spgemm_op")
                         + spgemm_body(kind, s, 0 != is_csr ? row_idx : column_idx, 0 != is_csr ? column_idx : row_idx) + "}\n";
   if (nullptr != buffer && 0 < buffer_size) {
@@ -662,9 +681,9 @@ bool soa_pattern_ok(SpKind kind, const SpShape& s, const unsigned* ptr, const un
   return true;
 }
 
-std::string soa_source(SpKind kind, const SpShape& s, const unsigned* ptr, const unsigned* idx, bool csr, const char* name)
-{
-  return spgemm_prologue(s.typesize, 1/*fma*/) + spgemm_signature(name) + soa_body(kind, s, ptr, idx, csr) + "}\n";
+std::string soa_source(SpKind kind, const SpShape& s, const unsigned* ptr, const unsigned* idx, bool csr, const char* name, int fma = 1)
+{ // (the kernels the library launches are fma; the other arithmetic exists for libxsmm_amd_soa_source)
+  return spgemm_prologue(s.typesize, fma) + spgemm_signature(name) + soa_body(kind, s, ptr, idx, csr) + "}\n";
 }
 
 libxsmm_amd_spgemm* soa_create(const libxsmm_gemm_descriptor* descriptor, int form, const unsigned* ptr, const unsigned* idx)
@@ -675,7 +694,7 @@ libxsmm_amd_spgemm* soa_create(const libxsmm_gemm_descriptor* descriptor, int fo
   SpShape s = shape_of(*descriptor);
   s.v = soa_width(s.typesize);
   const bool csr = (0 == form);
-  if (0 == s.m || 0 == s.n || 0 == s.k || !soa_pattern_ok(kind, s, ptr, idx, csr)) return nullptr;
+  if (0 == s.m || 0 == s.n || 0 == s.k || !shape_fits(kind, s) || !soa_pattern_ok(kind, s, ptr, idx, csr)) return nullptr;
   if (!device_ready()) { fail_no_device("libxsmm_create_*_soa"); return nullptr; }
   std::string log;
   JitKernel* const k = jit_compile(soa_source(kind, s, ptr, idx, csr, "xsmm_spgemm_op"), "xsmm_spgemm_op", &log);
@@ -688,8 +707,8 @@ libxsmm_amd_spgemm* soa_create(const libxsmm_gemm_descriptor* descriptor, int fo
   switch (kind) { // elements of the shared operand (staged when it lives on the host)
     case SP_SOA_ASPARSE: h->nnz = ptr[s.m]; break;
     case SP_SOA_BSPARSE: h->nnz = ptr[csr ? s.k : s.n]; break;
-    case SP_SOA_RM_AC: h->nnz = (unsigned)((s.k - 1) * s.ldb + s.n); break;
-    default: h->nnz = (unsigned)((s.m - 1) * s.lda + s.k); break;
+    case SP_SOA_RM_AC: h->nnz = (size_t)((s.k - 1) * s.ldb + s.n); break; // (64-bit products: SpShape)
+    default: h->nnz = (size_t)((s.m - 1) * s.lda + s.k); break;
   }
   return h;
 }
@@ -717,7 +736,7 @@ void emit_soa(libxsmm_generated_code* io, const libxsmm_gemm_descriptor* d, int 
   const unsigned e = classify_soa(*d, form, kind);
   if (0 != e) { fail(io, e); return; }
   SpShape s = shape_of(*d); s.v = soa_width(s.typesize);
-  if (!soa_pattern_ok(kind, s, ptr, idx, 0 == form)) { fail(io, ERR_SPGEMM_GEN); return; }
+  if (!shape_fits(kind, s) || !soa_pattern_ok(kind, s, ptr, idx, 0 == form)) { fail(io, ERR_SPGEMM_GEN); return; }
   append(io, soa_body(kind, s, ptr, idx, 0 == form));
 }
 
@@ -777,6 +796,30 @@ LIBXSMM_API void libxsmm_generator_spgemm_csc_soa_kernel(libxsmm_generated_code*
 LIBXSMM_API int libxsmm_amd_soa_width(libxsmm_gemm_precision precision)
 {
   return LIBXSMM_GEMM_PRECISION_F64 == precision ? 8 : (LIBXSMM_GEMM_PRECISION_F32 == precision ? 16 : 0);
+}
+
+LIBXSMM_API int libxsmm_amd_soa_source(const libxsmm_gemm_descriptor* descriptor, int form, const unsigned int* ptr, const unsigned int* idx,
+  int fma, char* buffer, size_t buffer_size, int compile)
+{ // the text soa_create compiles (form: 0 CSR, 1 CSC, 2 rm_ac, 3 rm_bc); conventions of libxsmm_amd_spgemm_source
+  if (nullptr == descriptor || !supported_precision(*descriptor) || form < 0 || form > 3) return -1;
+  SpKind kind = SP_SOA_ASPARSE;
+  if (0 != classify_soa(*descriptor, form, kind)) return -1;
+  SpShape s = shape_of(*descriptor);
+  s.v = soa_width(s.typesize);
+  const bool csr = (0 == form);
+  if (0 == s.m || 0 == s.n || 0 == s.k || !shape_fits(kind, s) || !soa_pattern_ok(kind, s, ptr, idx, csr)) return -1;
+  const std::string src = soa_source(kind, s, ptr, idx, csr, "xsmm_spgemm_op", 0 != fma ? 1 : 0);
+  if (nullptr != buffer && 0 < buffer_size) {
+    const size_t n = (src.size() < buffer_size - 1 ? src.size() : buffer_size - 1);
+    memcpy(buffer, src.data(), n); buffer[n] = 0;
+  }
+  if (0 != compile) {
+    std::string log;
+    const int rc = jit_check_source(src, &log);
+    if (0 != rc && 0 != libxsmm_verbosity) fprintf(stderr, "LIBXSMM-AMD: hiprtc: %s\n", log.c_str());
+    return rc;
+  }
+  return (int)src.size();
 }
 
 LIBXSMM_API int libxsmm_amd_kernel_execute_batch(const void* kernel, const void* a, const void* b, void* c,
