@@ -246,6 +246,8 @@ int launch(Packed& p, int form, const void* a, const void* b, void* c, long long
   *name = launch_name(s, form, nullptr != ring);
   JitKernel* const k = kernel_of(p, form);
   if (nullptr == k) return -1; // a missing kernel is an error, there is no other path
+  // (the grid is never clamped: a launch beyond 2^31 - 1 blocks is refused below. The form-1 kernel has a grid-stride loop over groups of G
+  // packs, but with one block per group it takes exactly one trip; form 2 has a lane per matrix and no loop)
   const long long blocks = (1 == form) ? (npacks + s.G - 1) / s.G : (npacks * s.vlen + 255) / 256;
   if (blocks < 1 || blocks > 0x7fffffffLL) return -1;
   void* args[] = { (void*)&a, (void*)&b, (void*)&c, (void*)&npacks, (void*)&count, (void*)&ring };

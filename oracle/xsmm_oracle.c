@@ -869,3 +869,167 @@ int xo_gemm_lowp(int kind, int beta0, int m, int n, int k, int lda, int ldb, int
   }
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------------
+ * packed ("compact") kernels: pgemm, getrf, trmm, trsm over packs of vlen interleaved matrices
+ * (descriptors: src/libxsmm_main.h:193-226). Written from this project's contract, in
+ * place on the packed buffers: element (i, j) of matrix v of pack p lies at
+ *   ((p * nl + line) * ld + within) * vlen + v
+ * with (line, within) = (j, i) for layout 102 (column major) and (i, j) for 101, nl the number of
+ * lines of the operand as it is stored. A loop per matrix; every statement is one rounded operation,
+ * fma()/fmaf() written out. What lies between the extent of a line and ld, and the triangle that is
+ * not referenced (the diagonal of a unit triangle included), is neither read nor written.
+ *   pgemm  c(i,j) = fma(+-opa(i,l), opb(l,j), c(i,j)) for l ascending (alpha = -1 negates the element of A)
+ *   getrf  for c: rinv = 1 / w(c,c); for r > c: l = w(r,c) * rinv, stored; for j > c: w(r,j) = fma(-l, w(c,j), w(r,j))
+ *   trsm   E = op(A) (side L: the vectors are the columns of B) or its transpose (side R: the rows of B);
+ *          x = alpha b (copy, negation, or one multiply); the columns c of E in elimination order;
+ *          non-unit: x[c] = x[c] * (1 / E(c,c)); for the r of the triangle, ascending: x[r] = fma(-E(r,c), x[c], x[r])
+ *   trmm   s = E(r,r) * x[r] (unit: x[r]); for the c of the triangle, ascending: s = fma(E(r,c), x[c], s);
+ *          the result is alpha s (copy, negation, or one multiply)
+ * Return 0, or -1 for arguments outside the domain (nothing is touched then).
+ * ------------------------------------------------------------------------------------------------ */
+static int xo_is(char c, char u) { return u == c || (char)(u | 0x20) == c; }
+
+#define XO_PK_AT(BASE, P, NL, LD, I, J) \
+  (BASE)[(((size_t)(P) * (size_t)(NL) + (size_t)(rowmajor ? (I) : (J))) * (size_t)(LD) + (size_t)(rowmajor ? (J) : (I))) * (size_t)vlen + (size_t)v]
+
+#define XO_DEFINE_PACKED(SUFFIX, T, FMAF)                                                               \
+static T xo_pk_alpha_##SUFFIX(int alpha_kind, T alpha, T x)                                             \
+{                                                                                                       \
+  if (0 == alpha_kind) return x;                                                                        \
+  if (1 == alpha_kind) return -x;                                                                       \
+  return alpha * x;                                                                                     \
+}                                                                                                       \
+static void xo_pk_pgemm_##SUFFIX(int vlen, int rowmajor, int m, int n, int k, int lda, int ldb, int ldc, \
+  int ta, int tb, int negate, const T* a, const T* b, T* c, long long npacks)                           \
+{                                                                                                       \
+  const int a_nl = rowmajor ? (ta ? k : m) : (ta ? m : k);                                              \
+  const int b_nl = rowmajor ? (tb ? n : k) : (tb ? k : n);                                              \
+  const int c_nl = rowmajor ? m : n;                                                                    \
+  long long p; int v, i, j, l;                                                                          \
+  for (p = 0; p < npacks; ++p) for (v = 0; v < vlen; ++v) {                                             \
+    for (i = 0; i < m; ++i) for (j = 0; j < n; ++j) {                                                   \
+      T acc = XO_PK_AT(c, p, c_nl, ldc, i, j);                                                          \
+      for (l = 0; l < k; ++l) {                                                                         \
+        const T av = ta ? XO_PK_AT(a, p, a_nl, lda, l, i) : XO_PK_AT(a, p, a_nl, lda, i, l);            \
+        const T bv = tb ? XO_PK_AT(b, p, b_nl, ldb, j, l) : XO_PK_AT(b, p, b_nl, ldb, l, j);            \
+        acc = FMAF(negate ? -av : av, bv, acc);                                                         \
+      }                                                                                                 \
+      XO_PK_AT(c, p, c_nl, ldc, i, j) = acc;                                                            \
+    }                                                                                                   \
+  }                                                                                                     \
+}                                                                                                       \
+static void xo_pk_getrf_##SUFFIX(int vlen, int rowmajor, int m, int n, int lda, T* a, long long npacks) \
+{                                                                                                       \
+  const int nl = rowmajor ? m : n, mn = (m < n ? m : n);                                                \
+  long long p; int v, c, r, j;                                                                          \
+  for (p = 0; p < npacks; ++p) for (v = 0; v < vlen; ++v) {                                             \
+    for (c = 0; c < mn; ++c) {                                                                          \
+      const T rinv = (T)1 / XO_PK_AT(a, p, nl, lda, c, c);                                              \
+      for (r = c + 1; r < m; ++r) {                                                                     \
+        const T l = XO_PK_AT(a, p, nl, lda, r, c) * rinv;                                               \
+        XO_PK_AT(a, p, nl, lda, r, c) = l;                                                              \
+        for (j = c + 1; j < n; ++j)                                                                     \
+          XO_PK_AT(a, p, nl, lda, r, j) = FMAF(-l, XO_PK_AT(a, p, nl, lda, c, j), XO_PK_AT(a, p, nl, lda, r, j)); \
+      }                                                                                                 \
+    }                                                                                                   \
+  }                                                                                                     \
+}                                                                                                       \
+/* E(r,c) and the vector element x[r] of vector q, for one matrix v of pack p */                        \
+static void xo_pk_tr_##SUFFIX(int solve, int vlen, int rowmajor, int m, int n, int lda, int ldb,        \
+  int side_r, int upper, int ta, int unit, int alpha_kind, T alpha, const T* a, T* b, long long npacks) \
+{                                                                                                       \
+  const int nt = side_r ? n : m, nv = side_r ? m : n;                                                   \
+  const int teff = (ta ? 1 : 0) ^ (side_r ? 1 : 0), lower = (upper ? 0 : 1) ^ teff;                     \
+  const int b_nl = rowmajor ? m : n;                                                                    \
+  T* const x = (T*)malloc(sizeof(T) * (size_t)(nt > 0 ? nt : 1));                                       \
+  long long p; int v, q, r, c, cc;                                                                      \
+  for (p = 0; p < npacks; ++p) for (v = 0; v < vlen; ++v) for (q = 0; q < nv; ++q) {                    \
+    for (r = 0; r < nt; ++r) x[r] = side_r ? XO_PK_AT(b, p, b_nl, ldb, q, r) : XO_PK_AT(b, p, b_nl, ldb, r, q); \
+    if (solve) {                                                                                        \
+      for (r = 0; r < nt; ++r) x[r] = xo_pk_alpha_##SUFFIX(alpha_kind, alpha, x[r]);                    \
+      for (cc = 0; cc < nt; ++cc) {                                                                     \
+        c = lower ? cc : nt - 1 - cc;                                                                   \
+        if (!unit) {                                                                                    \
+          const T rinv = (T)1 / XO_PK_AT(a, p, nt, lda, c, c);                                          \
+          x[c] = x[c] * rinv;                                                                           \
+        }                                                                                               \
+        for (r = (lower ? c + 1 : 0); r < (lower ? nt : c); ++r) {                                      \
+          const T e = teff ? XO_PK_AT(a, p, nt, lda, c, r) : XO_PK_AT(a, p, nt, lda, r, c);             \
+          x[r] = FMAF(-e, x[c], x[r]);                                                                  \
+        }                                                                                               \
+      }                                                                                                 \
+      for (r = 0; r < nt; ++r) {                                                                        \
+        if (side_r) XO_PK_AT(b, p, b_nl, ldb, q, r) = x[r]; else XO_PK_AT(b, p, b_nl, ldb, r, q) = x[r]; \
+      }                                                                                                 \
+    }                                                                                                   \
+    else {                                                                                              \
+      for (r = 0; r < nt; ++r) {                                                                        \
+        T s = x[r];                                                                                     \
+        if (!unit) s = XO_PK_AT(a, p, nt, lda, r, r) * x[r];                                            \
+        for (c = (lower ? 0 : r + 1); c < (lower ? r : nt); ++c) {                                      \
+          const T e = teff ? XO_PK_AT(a, p, nt, lda, c, r) : XO_PK_AT(a, p, nt, lda, r, c);             \
+          s = FMAF(e, x[c], s);                                                                         \
+        }                                                                                               \
+        s = xo_pk_alpha_##SUFFIX(alpha_kind, alpha, s);                                                 \
+        if (side_r) XO_PK_AT(b, p, b_nl, ldb, q, r) = s; else XO_PK_AT(b, p, b_nl, ldb, r, q) = s;      \
+      }                                                                                                 \
+    }                                                                                                   \
+  }                                                                                                     \
+  free(x);                                                                                              \
+}
+XO_DEFINE_PACKED(f64, double, fma)
+XO_DEFINE_PACKED(f32, float, fmaf)
+
+static int xo_pk_ok(int typesize, int vlen, int layout, int rows, int cols, int ld)
+{
+  return (4 == typesize || 8 == typesize) && 1 <= vlen && (101 == layout || 102 == layout) && 1 <= rows && 1 <= cols
+    && (101 == layout ? cols : rows) <= ld;
+}
+
+int xo_packed_pgemm(int typesize, int vlen, int layout, int m, int n, int k, int lda, int ldb, int ldc,
+                    char transa, char transb, double alpha, const void* a, const void* b, void* c, long long npacks)
+{
+  const int ta = xo_is(transa, 'T'), tb = xo_is(transb, 'T');
+  if ((!ta && !xo_is(transa, 'N')) || (!tb && !xo_is(transb, 'N')) || (1.0 != alpha && -1.0 != alpha)) return -1;
+  if (NULL == a || NULL == b || NULL == c || npacks < 0) return -1;
+  if (!xo_pk_ok(typesize, vlen, layout, ta ? k : m, ta ? m : k, lda) || !xo_pk_ok(typesize, vlen, layout, tb ? n : k, tb ? k : n, ldb)
+    || !xo_pk_ok(typesize, vlen, layout, m, n, ldc)) return -1;
+  if (8 == typesize) xo_pk_pgemm_f64(vlen, 101 == layout, m, n, k, lda, ldb, ldc, ta, tb, -1.0 == alpha, (const double*)a, (const double*)b, (double*)c, npacks);
+  else xo_pk_pgemm_f32(vlen, 101 == layout, m, n, k, lda, ldb, ldc, ta, tb, -1.0 == alpha, (const float*)a, (const float*)b, (float*)c, npacks);
+  return 0;
+}
+
+int xo_packed_getrf(int typesize, int vlen, int layout, int m, int n, int lda, void* a, long long npacks)
+{
+  if (NULL == a || npacks < 0 || !xo_pk_ok(typesize, vlen, layout, m, n, lda)) return -1;
+  if (8 == typesize) xo_pk_getrf_f64(vlen, 101 == layout, m, n, lda, (double*)a, npacks);
+  else xo_pk_getrf_f32(vlen, 101 == layout, m, n, lda, (float*)a, npacks);
+  return 0;
+}
+
+static int xo_packed_tr(int solve, int typesize, int vlen, int layout, int m, int n, int lda, int ldb,
+                        char side, char uplo, char transa, char diag, double alpha, const void* a, void* b, long long npacks)
+{
+  const int side_r = xo_is(side, 'R'), upper = xo_is(uplo, 'U'), ta = xo_is(transa, 'T'), unit = xo_is(diag, 'U');
+  const int nt = side_r ? n : m;
+  const int alpha_kind = (1.0 == alpha ? 0 : (-1.0 == alpha ? 1 : 2));
+  if ((!side_r && !xo_is(side, 'L')) || (!upper && !xo_is(uplo, 'L')) || (!ta && !xo_is(transa, 'N')) || (!unit && !xo_is(diag, 'N'))) return -1;
+  if (NULL == a || NULL == b || npacks < 0 || !(alpha - alpha == 0.0)) return -1;
+  if (!xo_pk_ok(typesize, vlen, layout, nt, nt, lda) || !xo_pk_ok(typesize, vlen, layout, m, n, ldb)) return -1;
+  if (8 == typesize) xo_pk_tr_f64(solve, vlen, 101 == layout, m, n, lda, ldb, side_r, upper, ta, unit, alpha_kind, alpha, (const double*)a, (double*)b, npacks);
+  else xo_pk_tr_f32(solve, vlen, 101 == layout, m, n, lda, ldb, side_r, upper, ta, unit, alpha_kind, (float)alpha, (const float*)a, (float*)b, npacks);
+  return 0;
+}
+
+int xo_packed_trmm(int typesize, int vlen, int layout, int m, int n, int lda, int ldb,
+                   char side, char uplo, char transa, char diag, double alpha, const void* a, void* b, long long npacks)
+{
+  return xo_packed_tr(0, typesize, vlen, layout, m, n, lda, ldb, side, uplo, transa, diag, alpha, a, b, npacks);
+}
+
+int xo_packed_trsm(int typesize, int vlen, int layout, int m, int n, int lda, int ldb,
+                   char side, char uplo, char transa, char diag, double alpha, const void* a, void* b, long long npacks)
+{
+  return xo_packed_tr(1, typesize, vlen, layout, m, n, lda, ldb, side, uplo, transa, diag, alpha, a, b, npacks);
+}

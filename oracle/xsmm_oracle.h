@@ -164,6 +164,21 @@ void xo_bgemm_st(int arith, const xo_bgemm* h, const void* a, const void* b, voi
 int xo_gemm_lowp(int kind, int beta0, int m, int n, int k, int lda, int ldb, int ldc,
                  const unsigned short* a, const unsigned short* b, void* c, float scf);
 
+/* ---- packed ("compact") kernels (libxsmm_dispatch_pgemm / getrf / trmm / trsm; descriptors src/libxsmm_main.h:193-226) ----
+ * In place on the packed buffers: element (i, j) of matrix v of pack p at ((p * nl + line) * ld + within) * vlen + v, a line
+ * being a column (layout 102) or a row (101) and nl the number of lines of the operand as stored (A of pgemm under transa:
+ * k x m). typesize 8 -> double, 4 -> float (alpha is narrowed to the type). One fixed order of operations per element, fma
+ * written out, the rounded reciprocal of the pivot, alpha = +-1 without a rounding: the contract of DESIGN.md 8a, stated in
+ * xsmm_oracle.c. Padding (ld beyond the extent of a line), the strict other triangle and the diagonal of a unit triangle are
+ * neither read nor written. pgemm takes alpha = 1 or -1 only. Return 0, or -1 for arguments outside the domain. */
+int xo_packed_pgemm(int typesize, int vlen, int layout, int m, int n, int k, int lda, int ldb, int ldc,
+                    char transa, char transb, double alpha, const void* a, const void* b, void* c, long long npacks);
+int xo_packed_getrf(int typesize, int vlen, int layout, int m, int n, int lda, void* a, long long npacks);
+int xo_packed_trmm(int typesize, int vlen, int layout, int m, int n, int lda, int ldb,
+                   char side, char uplo, char transa, char diag, double alpha, const void* a, void* b, long long npacks);
+int xo_packed_trsm(int typesize, int vlen, int layout, int m, int n, int lda, int ldb,
+                   char side, char uplo, char transa, char diag, double alpha, const void* a, void* b, long long npacks);
+
 /* ---- input generators used by the reference's samples ---- */
 /* LIBXSMM_MATINIT, seed != 0 branch (include/libxsmm_frontend.h:414-431) */
 void xo_matinit_f64(int seed, double* dst, int nrows, int ncols, int ld, double scale);

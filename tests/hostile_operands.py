@@ -1,5 +1,6 @@
 """What tests/test_hostile_operands_{cpu,gpu}.py share: operands whose surroundings are poisoned, operand values at the
-edges of the number line, and the comparison that goes with them.
+edges of the number line, and the comparison that goes with them. The packed kernels' hostile matrices (packed_hostile(), at the
+end of the file) serve tests/test_packed_hostile_gpu.py and tests/test_packed_chain_cpu.py.
 
 Layout. An operand is a batch of column-major matrices inside one flat array: a guard band of GUARD elements in front and
 behind, leading dimensions of extent + 3, and (where a call takes strides) items that lie size + 4 or size + 1 elements
@@ -616,3 +617,259 @@ LOWP_CASES = [
     LowpCase("lowp-bf16f32-32-reduce", 2, (32, 32, 32), 3, "smm_bf16f32_reduce_lowp", reduce=True, extras=(8, 4, 1)),
     LowpCase("lowp-bf16-32-reduce", 3, (32, 32, 32), 3, "smm_bf16_reduce_lowp", reduce=True, extras=(8, 4, 1)),
 ]
+
+
+# ---- the packed kernels (pgemm, getrf, trmm, trsm): hostile matrices in three lanes of every pack ----------------------------------
+PACKED_PACKS = 3
+
+
+def packed_cases():
+    """(op, format, size) of every descriptor of tests/test_packed_hostile_gpu.py: 8 (register-resident; pgemm 8 x 8 x 8) and 16 (the
+    in-place loops) per operation and type. The descriptor does not depend on the kind of values."""
+    import packed_common as pc
+    return [(op, fmt, size) for op in (pc.PGEMM, pc.GETRF, pc.TRMM, pc.TRSM) for fmt in ("f32", "f64") for size in (8, 16)]
+
+
+def packed_case(op, fmt, size):
+    """the benign case of a descriptor (tests/packed_common.py:Case, three packs). Layout, alpha, side / uplo / trans rotate with the
+    format and the size so that every operation sees both layouts and every alpha it takes; triangles are non-unit."""
+    import packed_common as pc
+    fi, si = ("f32", "f64").index(fmt), (8, 16).index(size)
+    j = 2 * fi + si
+    layout = pc.COL if fi == si else pc.ROW
+    kw = dict(layout=layout, nmat=PACKED_PACKS * pc.width(np_dtype(fmt)), seed=seed_of("packed", op, fmt, size) % (2 ** 31))
+    if op == pc.PGEMM:
+        ta, tb = (("N", "N"), ("T", "N"), ("N", "T"), ("T", "T"))[j]
+        return pc.Case(op, np_dtype(fmt), size, size, size, transa=ta, transb=tb, alpha=(1.0, -1.0)[(j + j // 2) % 2], **kw)
+    if op == pc.GETRF:
+        return pc.Case(op, np_dtype(fmt), size, size, **kw)
+    side, uplo, trans = (("L", "L", "N"), ("R", "U", "N"), ("L", "U", "T"), ("R", "L", "T"))[(j + (1 if op == pc.TRMM else 0)) % 4]
+    return pc.Case(op, np_dtype(fmt), size, size, side=side, uplo=uplo, transa=trans, diag="N", alpha=(1.0, -1.0, 0.75)[(j + op) % 3], **kw)
+
+
+def packed_hostile_lanes(case):
+    """indexes (into the case's nmat matrices) of lanes 1, VLEN / 2 and VLEN - 1 of every pack"""
+    v = 64 // case.dtype.itemsize
+    return np.array([p * v + lane for p in range(case.nmat // v) for lane in (1, v // 2, v - 1)])
+
+
+class _Tri(object):
+    """the effective triangle E (op(A) for side L, its transpose for side R) and the vectors (columns of B for side L, rows for
+    side R) of a trmm / trsm case, addressed as the kernels' contract states them"""
+
+    def __init__(self, case):
+        self.side_r = case.side == "R"
+        self.teff = (case.transa == "T") ^ self.side_r
+        self.lower = (case.uplo == "L") ^ self.teff
+        self.nt = case.n if self.side_r else case.m
+        self.nv = case.m if self.side_r else case.n
+        self.order = list(range(self.nt)) if self.lower else list(range(self.nt - 1, -1, -1))  # elimination order of trsm
+
+    def e(self, r, c):
+        return (c, r) if self.teff else (r, c)
+
+    def v(self, r, q):
+        return (q, r) if self.side_r else (r, q)
+
+    def triangle(self):
+        """[(r, c)] of the strict triangle of E"""
+        return [(r, c) for r in range(self.nt) for c in range(self.nt) if (c < r if self.lower else c > r)]
+
+
+def packed_hostile(case, kind):
+    """a copy of `case` whose lanes packed_hostile_lanes() hold hostile matrices of `kind`; everything else (the benign lanes, the
+    NaN in what a triangle never reads) stays. Per operation, hostile matrix h = 0 ... 8 takes recipe h modulo the number of recipes:
+
+    specials   pgemm: operands("specials") (its -0.0 row of A takes the sign that alpha = -1 turns into -0.0).
+               getrf: (0) NaN in the last element, Inf in the first line; (1) a(0,0) = 0; (2) an all-zero row 2 against an Inf in the
+               last column of row 0; (3) -0.0 in the last element of column 0 (l = -0.0 is stored).
+               trsm: (0) NaN in the last element of B, Inf in its first line; (1) t(1,1) = 0; (2) a triangle whose off-diagonal entries
+               are all zero against an Inf in the first unknown of a vector; (3) a vector of -0.0 and a vector of +0.0 (alpha = 1, -1
+               or 0.75 and the sign of the pivot decide which of the two ends as -0.0).
+               trmm: (0) as trsm; (1) an all-zero triangle (diagonal included) against an Inf in B: 0 * Inf in one vector, signed zeros
+               in all others; (2) the two vectors of zeros.
+    underflow  pgemm: operands("underflow"). The others: matrix 0 has the pivot 1.5 * 2^(emin - 1) (subnormal, its reciprocal finite and
+               inexact), matrix 1 the pivot 2^(emin - 4) (its reciprocal is Inf) -- getrf a(0,0), trsm t(1,1); trmm, which has no pivot,
+               takes these two as entries of the diagonal. All other matrices are the benign ones with their vectors (getrf: the columns
+               of A) scaled by powers of two, so that X, C or U land among the subnormals and round there.
+               Changed against the first recipe (one scale of 2^(emin + 2) for a whole matrix), which left fewer than a quarter of the
+               results subnormal: the vectors alternate between 2^(emin - 4) and 2^(emin + 4) (getrf: seven columns of eight at
+               2^(emin - 2), where the reciprocal of every pivot stays finite, the eighth at 2^(emin + 4)), and seven of the nine
+               matrices are of this kind.
+    overflow   pgemm: operands("overflow"), and in matrix 0 a triple whose product 2^(emax + 1) overflows on its own while the fused
+               result 2^emax is finite. The others: matrix 0 holds such a triple where the kernel has its fma (getrf: the update of
+               w(1,1); trsm: the first update of the second unknown; trmm: the first term after the diagonal), in benign surroundings;
+               the other matrices have entries of one sign per vector but for one in eight, and chains that pass 2^(emax + 1) in some
+               elements and stay finite in others. Changed against the first recipe (benign matrices scaled to 2^(emax - 7) ...
+               2^(emax + 1)), which left fewer than an eighth of the results Inf: trmm takes a positive triangle in 1 ... 2 and vectors at
+               2^(emax - 3) ... 2^emax; trsm a diagonal in 0.5 ... 1 and a negative triangle, so that the unknowns of a vector grow with
+               one sign; getrf a left half that is nearly lower triangular with l in -4 ... -1 and a positive right half at 2^(emax - 1)
+               and 2^emax, whose updates all add (the comments in the code give the details)."""
+    import copy
+    import packed_common as pc
+    assert kind in KINDS
+    fmt = fmt_of(case.dtype)
+    emin, emax, p = RANGE[fmt]
+    half = (emax + 1) // 2
+    out = copy.copy(case)
+    ops = {name: x.astype(np.float64) for name, x in case.ops.items()}
+    lanes = packed_hostile_lanes(case)
+    rng = np.random.default_rng(seed_of("packed-hostile", case.kind, fmt, case.m, kind))
+    m, n = case.m, case.n
+    alpha = case.alpha
+    sgn = 1.0 if alpha > 0 else -1.0
+    if case.kind == pc.PGEMM:
+        k = case.k
+        a, b, c = operands(kind, fmt, seed_of("packed-hostile", fmt, case.m, kind), len(lanes), m, n, k)
+        a, b, c = a.astype(np.float64), b.astype(np.float64), c.astype(np.float64)
+        if kind == "specials":
+            for t in range(len(lanes)):
+                if np.all(a[t, 1, :] == 0) and np.all(np.signbit(a[t, 1, :])):
+                    a[t, 1, :] *= alpha  # (alpha = -1: +0.0, which the kernel negates)
+        elif kind == "overflow":
+            a[0, m - 1, :] = 0.0
+            a[0, m - 1, 0] = alpha * 2.0 ** half
+            b[0, 0, n - 1] = 2.0 ** half
+            c[0, m - 1, n - 1] = -2.0 ** emax
+        ops["a"][lanes] = a.transpose(0, 2, 1) if case.transa == "T" else a
+        ops["b"][lanes] = b.transpose(0, 2, 1) if case.transb == "T" else b
+        ops["c"][lanes] = c
+    elif case.kind == pc.GETRF:
+        a = ops["a"]
+        for h, t in enumerate(lanes):
+            if kind == "specials":
+                r = h % 4
+                if r == 0:
+                    a[t, m - 1, n - 1] = np.nan
+                    if case.layout == pc.COL:
+                        a[t, m // 2, 0] = np.inf
+                    else:
+                        a[t, 0, n // 2] = np.inf
+                elif r == 1:
+                    a[t, 0, 0] = 0.0
+                elif r == 2:
+                    a[t, 2, :] = 0.0
+                    a[t, 0, n - 1] = np.inf
+                else:
+                    a[t, 0, 0] = abs(a[t, 0, 0])
+                    a[t, m - 1, 0] = -0.0
+            elif kind == "underflow":
+                if h == 0:
+                    a[t, 0, 0] = 1.5 * 2.0 ** (emin - 1)
+                elif h == 1:
+                    a[t, 0, 0] = 2.0 ** (emin - 4)
+                else:
+                    a[t] *= np.exp2(np.where(np.arange(n) % 8 != 7, emin - 2, emin + 4).astype(np.float64))[None, :]
+            else:
+                if h == 0:
+                    a[t, 0, 0], a[t, 1, 0], a[t, 0, 1], a[t, 1, 1] = 1.0, -2.0 ** half, 2.0 ** half, -2.0 ** emax
+                else:
+                    # the left half of the columns is nearly lower triangular -- a diagonal in 0.25 ... 0.5, -0.5 ... -1 below it, 2^-10
+                    # above it --, so that every l is negative, 1 ... 4 in magnitude, and stays so; the right half is positive but for one
+                    # sign in eight, at 2^emax and 2^(emax - 1) in turn: its updates all add, the chains pass 2^(emax + 1) from the second
+                    # or third row on and stay +Inf (the rows below the first pivot that is Inf end as NaN, whatever a kernel does)
+                    nl = n // 2
+                    rr, cc = np.arange(m)[:, None], np.arange(n)[None, :]
+                    mag = rng.uniform(0.5, 1.0, (m, n))
+                    left = np.where(rr > cc, -mag, np.where(rr == cc, 0.5 * mag, mag * 2.0 ** -10))
+                    right = mag * np.where(rng.integers(0, 8, (m, n)) == 0, -1.0, 1.0) * np.exp2((emax - cc % 2).astype(np.float64))
+                    a[t] = np.where(cc < nl, left, right)
+    else:
+        tri = _Tri(case)
+        a, b = ops["a"], ops["b"]
+        nt, nv = tri.nt, tri.nv
+        c0, r1 = tri.order[0], tri.order[1]
+        solve = case.kind == pc.TRSM
+        for h, t in enumerate(lanes):
+            A, B = a[t], b[t]
+            if kind == "specials":
+                r = h % (4 if solve else 3)
+                if not solve and r > 0:
+                    r += 1  # (trmm has no pivot: recipes 0, 2, 3)
+                if r == 0:
+                    B[m - 1, n - 1] = np.nan
+                    if case.layout == pc.COL:
+                        B[m // 2, 0] = np.inf
+                    else:
+                        B[0, n // 2] = np.inf
+                elif r == 1:
+                    A[1, 1] = 0.0
+                elif r == 2:
+                    for rc in tri.triangle():
+                        A[tri.e(*rc)] = 0.0
+                    if not solve:
+                        A[np.arange(nt), np.arange(nt)] = 0.0
+                    B[tri.v(c0 if solve else nt // 2, 1)] = np.inf
+                else:
+                    for rr in range(nt):
+                        B[tri.v(rr, 0)] = -0.0
+                        B[tri.v(rr, nv - 1)] = 0.0
+            elif kind == "underflow":
+                if h == 0:
+                    A[1, 1] = 1.5 * 2.0 ** (emin - 1)
+                elif h == 1:
+                    A[1, 1] = 2.0 ** (emin - 4)
+                else:
+                    for q in range(nv):
+                        for rr in range(nt):
+                            B[tri.v(rr, q)] *= 2.0 ** (emin - 4 if q % 2 == 0 else emin + 4)
+            else:
+                if h == 0:
+                    # |alpha| = 1: product 2^(emax + 1), addend -2^emax; alpha = 0.75: product 1.5 * 2^(emax + 1), addend -1.125 * 2^emax
+                    big = half if abs(alpha) == 1.0 else half + 1
+                    if solve:  # x[r1] = fma(-E(r1, c0), x[c0], x[r1]) with x = alpha b and E(c0, c0) = 1
+                        A[tri.e(c0, c0)] = 1.0
+                        A[tri.e(r1, c0)] = -sgn * 2.0 ** big
+                        B[tri.v(c0, 0)] = 2.0 ** half
+                        B[tri.v(r1, 0)] = -sgn * 2.0 ** emax * (1.0 if abs(alpha) == 1.0 else 1.5)
+                    else:      # s = E(r, r) x[r], then s = fma(E(r, c), x[c], s) with c the only entry of the row's triangle
+                        r, c = r1, c0
+                        A[tri.e(r, r)] = 1.0
+                        A[tri.e(r, c)] = 2.0 ** half
+                        B[tri.v(c, 0)] = 2.0 ** half
+                        B[tri.v(r, 0)] = -2.0 ** emax
+                else:
+                    # trsm: a positive diagonal in 0.5 ... 1 and negative entries in the triangle, so that every update adds to an unknown
+                    # of the vector's sign; trmm: a positive triangle. One sign in eight flipped. Vector q at 2^(e_q).
+                    flip = lambda: (-1.0 if rng.integers(0, 8) == 0 else 1.0)
+                    for rc in tri.triangle():
+                        A[tri.e(*rc)] = (-rng.uniform(0.5, 1.0) if solve else rng.uniform(1.0, 2.0)) * flip()
+                    for rr in range(nt):
+                        A[tri.e(rr, rr)] = rng.uniform(0.5, 1.0)
+                    for q in range(nv):
+                        e = emax - (4 * q) // nv
+                        s = rng.choice([-1.0, 1.0])
+                        for rr in range(nt):
+                            B[tri.v(rr, q)] = s * flip() * rng.uniform(0.5, 1.0) * 2.0 ** e
+    with np.errstate(over="ignore"):
+        out.ops = {name: x.astype(case.dtype) for name, x in ops.items()}
+    for name in out.ops:  # the benign lanes keep their bits
+        keep = np.ones(case.nmat, bool); keep[lanes] = False
+        assert raw(out.ops[name][keep]).tobytes() == raw(case.ops[name][keep]).tobytes()
+    return out
+
+
+def packed_fused_spot(case):
+    """(matrix, row, column) of the written operand where hostile matrix 0 of the overflow kind has its planted triple: the product
+    alone is beyond the largest finite number, the fused result is finite"""
+    import packed_common as pc
+    t = int(packed_hostile_lanes(case)[0])
+    if case.kind == pc.PGEMM:
+        return t, case.m - 1, case.n - 1
+    if case.kind == pc.GETRF:
+        return t, 1, 1
+    tri = _Tri(case)
+    return (t,) + tri.v(tri.order[1], 0)
+
+
+def packed_conditions(kind, ref):
+    """what the oracle's results in the hostile lanes (any shape) have to show, so that the comparison with them compares something: the
+    fractions of conditions(), but for the share of NaN among the specials, which may reach three quarters (a zero pivot of getrf leaves a
+    whole trailing matrix NaN, whatever a kernel does)"""
+    ref = np.asarray(ref)
+    if kind != "specials":
+        return conditions(kind, ref)
+    nnan = np.sum(np.isnan(ref))
+    assert 1 <= nnan <= 3 * ref.size / 4, ("NaN", int(nnan), ref.size)
+    assert np.isinf(ref).any(), "no Inf"
+    assert np.any((ref == 0) & np.signbit(ref)), "no -0.0"

@@ -271,6 +271,33 @@ def bgemm_st(arith, h, a, b, c):
     lib().xo_bgemm_st(arith, C.byref(h), p(a), p(b), p(c))
 
 
+def _packed_fn(name, nints, nchars, nptrs):
+    f = getattr(lib(), name)
+    f.argtypes = [C.c_int] * nints + [C.c_char] * nchars + ([C.c_double] if nchars else []) + [C.c_void_p] * nptrs + [C.c_longlong]
+    f.restype = C.c_int
+    return f
+
+
+def packed_pgemm(vlen, layout, m, n, k, lda, ldb, ldc, transa, transb, alpha, a, b, c, npacks):
+    """xo_packed_pgemm in place on the packed buffer c (flat numpy arrays of one float type)"""
+    return _packed_fn("xo_packed_pgemm", 9, 2, 3)(_ts(c), vlen, layout, m, n, k, lda, ldb, ldc, transa.encode(), transb.encode(), alpha,
+                                                 a.ctypes.data, b.ctypes.data, c.ctypes.data, npacks)
+
+
+def packed_getrf(vlen, layout, m, n, lda, a, npacks):
+    return _packed_fn("xo_packed_getrf", 6, 0, 1)(_ts(a), vlen, layout, m, n, lda, a.ctypes.data, npacks)
+
+
+def packed_trmm(vlen, layout, m, n, lda, ldb, side, uplo, transa, diag, alpha, a, b, npacks):
+    return _packed_fn("xo_packed_trmm", 7, 4, 2)(_ts(b), vlen, layout, m, n, lda, ldb, side.encode(), uplo.encode(), transa.encode(),
+                                                diag.encode(), alpha, a.ctypes.data, b.ctypes.data, npacks)
+
+
+def packed_trsm(vlen, layout, m, n, lda, ldb, side, uplo, transa, diag, alpha, a, b, npacks):
+    return _packed_fn("xo_packed_trsm", 7, 4, 2)(_ts(b), vlen, layout, m, n, lda, ldb, side.encode(), uplo.encode(), transa.encode(),
+                                                diag.encode(), alpha, a.ctypes.data, b.ctypes.data, npacks)
+
+
 def matinit(seed, nrows, ncols, ld, scale, dtype):
     out = np.zeros(ncols * ld, dtype=dtype)
     f = lib().xo_matinit_f64 if dtype == np.float64 else lib().xo_matinit_f32

@@ -1,4 +1,4 @@
-"""Shared by tests/test_packed_cpu.py and tests/test_packed_gpu.py: random cases for the packed kernels (pgemm, getrf, trmm,
+"""Shared by tests/test_packed_cpu.py, tests/test_packed_chain_cpu.py and tests/test_packed_gpu.py: random cases for the packed kernels (pgemm, getrf, trmm,
 trsm over packs of interleaved matrices), a plain numpy implementation of the four operations in the kernel's own type, and
 the componentwise backward-error bounds every result must meet.
 
@@ -12,6 +12,7 @@ gamma_p = p u / (1 - p u); the +1 / +2 cover the scaling by alpha and a rounded 
 The left sides are evaluated from the kernel's output in the next wider type (float64 for fp32, numpy.longdouble for fp64; if
 longdouble is no wider than float64 on the machine, exactly with fractions.Fraction on the first 64 matrices)."""
 import ctypes as C
+import itertools
 from fractions import Fraction
 
 import numpy as np
@@ -105,6 +106,25 @@ class Case:
         """the written operand's matrices out of its buffer"""
         x = self.ops[self.written]
         return xs.unpack(buf[GUARD:-GUARD], self.nmat, x.shape[1], x.shape[2], self.ld[self.written], self.layout)
+
+    def chain(self, xs, orc):
+        """the oracle's ordered chain (oracle/xsmm_oracle.c: xo_packed_*) in place on buffers(), canaries included: the buffers
+        after the call. Every kernel result is held against the written one bit for bit."""
+        bufs = self.buffers(xs)
+        v = 64 // self.dtype.itemsize
+        npacks = (self.nmat + v - 1) // v
+        at = {name: x[GUARD:] for name, x in bufs.items()}
+        ld = self.ld
+        if self.kind == PGEMM:
+            rc = orc.packed_pgemm(v, self.layout, self.m, self.n, self.k, ld["a"], ld["b"], ld["c"], self.transa, self.transb, self.alpha,
+                                  at["a"], at["b"], at["c"], npacks)
+        elif self.kind == GETRF:
+            rc = orc.packed_getrf(v, self.layout, self.m, self.n, ld["a"], at["a"], npacks)
+        else:
+            f = orc.packed_trmm if self.kind == TRMM else orc.packed_trsm
+            rc = f(v, self.layout, self.m, self.n, ld["a"], ld["b"], self.side, self.uplo, self.transa, self.diag, self.alpha, at["a"], at["b"], npacks)
+        assert rc == 0, "the oracle refused %r" % (self,)
+        return bufs
 
     def untouched(self, xs, before, after):
         """every operand's canaries (guards, padding) and everything that is only read keep their bits; returns a message or None"""
@@ -237,7 +257,96 @@ def one_like(x):
     return Fraction(1) if x.dtype == object else x.dtype.type(1)
 
 
-# ---- the caller's loop over packs, in C (a Python loop is too slow to keep a burst of deferred calls open) ----
+# ---- the cases of the GPU sweeps (tests/test_packed_gpu.py runs them on the kernels, tests/test_packed_chain_cpu.py on the oracle) ----
+SIZES = (1, 2, 3, 5, 8, 13, 16, 23, 32)
+RECT = ((1, 32), (32, 1), (2, 13), (13, 2), (3, 23), (23, 5), (5, 16), (16, 8), (8, 3), (32, 13), (13, 32), (23, 16))
+PACKS = (1, 7, 8, 9)
+FLAGS = list(itertools.product("LR", "LU", "NT", "NU"))
+MNK = [(s, s, s) for s in SIZES] + [(1, 32, 5), (32, 1, 13), (2, 13, 32), (13, 2, 1), (3, 23, 16), (23, 5, 8), (5, 16, 3), (16, 8, 23), (8, 3, 2)]
+
+
+def width(dtype):
+    """matrices per pack: a line of a pack is 64 bytes per element (libxsmm_amd_packed_width)"""
+    return 64 // np.dtype(dtype).itemsize
+
+
+def flag_sweep(kind, dtype, layout):
+    """the sixteen flag combinations, each on a tight and a padded shape (shapes, alpha and pack counts rotate through their sets)"""
+    v = width(dtype)
+    shapes = [(s, s) for s in SIZES] + list(RECT)
+    out = []
+    for i, (side, uplo, trans, diag) in enumerate(FLAGS):
+        for j, pad in enumerate((0, 3)):
+            m, n = shapes[(2 * i + j + (7 if kind == TRMM else 0)) % len(shapes)]
+            out.append(Case(kind, dtype, m, n, layout=layout, side=side, uplo=uplo, transa=trans, diag=diag, alpha=(1.0, -1.0, 0.75)[(i + j) % 3],
+                            pad=pad, nmat=v * PACKS[(i + j) % 4], seed=100 * i + j))
+    return out
+
+
+def shape_sweep(kind, dtype, layout):
+    """every square size and the rectangular ones, tight and padded in turn, flags rotating"""
+    v = width(dtype)
+    out = []
+    for i, (m, n) in enumerate([(s, s) for s in SIZES] + list(RECT)):
+        side, uplo, trans, diag = FLAGS[(5 * i + 3) % 16]
+        out.append(Case(kind, dtype, m, n, layout=layout, side=side, uplo=uplo, transa=trans, diag=diag, alpha=(0.75, 1.0, -1.0)[i % 3],
+                        pad=(0, 5)[i % 2], nmat=v * PACKS[i % 4], seed=7 * i))
+    return out
+
+
+def pgemm_sweep(dtype, layout):
+    """every trans and alpha, tight and padded; then every shape once more with rotating flags"""
+    v = width(dtype)
+    out = []
+    for i, (ta, tb, alpha) in enumerate(itertools.product("NT", "NT", (1.0, -1.0))):
+        for j, pad in enumerate((0, 2)):
+            m, n, k = MNK[(2 * i + j) % len(MNK)]
+            out.append(Case(PGEMM, dtype, m, n, k, layout=layout, transa=ta, transb=tb, alpha=alpha, pad=pad, nmat=v * PACKS[(i + j) % 4], seed=i))
+    for i, (m, n, k) in enumerate(MNK):
+        ta, tb = "NT"[i % 2], "NT"[(i // 2) % 2]
+        out.append(Case(PGEMM, dtype, m, n, k, layout=layout, transa=ta, transb=tb, alpha=(1.0, -1.0)[i % 2], pad=(4, 0)[i % 2], nmat=v * PACKS[i % 4], seed=50 + i))
+    return out
+
+
+ONE_ANSWER = [(TRSM, 8, 8, 0, dict(side="L", uplo="L")), (TRSM, 13, 5, 0, dict(side="R", uplo="U", transa="T", alpha=0.75, pad=3)),
+              (TRMM, 8, 16, 0, dict(uplo="U", diag="U", alpha=-1.0)), (GETRF, 8, 8, 0, dict()), (GETRF, 16, 13, 0, dict(pad=1)),
+              (PGEMM, 8, 8, 8, dict(alpha=-1.0)), (PGEMM, 5, 16, 13, dict(transa="T", pad=2))]
+
+
+def one_answer_case(kind, m, n, k, kw, dtype):
+    return Case(kind, dtype, m, n, k, nmat=1000 * width(dtype), seed=11, layout=ROW if kw.get("pad") else COL, **kw)
+
+
+RESIDENT_CASES = [(TRSM, 8, 8, 0, dict(side="R", uplo="U", alpha=0.75)), (TRSM, 5, 8, 0, dict(transa="T", alpha=-1.0)), (TRMM, 8, 5, 0, dict(uplo="U")),
+                  (TRMM, 3, 8, 0, dict(side="R", diag="U", alpha=0.75)), (GETRF, 8, 8, 0, dict()), (GETRF, 5, 8, 0, dict()), (PGEMM, 8, 5, 8, dict(alpha=-1.0, transb="T"))]
+
+
+def resident_case(kind, m, n, k, kw, dtype, layout):
+    return Case(kind, dtype, m, n, k, nmat=9 * width(dtype), seed=21, layout=layout, pad=(1 if layout == ROW else 0), **kw)
+
+
+UNALIGNED_CASES = [(TRSM, 8, 5, 0, dict(uplo="U", pad=2)), (TRMM, 13, 3, 0, dict()), (GETRF, 8, 8, 0, dict(pad=1)), (PGEMM, 5, 8, 3, dict())]
+
+
+def unaligned_case(kind, m, n, k, kw, dtype):
+    return Case(kind, dtype, m, n, k, nmat=9 * width(dtype), seed=31, **kw)
+
+
+def redispatch_case(kind):
+    return Case(kind, np.float32, 5, 3, 2, nmat=16, seed=2)
+
+
+# ---- operands past 2^31 elements and 2^32 bytes (tests/test_wide_offsets_gpu.py; the offsets are checked in tests/test_packed_chain_cpu.py) ----
+WIDE_LD, WIDE_LINES = 4096, 32  # the largest leading dimension (PK_MAXLD), column major, 32 columns: a pack spans 2^21 fp32 elements
+# (id, kind, type, m, n, k, the wide operand, packs, flags)
+WIDE_CASES = [("getrf-a", GETRF, np.float32, 2, 32, 0, "a", 1026, dict()),
+              ("trsm-b", TRSM, np.float32, 4, 32, 0, "b", 1026, dict(side="L", uplo="L", transa="N", diag="N")),
+              ("pgemm-c", PGEMM, np.float32, 2, 32, 2, "c", 1026, dict()),
+              ("pgemm-a", PGEMM, np.float32, 2, 2, 32, "a", 1026, dict()),
+              ("trmm-b", TRMM, np.float64, 4, 32, 0, "b", 520, dict())]
+
+
+# ---- the caller's loop over packs, in C(a Python loop is too slow to keep a burst of deferred calls open) ----
 LOOP_C = r"""
 typedef void (*fn3)(const void*, const void*, void*);
 void pack_loop(fn3 f, const char* a, const char* b, char* c, long long sa, long long sb, long long sc, long long n)

@@ -1,5 +1,6 @@
 """Packed kernels on the GPU through the C-ABI (libxsmm_dispatch_pgemm / getrf / trmm / trsm, libxsmm_amd_packed_execute_batch, the
-defer bracket): every result against the derived componentwise bounds of tests/packed_common.py, memory that must stay untouched,
+defer bracket): every result against the derived componentwise bounds of tests/packed_common.py and bit for bit against the ordered chain of the
+CPU oracle (oracle/xsmm_oracle.c, xo_packed_*), memory that must stay untouched,
 one answer whatever the entry point and the kernel form, the number of launches, and the C caller examples/packed_caller.c."""
 import ctypes as C
 import itertools
@@ -14,12 +15,6 @@ from packed_common import PGEMM, GETRF, TRMM, TRSM, COL, ROW, Case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-SIZES = (1, 2, 3, 5, 8, 13, 16, 23, 32)
-RECT = ((1, 32), (32, 1), (2, 13), (13, 2), (3, 23), (23, 5), (5, 16), (16, 8), (8, 3), (32, 13), (13, 32), (23, 16))
-PACKS = (1, 7, 8, 9)
-FLAGS = list(itertools.product("LR", "LU", "NT", "NU"))
-
 
 @pytest.fixture(scope="module")
 def loop(tmp_path_factory):
@@ -57,74 +52,59 @@ def run(xs, torch, case, mode, loop=None, fn=None, shift=0):
     return before, {name: t.cpu().numpy() for name, t in dev.items()}
 
 
-def verify(xs, case, before, after):
+def verify(xs, orc, case, before, after):
+    """the derived bound, nothing else touched, and the written operand's whole buffer (canaries included) bit for bit the oracle's ordered
+    chain (Case.chain: one fixed order per element, explicit fma, the rounded reciprocal of the pivot, alpha = +-1 without a rounding)"""
     out = case.result(xs, after[case.written])
     ratio, msg = case.check(out)
     print("%r: worst residual / bound = %.3f" % (case, ratio))
     assert msg is None, (case, msg)
     msg = case.untouched(xs, before, after)
     assert msg is None, (case, msg)
+    want = case.chain(xs, orc)[case.written]
+    bits = np.uint32 if case.dtype == np.float32 else np.uint64
+    diff = np.flatnonzero(after[case.written].view(bits) != want.view(bits))
+    assert diff.size == 0, (case, "%d elements differ from the oracle's chain; first at %d: %r, oracle %r" % (
+        diff.size, int(diff[0]), after[case.written][diff[0]], want[diff[0]]))
     return out
 
 
 @pytest.mark.parametrize("layout", [COL, ROW])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("kind", [TRSM, TRMM])
-def test_every_side_uplo_trans_diag(xs, torch_gpu, kind, dtype, layout):
-    """the sixteen flag combinations, each on a tight and a padded shape (shapes, alpha and pack counts rotate through their sets)"""
-    v = xs.packed_width(np.dtype(dtype).itemsize)
-    shapes = [(s, s) for s in SIZES] + list(RECT)
-    for i, (side, uplo, trans, diag) in enumerate(FLAGS):
-        for j, pad in enumerate((0, 3)):
-            m, n = shapes[(2 * i + j + (7 if kind == TRMM else 0)) % len(shapes)]
-            case = Case(kind, dtype, m, n, layout=layout, side=side, uplo=uplo, transa=trans, diag=diag, alpha=(1.0, -1.0, 0.75)[(i + j) % 3],
-                        pad=pad, nmat=v * PACKS[(i + j) % 4], seed=100 * i + j)
-            verify(xs, case, *run(xs, torch_gpu, case, "batch"))
+def test_every_side_uplo_trans_diag(xs, orc, torch_gpu, kind, dtype, layout):
+    """the sixteen flag combinations, each on a tight and a padded shape (packed_common.flag_sweep)"""
+    for case in pc.flag_sweep(kind, dtype, layout):
+        verify(xs, orc, case, *run(xs, torch_gpu, case, "batch"))
 
 
 @pytest.mark.parametrize("layout", [COL, ROW])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("kind", [TRSM, TRMM, GETRF])
-def test_every_shape(xs, torch_gpu, kind, dtype, layout):
-    """every square size and the rectangular ones, tight and padded in turn, flags rotating"""
-    v = xs.packed_width(np.dtype(dtype).itemsize)
-    for i, (m, n) in enumerate([(s, s) for s in SIZES] + list(RECT)):
-        side, uplo, trans, diag = FLAGS[(5 * i + 3) % 16]
-        case = Case(kind, dtype, m, n, layout=layout, side=side, uplo=uplo, transa=trans, diag=diag, alpha=(0.75, 1.0, -1.0)[i % 3],
-                    pad=(0, 5)[i % 2], nmat=v * PACKS[i % 4], seed=7 * i)
-        verify(xs, case, *run(xs, torch_gpu, case, "batch"))
+def test_every_shape(xs, orc, torch_gpu, kind, dtype, layout):
+    """every square size and the rectangular ones, tight and padded in turn, flags rotating (packed_common.shape_sweep)"""
+    for case in pc.shape_sweep(kind, dtype, layout):
+        verify(xs, orc, case, *run(xs, torch_gpu, case, "batch"))
 
 
 @pytest.mark.parametrize("layout", [COL, ROW])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_pgemm_every_trans_and_alpha(xs, torch_gpu, dtype, layout):
-    v = xs.packed_width(np.dtype(dtype).itemsize)
-    mnk = [(s, s, s) for s in SIZES] + [(1, 32, 5), (32, 1, 13), (2, 13, 32), (13, 2, 1), (3, 23, 16), (23, 5, 8), (5, 16, 3), (16, 8, 23), (8, 3, 2)]
-    for i, (ta, tb, alpha) in enumerate(itertools.product("NT", "NT", (1.0, -1.0))):
-        for j, pad in enumerate((0, 2)):
-            m, n, k = mnk[(2 * i + j) % len(mnk)]
-            case = Case(PGEMM, dtype, m, n, k, layout=layout, transa=ta, transb=tb, alpha=alpha, pad=pad, nmat=v * PACKS[(i + j) % 4], seed=i)
-            verify(xs, case, *run(xs, torch_gpu, case, "batch"))
-    for i, (m, n, k) in enumerate(mnk):  # and every shape once more with rotating flags
-        ta, tb = "NT"[i % 2], "NT"[(i // 2) % 2]
-        case = Case(PGEMM, dtype, m, n, k, layout=layout, transa=ta, transb=tb, alpha=(1.0, -1.0)[i % 2], pad=(4, 0)[i % 2], nmat=v * PACKS[i % 4], seed=50 + i)
-        verify(xs, case, *run(xs, torch_gpu, case, "batch"))
-
-
-ONE_ANSWER = [(TRSM, 8, 8, 0, dict(side="L", uplo="L")), (TRSM, 13, 5, 0, dict(side="R", uplo="U", transa="T", alpha=0.75, pad=3)),
-              (TRMM, 8, 16, 0, dict(uplo="U", diag="U", alpha=-1.0)), (GETRF, 8, 8, 0, dict()), (GETRF, 16, 13, 0, dict(pad=1)),
-              (PGEMM, 8, 8, 8, dict(alpha=-1.0)), (PGEMM, 5, 16, 13, dict(transa="T", pad=2))]
+def test_pgemm_every_trans_and_alpha(xs, orc, torch_gpu, dtype, layout):
+    """packed_common.pgemm_sweep: every trans and alpha, then every shape once more with rotating flags"""
+    for case in pc.pgemm_sweep(dtype, layout):
+        verify(xs, orc, case, *run(xs, torch_gpu, case, "batch"))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("kind,m,n,k,kw", ONE_ANSWER)
-def test_one_answer_from_every_entry_and_form(xs, torch_gpu, loop, monkeypatch, kind, m, n, k, kw, dtype):
+@pytest.mark.parametrize("kind,m,n,k,kw", pc.ONE_ANSWER)
+def test_one_answer_from_every_entry_and_form(xs, orc, torch_gpu, loop, monkeypatch, kind, m, n, k, kw, dtype):
     """1000 packs: per-call loop on device memory, the same loop inside the bracket, the batch entry, a per-call loop on host memory
     (fewer packs: it is staged call by call), and both kernel forms -- the same bits"""
     v = xs.packed_width(np.dtype(dtype).itemsize)
-    case = Case(kind, dtype, m, n, k, nmat=1000 * v, seed=11, layout=ROW if kw.get("pad") else COL, **kw)
+    case = pc.one_answer_case(kind, m, n, k, kw, dtype)
+    assert case.nmat == 1000 * v
     fn = case.dispatch(xs)
-    ref = verify(xs, case, *run(xs, torch_gpu, case, "batch", fn=fn))
+    ref = verify(xs, orc, case, *run(xs, torch_gpu, case, "batch", fn=fn))
     for mode in ("loop", "bracket"):
         before, after = run(xs, torch_gpu, case, mode, loop, fn)
         assert np.array_equal(case.result(xs, after[case.written]), ref), (case, mode)
@@ -139,32 +119,27 @@ def test_one_answer_from_every_entry_and_form(xs, torch_gpu, loop, monkeypatch, 
     monkeypatch.delenv("LIBXSMM_AMD_PACKED_FORM")
     small = Case(kind, dtype, m, n, k, nmat=9 * v, seed=11, layout=case.layout, **kw)
     small.ops = {name: np.ascontiguousarray(x[:9 * v]) for name, x in case.ops.items()}  # the first nine packs of the same matrices
-    want = verify(xs, small, *run(xs, torch_gpu, small, "batch", fn=fn))
+    want = verify(xs, orc, small, *run(xs, torch_gpu, small, "batch", fn=fn))
     before, after = run(xs, torch_gpu, small, "host", loop, fn)
     assert np.array_equal(small.result(xs, after[small.written]), want)
     assert small.untouched(xs, before, after) is None
     assert np.array_equal(want, ref[:9 * v])  # (the same matrices: the batch size does not change a result either)
 
 
-RESIDENT_CASES = [(TRSM, 8, 8, 0, dict(side="R", uplo="U", alpha=0.75)), (TRSM, 5, 8, 0, dict(transa="T", alpha=-1.0)), (TRMM, 8, 5, 0, dict(uplo="U")),
-                  (TRMM, 3, 8, 0, dict(side="R", diag="U", alpha=0.75)), (GETRF, 8, 8, 0, dict()), (GETRF, 5, 8, 0, dict()), (PGEMM, 8, 5, 8, dict(alpha=-1.0, transb="T"))]
-
-
 @pytest.mark.parametrize("layout", [COL, ROW])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("kind,m,n,k,kw", RESIDENT_CASES)
-def test_register_resident_and_in_place_arithmetic_agree(xs, torch_gpu, monkeypatch, kind, m, n, k, kw, dtype, layout):
+@pytest.mark.parametrize("kind,m,n,k,kw", pc.RESIDENT_CASES)
+def test_register_resident_and_in_place_arithmetic_agree(xs, orc, torch_gpu, monkeypatch, kind, m, n, k, kw, dtype, layout):
     """one shape through the register-resident text and through the loops that large shapes run (LIBXSMM_AMD_PACKED_RESIDENT=0),
     each staged through LDS and on global memory: the same bits"""
-    v = xs.packed_width(np.dtype(dtype).itemsize)
-    case = Case(kind, dtype, m, n, k, nmat=9 * v, seed=21, layout=layout, pad=(1 if layout == ROW else 0), **kw)
+    case = pc.resident_case(kind, m, n, k, kw, dtype, layout)
     fn = case.dispatch(xs)
     blob, d = xs.packed_descriptor(kind, case.dtype.itemsize, m, n, k)
     assert "#define RESIDENT 1" in xs.packed_kernel_source(kind, d)[1]
     monkeypatch.setenv("LIBXSMM_AMD_PACKED_RESIDENT", "0")
     assert "#define RESIDENT 0" in xs.packed_kernel_source(kind, d)[1]
     monkeypatch.delenv("LIBXSMM_AMD_PACKED_RESIDENT")
-    ref = verify(xs, case, *run(xs, torch_gpu, case, "batch", fn=fn))
+    ref = verify(xs, orc, case, *run(xs, torch_gpu, case, "batch", fn=fn))
     for resident, form in itertools.product(("1", "0"), ("1", "2")):
         monkeypatch.setenv("LIBXSMM_AMD_PACKED_RESIDENT", resident)
         monkeypatch.setenv("LIBXSMM_AMD_PACKED_FORM", form)
@@ -174,15 +149,14 @@ def test_register_resident_and_in_place_arithmetic_agree(xs, torch_gpu, monkeypa
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("kind,m,n,k,kw", [(TRSM, 8, 5, 0, dict(uplo="U", pad=2)), (TRMM, 13, 3, 0, dict()), (GETRF, 8, 8, 0, dict(pad=1)), (PGEMM, 5, 8, 3, dict())])
-def test_operands_that_are_not_16_byte_aligned(xs, torch_gpu, loop, monkeypatch, kind, m, n, k, kw, dtype):
+@pytest.mark.parametrize("kind,m,n,k,kw", pc.UNALIGNED_CASES)
+def test_operands_that_are_not_16_byte_aligned(xs, orc, torch_gpu, loop, monkeypatch, kind, m, n, k, kw, dtype):
     """operands one element off a 16-byte boundary take the form that works on global memory, whatever form is asked for -- in the
     batch entry, per call, and inside the bracket (such calls are not recorded) -- with the bits of the aligned run, nothing else touched"""
-    v = xs.packed_width(np.dtype(dtype).itemsize)
-    case = Case(kind, dtype, m, n, k, nmat=9 * v, seed=31, **kw)
+    case = pc.unaligned_case(kind, m, n, k, kw, dtype)
     fn = case.dispatch(xs)
     monkeypatch.setenv("LIBXSMM_AMD_PACKED_FORM", "1")
-    ref = verify(xs, case, *run(xs, torch_gpu, case, "batch", fn=fn))
+    ref = verify(xs, orc, case, *run(xs, torch_gpu, case, "batch", fn=fn))
     assert xs.last_kernel().endswith("_lds"), xs.last_kernel()
     for mode in ("batch", "loop", "bracket"):
         before, after = run(xs, torch_gpu, case, mode, loop, fn, shift=1)
@@ -285,17 +259,17 @@ def test_bracketed_getrf_then_trsm_on_its_factor(xs, torch_gpu, loop, dtype):
     assert msg is None, msg
 
 
-def test_kinds_and_redispatch(xs, torch_gpu):
+def test_kinds_and_redispatch(xs, orc, torch_gpu):
     L = xs.lib()
     for kind, want in ((PGEMM, 3), (GETRF, 4), (TRMM, 5), (TRSM, 6)):
-        case = Case(kind, np.float32, 5, 3, 2, nmat=16, seed=2)
+        case = pc.redispatch_case(kind)
         fn = case.dispatch(xs)
         got = C.c_int(-1)
         assert 0 == L.libxsmm_get_kernel_kind(fn, C.byref(got)) and got.value == want
-        verify(xs, case, *run(xs, torch_gpu, case, "batch", fn=fn))
+        verify(xs, orc, case, *run(xs, torch_gpu, case, "batch", fn=fn))
         L.libxsmm_release_kernel(fn)
         fn2 = case.dispatch(xs)
-        verify(xs, case, *run(xs, torch_gpu, case, "batch", fn=fn2))
+        verify(xs, orc, case, *run(xs, torch_gpu, case, "batch", fn=fn2))
     fn = L.libxsmm_smmdispatch(4, 4, 4, None, None, None, None, None, None, None)
     got = C.c_int(-1)
     assert 0 == L.libxsmm_get_kernel_kind(fn, C.byref(got)) and got.value == 0

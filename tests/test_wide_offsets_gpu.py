@@ -1,6 +1,6 @@
 """Operands whose element offsets pass 2^31 (and whose byte offsets pass 2^32): the 64-bit instantiation of the quantise layout
 kernel, leading dimensions of 2^30 + 7 in the tiled GEMMs, a strided batch with a C stride of 2^20 elements, fsspmdm at the
-leading dimension of BASELINE config 3, and pooling over more than 2^31 elements. The convolution layer refuses tensors of 2^31
+leading dimension of BASELINE config 3, pooling over more than 2^31 elements, and packed operands whose packs lie 2^21 elements apart. The convolution layer refuses tensors of 2^31
 elements (its offsets are 32-bit): it runs on the largest ones it accepts, an input and a filter just below 2^31 elements.
 
 The operands are built on the device and never travel whole. Each case checks (i) a sample gathered to the host against the
@@ -18,6 +18,7 @@ import pytest
 import conv_common as cc
 import launch_limits as ll
 import lowp_gemm_common as lg
+import packed_common as pk
 import pool_common as pc
 import quant_common as qc
 from conftest import GOLDEN
@@ -537,3 +538,63 @@ def test_conv_filter_below_2_31_elements(xs, torch_gpu, part):
         assert bit_sum(torch, w) == before and bands_intact(bw) and bands_intact(bt)
     assert np.all(scratch == 0)
     conv_close(xs, handle, tensors)
+
+
+# ---- packed kernels: a pack of 2^21 elements, a thousand packs -----------------------------------------------------------------------
+@pytest.mark.parametrize("form", ["1", "2"])
+@pytest.mark.parametrize("name,kind,dtype,m,n,k,wide,npacks,kw", pk.WIDE_CASES, ids=[c[0] for c in pk.WIDE_CASES])
+def test_packed_operand_past_2_31_elements(xs, orc, torch_gpu, monkeypatch, name, kind, dtype, m, n, k, wide, npacks, kw, form):
+    """one operand with ld = 4096, column major, 32 columns: its packs lie 2^21 (fp64: 2^20) elements apart, the last one starts past
+    element 2^31 and byte 2^33 (fp64: byte 2^32) -- p * (long long)LD * (NL * VLEN) in the kernel text, once per operand slot and form. The
+    other operands are tight. All valid elements of all packs, gathered through the index tensor that scattered them, against the oracle
+    on tight copies of the same matrices, bit for bit; the padding between the extent of a column and ld keeps the canary everywhere."""
+    torch, L = torch_gpu, xs.lib()
+    v, ts = pk.width(dtype), np.dtype(dtype).itemsize
+    tight = pk.Case(kind, dtype, m, n, k, nmat=npacks * v, seed=41, **kw)
+    rows, cols = tight.ops[wide].shape[1:]
+    ld, nl, guard = pk.WIDE_LD, pk.WIDE_LINES, pk.GUARD
+    assert cols == nl and tight.layout == pk.COL and tight.ld[wide] == rows
+    ps = ld * nl * v
+    assert (npacks - 1) * ps * ts >= 1 << 32 and (ts == 8 or ((npacks - 1) * ps >= W31 and (npacks - 1) * ps * ts >= 1 << 33))
+    need(torch, (npacks * ps + 2 * guard) * ts)
+    want = tight.chain(xs, orc)  # the oracle on the tight layout: the leading dimension only places the columns
+    host = tight.buffers(xs)
+    body = lambda buf: buf[guard:-guard]
+    # where element (i, j) of matrix lane of pack p lies in the wide operand, in the order of the tight packed buffer [p][j][i][lane]
+    p_, j_, i_, l_ = np.meshgrid(np.arange(npacks, dtype=np.int64), np.arange(nl, dtype=np.int64), np.arange(rows, dtype=np.int64),
+                                 np.arange(v, dtype=np.int64), indexing="ij")
+    index = (guard + ((p_ * nl + j_) * ld + i_) * v + l_).reshape(-1)
+    assert index.size == body(host[wide]).size and index[-1] == guard + (npacks - 1) * ps + ((nl - 1) * ld + rows) * v - 1 and int(index.max()) * ts >= 1 << 32
+    dindex = torch.from_numpy(index).cuda()
+    tt = torch.float32 if ts == 4 else torch.float64
+    dwide = torch.full((npacks * ps + 2 * guard,), CANARY, dtype=tt, device="cuda")
+    assert dwide.data_ptr() % 16 == 0
+    dwide[dindex] = torch.from_numpy(body(host[wide])).cuda()
+    dev = {nm: torch.from_numpy(x).cuda() for nm, x in host.items() if nm != wide}
+    ptr = {nm: t.data_ptr() + guard * ts for nm, t in dev.items()}
+    ptr[wide] = dwide.data_ptr() + guard * ts
+    a, b, c = (ptr["a"], ptr["b"], ptr["c"]) if kind == pk.PGEMM else ((ptr["a"], ptr["a"], None) if kind == pk.GETRF else (ptr["a"], ptr["b"], None))
+    case = pk.Case(kind, dtype, m, n, k, nmat=v, seed=41, **kw)  # (the descriptor: one pack will do)
+    case.ld[wide] = ld
+    fn = case.dispatch(xs)
+    monkeypatch.setenv("LIBXSMM_AMD_PACKED_FORM", form)
+    torch.cuda.synchronize()
+    assert 0 == L.libxsmm_amd_packed_execute_batch(fn, a, b, c, npacks)
+    assert 0 == L.libxsmm_amd_synchronize()
+    assert xs.last_kernel().endswith("_lds" if form == "1" else "_direct"), xs.last_kernel()
+    bits = np.uint32 if ts == 4 else np.uint64
+    got = {nm: t.cpu().numpy() for nm, t in dev.items()}
+    got_wide = dwide[dindex].cpu().numpy()
+    diff = np.flatnonzero(got_wide.view(bits) != body(want[wide]).view(bits))
+    assert diff.size == 0, (diff.size, "first in pack %d" % (int(diff[0]) // (nl * rows * v)))
+    for nm in got:  # the tight operands, canaries included
+        assert np.array_equal(got[nm].view(bits), want[nm].view(bits)), nm
+    per = nl * rows * v if tight.written == wide else tight.pack_elems(tight.written)
+    out, was = (got_wide, body(host[wide])) if tight.written == wide else (body(got[tight.written]), body(host[tight.written]))
+    assert np.any(out[:per].view(bits) != was[:per].view(bits)) and np.any(out[-per:].view(bits) != was[-per:].view(bits))  # first and last pack written
+    # the canaries of the wide operand: both guards, and of every column what lies between its extent and ld
+    assert all_equal(torch, dwide, CANARY, 0, guard) and all_equal(torch, dwide, CANARY, guard + (npacks * nl - 1) * ld * v + rows * v, dwide.numel())
+    columns = dwide[guard:guard + npacks * ps].view(npacks * nl, ld * v)
+    step = max(1, SLAB // (ld * v))
+    for r0 in range(0, npacks * nl, step):
+        assert bool((columns[r0:r0 + step, rows * v:] == CANARY).all()), r0
