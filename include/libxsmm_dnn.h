@@ -5,7 +5,7 @@
  * that uses the tensor handles is the fully-connected one (libxsmm_dnn_fullyconnected.h); the pooling layer and the fused
  * batch-norm layer have headers of their own (libxsmm_dnn_pooling.h, libxsmm_dnn_fusedbatchnorm.h). The convolution layer
  * (:265-329 and :364-412) is declared in libxsmm_dnn_convolution.h, a file of this project's that this header includes. The RNN
- * entry points of the reference are not provided, nor are the descriptors and enumerations only they use. The
+ * cell layer is declared in libxsmm_dnn_rnncell.h, as in the reference, and included below (forward pass only: DESIGN.md 8q). The
  * common part lies in libxsmm_dnn_tensor.h, another file of this project's that this header includes (the reference keeps both
  * in libxsmm_dnn.h itself); the quantisation and conversion functions are declared below. Line numbers refer to the
  * reference's include/libxsmm_dnn.h unless a file is named.
@@ -81,5 +81,7 @@ LIBXSMM_API void libxsmm_truncate_convert_f32_bf16(const float* in, libxsmm_bflo
 LIBXSMM_API void libxsmm_rnaz_convert_fp32_bfp16(const float* in, libxsmm_bfloat16* out, unsigned int len);
 LIBXSMM_API void libxsmm_rne_convert_fp32_bfp16(const float* in, libxsmm_bfloat16* out, unsigned int len);
 LIBXSMM_API void libxsmm_convert_bf16_f32(const libxsmm_bfloat16* in, float* out, unsigned int length);
+
+#include "libxsmm_dnn_rnncell.h" /* the RNN cell layer (its header includes this one first, as the reference's does) */
 
 #endif /* LIBXSMM_DNN_H */

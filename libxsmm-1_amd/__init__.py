@@ -104,6 +104,11 @@ class ConvDesc(C.Structure):  # libxsmm_dnn_conv_desc
         + [("pre_bn", C.c_void_p), ("post_bn", C.c_void_p)]
 
 
+class RnncellDesc(C.Structure):  # libxsmm_dnn_rnncell_desc
+    _fields_ = [(n, C.c_int) for n in ("threads", "K", "N", "C", "max_T", "bk", "bn", "bc", "cell_type", "datatype_in", "datatype_out",
+                                       "buffer_format", "filter_format")]
+
+
 def build(verbose=False):
     """Compile csrc/ into lib/libxsmm.so for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(["make", "-C", CSRC, "-j8"], capture_output=True, text=True)
@@ -441,6 +446,26 @@ def _declare(L):
     sig("libxsmm_dnn_reduce_wu_filters", u, vp, i)
     sig("libxsmm_dnn_get_codegen_success", u, vp, i)
     sig("libxsmm_dnn_get_parallel_tasks", u, vp, i, up)
+    # the RNN cell layer (include/libxsmm_dnn_rnncell.h)
+    sig("libxsmm_dnn_create_rnncell", vp, RnncellDesc, up)
+    sig("libxsmm_dnn_destroy_rnncell", u, vp)
+    sig("libxsmm_dnn_rnncell_create_tensor_datalayout", lp, vp, i, up)
+    sig("libxsmm_dnn_rnncell_get_scratch_size", C.c_size_t, vp, i, up)
+    sig("libxsmm_dnn_rnncell_get_scratch_ptr", vp, vp, up)
+    sig("libxsmm_dnn_rnncell_bind_scratch", u, vp, i, vp)
+    sig("libxsmm_dnn_rnncell_release_scratch", u, vp, i)
+    sig("libxsmm_dnn_rnncell_get_internalstate_size", C.c_size_t, vp, i, up)
+    sig("libxsmm_dnn_rnncell_get_internalstate_ptr", vp, vp, up)
+    sig("libxsmm_dnn_rnncell_bind_internalstate", u, vp, i, vp)
+    sig("libxsmm_dnn_rnncell_release_internalstate", u, vp, i)
+    sig("libxsmm_dnn_rnncell_allocate_forget_bias", u, vp, C.c_float)
+    sig("libxsmm_dnn_rnncell_bind_tensor", u, vp, vp, i)
+    sig("libxsmm_dnn_rnncell_get_tensor", vp, vp, i, up)
+    sig("libxsmm_dnn_rnncell_release_tensor", u, vp, i)
+    sig("libxsmm_dnn_rnncell_set_sequence_length", u, vp, i)
+    sig("libxsmm_dnn_rnncell_get_sequence_length", i, vp, up)
+    sig("libxsmm_dnn_rnncell_execute_st", u, vp, i, i, i)
+    sig("libxsmm_amd_rnn_segments", i, i, i, i, i, i, i, c_int_p, i)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -1103,3 +1128,53 @@ def conv_bind_new(handle, ttype, data):
 def conv_execute(handle, kind, start_thread=0, tid=0):
     """libxsmm_dnn_execute_st; returns the status"""
     return lib().libxsmm_dnn_execute_st(handle, kind, start_thread, tid)
+
+
+# ---- the RNN cell layer (include/libxsmm_dnn_rnncell.h) -----------------------------------------------------------------------------
+DNN_FORMAT_CK, DNN_FORMAT_CKPACKED, DNN_FORMAT_NCPACKED, DNN_FORMAT_NC = 32, 64, 128, 256
+DNN_RNNCELL_RNN_RELU, DNN_RNNCELL_RNN_SIGMOID, DNN_RNNCELL_RNN_TANH, DNN_RNNCELL_LSTM, DNN_RNNCELL_GRU = 0, 1, 2, 3, 4
+DNN_RNN_FIRST_TYPE = 33  # LIBXSMM_DNN_RNN_REGULAR_INPUT; the 23 RNN tensor types follow each other
+
+
+def rnn_create(N, Cc, K, max_T, cell_type, bn=0, bc=0, bk=0, threads=1, datatype_in=DNN_F32, datatype_out=DNN_F32,
+               buffer_format=DNN_FORMAT_NC, filter_format=DNN_FORMAT_CK):
+    """libxsmm_dnn_create_rnncell; returns (handle or None, status)"""
+    st = C.c_uint(0xdead)
+    desc = RnncellDesc(threads, K, N, Cc, max_T, bk, bn, bc, cell_type, datatype_in, datatype_out, buffer_format, filter_format)
+    h = lib().libxsmm_dnn_create_rnncell(desc, C.byref(st))
+    return h, st.value
+
+
+def rnn_layout(handle, ttype):
+    """libxsmm_dnn_rnncell_create_tensor_datalayout; returns (pointer or None, status). The caller destroys the layout."""
+    st = C.c_uint(0xdead)
+    l = lib().libxsmm_dnn_rnncell_create_tensor_datalayout(handle, ttype, C.byref(st))
+    return (l if l else None), st.value
+
+
+def rnn_bind_new(handle, ttype, data):
+    """layout of ttype, a tensor linked to data, bound to the handle; returns the tensor handle (the caller destroys it)"""
+    L = lib()
+    l, st = rnn_layout(handle, ttype)
+    if l is None:
+        raise RuntimeError("no layout: status %d" % st)
+    t, st = dnn_link_tensor(l, data)
+    L.libxsmm_dnn_destroy_tensor_datalayout(l)
+    if not t:
+        raise RuntimeError("link failed: status %d" % st)
+    st = L.libxsmm_dnn_rnncell_bind_tensor(handle, t, ttype)
+    if 0 != st:
+        raise RuntimeError("bind failed: status %d" % st)
+    return t
+
+
+def rnn_execute(handle, kind, start_thread=0, tid=0):
+    """libxsmm_dnn_rnncell_execute_st; returns the status"""
+    return lib().libxsmm_dnn_rnncell_execute_st(handle, kind, start_thread, tid)
+
+
+def rnn_segments(cell_type, Cc, K, bc, bk, phase=0):
+    """libxsmm_amd_rnn_segments; returns the list of (operand pair, first row, rows)"""
+    buf = (C.c_int * (3 * 64))()
+    n = lib().libxsmm_amd_rnn_segments(cell_type, Cc, K, bc, bk, phase, buf, 64)
+    return [(buf[3 * j], buf[3 * j + 1], buf[3 * j + 2]) for j in range(n)]

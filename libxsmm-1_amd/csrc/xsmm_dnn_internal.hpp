@@ -68,6 +68,26 @@ int launch_conv_bwd(const ConvArgs& args, void* stream, const char** name);
 int launch_conv_upd(const ConvArgs& args, void* stream, const char** name);
 int launch_conv_trans_filter(const ConvArgs& args, void* stream, const char** name);
 
+// RNN cell layer (xsmm_dnn_rnn.cpp, kernels/rnn.hip): one launch computes, for the rows [n0, n1) of the minibatch and all K outputs,
+// G accumulator sets (gates) of one step -- or, with nz > 1, of nz steps whose operands lie zx / zo elements apart
+constexpr int RNN_MAX_SEG = 34; // two operand pairs times the largest BF, and two to spare
+enum RnnEpilogue : int { RNN_EPI_NONE = 0 /* store the chains where they are continued from */, RNN_EPI_RNN, RNN_EPI_LSTM, RNN_EPI_GRU1, RNN_EPI_GRU2 };
+struct RnnSeg { int which, start, len; }; // operand pair (0: x / w, 1: hsrc / r), first row of w or r, rows; in chain order
+struct RnnArgs {
+  const float* x; const float* hsrc;      // [row][C] and [row][K]: the step's input and what r multiplies (h of the step before, hp, or the GRU's o)
+  const float* w; const float* r; const float* b; // [C][ldw], [K][ldw], [ldw]
+  float* pre[4];                          // per set: where its chain is stored (EPI_NONE) or continued from (!from_bias); RNN: z
+  int gcol[4];                            // per set: its first column in w, r and b
+  const float* hprev; const float* csprev; // the epilogues' operands of the step before, [row][K]
+  float* gi; float* gf; float* go; float* gci; float* gco; float* cs; float* h; // the step's destinations, [row][K]
+  int n0, n1, K, C, ldw, G;
+  int nz; long long zx, zo;               // steps per launch; their distance in x and in pre
+  int from_bias, fgate; float forget_bias; // the chains start from b (set fgate: from b + forget_bias), else from pre
+  int epi, act;                           // RnnEpilogue; RNN: the cell type
+  int nseg; RnnSeg seg[RNN_MAX_SEG];
+};
+int launch_rnn(const RnnArgs& args, void* stream, const char** name); // returns hipError_t as int
+
 // ---- what the layers share on the host (xsmm_dnn_layer.cpp) ---------------------------------------------------------------
 // A layer provides slot_of(handle*, type) at global scope (the tensor pointer a type binds; nullptr for a type it does not
 // bind), its create_tensor_datalayout and its execute_st; the rest of its API forwards to the templates below.
@@ -97,7 +117,7 @@ bool thread_share(long long work, int threads, int ltid, long long* b0, long lon
 // (slot 6 of the calling thread), carved up at 256-byte offsets in the order in which they are asked for, and are uploaded.
 struct Operand { void* dev; void* host; size_t bytes; size_t offset; }; // host: nullptr unless staged
 struct Staging {
-  Operand op[12]; int n = 0; size_t total = 0; bool wait = false;
+  Operand op[16]; int n = 0; size_t total = 0; bool wait = false;
   const Operand* add(const libxsmm_dnn_tensor* t); // (dev is valid after place)
   bool place();                                    // false: no memory, or a copy failed
   // after the launches: the staged ones of the operands the pass wrote (nullptr: skipped) travel back, and the stream is idle on
