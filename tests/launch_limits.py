@@ -15,6 +15,7 @@ CSRC = os.path.join(ROOT, "libxsmm-1_amd", "csrc")
 QUANT, MATDIFF, POOL, TILE, SPARSE, GENERIC, LOWP, XCOPY = ("kernels/quant.hip", "kernels/matdiff.hip", "kernels/pool.hip",
     "kernels/tile_gemm.cuh", "kernels/sparse.hip", "kernels/smm_generic.hip", "kernels/smm_lowp.hip", "kernels/xcopy.hip")
 CONV = "kernels/conv.hip"
+RNN, RNN_HOST = "kernels/rnn.hip", "xsmm_dnn_rnn.cpp"
 GRID_FOR = (SPARSE, r"if \(blocks > 256LL \* (\d+)\) blocks = 256LL \* \1;", 32)
 
 LIMITS = {
@@ -68,6 +69,12 @@ LIMITS = {
         (CONV, r"gx = blocks < (\d+) \? blocks : \1, gy = \(blocks \+ gx - 1\) / gx", 65536), (TILE, r"constexpr int NTHREADS = (\d+);", 256),
         (CONV, r"blocks = \(total \+ NTHREADS - 1\) / NTHREADS", None),
         (CONV, r"\(\(long long\)blockIdx\.x \+ \(long long\)blockIdx\.y \* gridDim\.x\) \* NTHREADS \+ threadIdx\.x", None)]),
+    # RNN cell: the split plan's launch of bias + w.x takes 65535 steps at a time (gridDim.z) and moves x and the chains along
+    "rnn_steps": dict(derive=lambda v: v[0], unit="steps", per_trip=65535, source=[
+        (RNN_HOST, r"for \(int t0 = 0; t0 < T; t0 \+= (\d+)\)", 65535),
+        (RNN_HOST, r"a\.nz = \(T - t0 < (\d+)\) \? \(T - t0\) : \1;", 65535), (RNN, r"\|\| g\.nz > (\d+)\) return \(int\)hipErrorInvalidValue;", 65535),
+        (RNN_HOST, r"a\.pre\[q\] = chain\[q\] \+ t0 \* nk;", None), (RNN_HOST, r"a\.x = f32\(ox\) \+ t0 \* nc;", None),
+        (RNN, r"zx = \(long long\)blockIdx\.z \* g\.zx, zo = \(long long\)blockIdx\.z \* g\.zo;", None)]),
     # tiled GEMM: one grid covers 65535 tiles of columns. A test asks libxsmm_amd_gemm_tile() for the tile; tile_cross_check is
     # only what that answer is held against
     "tgemm_band": dict(derive=lambda v: v[0], unit="tiles of columns", per_trip=65535, tile_cross_check=128, source=[
@@ -117,6 +124,12 @@ THRESHOLDS = {
     "quant_layout_wide": dict(derive=lambda v: 1 << v[0], unit="outputs", threshold=1 << 31, source=[
         (QUANT, r"if \(g\.total < \(1LL << (\d+)\)\) hipLaunchKernelGGL\(\(quant_layout_kernel<MODE, unsigned int>\)", 31),
         (QUANT, r"else hipLaunchKernelGGL\(\(quant_layout_kernel<MODE, unsigned long long>\)", None)]),
+    # RNN cell: a share of more than 65535 tiles of 64 rows (gridDim.y) is refused, not split: the rows go to more logical threads.
+    # chunk: the rows of w or r per trip through LDS (a segment's rest below it ends on the vector ALU)
+    "rnn_rows_per_share": dict(derive=lambda v: v[0] * v[1], unit="rows", threshold=65535 * 64, tiles=65535, tile=64, chunk=32, source=[
+        (RNN, r"if \(tk > 0x7fffffffLL \|\| tn > (\d+) \|\|", 65535), (RNN, r"constexpr int BT = (\d+);", 64),
+        (RNN, r"tn = \(\(long long\)\(g\.n1 - g\.n0\) \+ BT - 1\) / BT;", None), (RNN, r"jt0 = g\.n0 \+ BT \* \(int\)blockIdx\.y;", None),
+        (RNN, r"constexpr int BK = (\d+);", 32)]),
 }
 
 

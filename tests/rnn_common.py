@@ -219,15 +219,25 @@ def relu(a):
         return np.where(a < 0, np.float32(0), a)
 
 
+def _first_nan(a, b, res):
+    """where both operands are NaN the result is the first one, as the scalar x86 instruction has it (numpy's own choice depends on
+    whether its vector loop or its scalar loop runs, that is on the shape; the signs of the NaNs of special_* are in the capture)"""
+    return np.where(np.isnan(a) & np.isnan(b), a, res)
+
+
 def mul(a, b):
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
     with np.errstate(all="ignore"):
-        return np.asarray(a, dtype=np.float32) * np.asarray(b, dtype=np.float32)
+        return _first_nan(a, b, a * b)
 
 
 def fma_ld(a, b, c, fused):
     """dst += src0 * src1: a multiply and an add (what the capture shows), or one fused operation"""
     with np.errstate(all="ignore"):
-        return fma(a, b, c) if fused else (np.asarray(c, dtype=np.float32) + mul(a, b))
+        if fused:
+            return fma(a, b, c)
+        c, p = np.asarray(c, dtype=np.float32), mul(a, b)
+        return _first_nan(c, p, c + p)
 
 
 def filled(shape):
@@ -381,11 +391,24 @@ def _compute_cases():
     c["fbias_lstm"] = desc(4, 8, 12, 2, LSTM, bn=2, bc=4, bk=4, forget_bias=1.0)
     c["bf_lstm"] = desc(4, 1040, 1040, 2, LSTM, bn=4, bc=16, bk=16)    # BF = 5, the diffused body
     c["bf_gru"] = desc(4, 1040, 1040, 2, GRU, bn=4, bc=16, bk=16)      # BF = 5, alternating chunks
+    for cell in CELLS:  # three tiles of k (the last 8 wide) by three tiles of rows (the last 2 rows); reductions of 32 + 8 and 4 * 32 + 8
+        c["rows_" + CELL_NAMES[cell]] = desc(*ROWS_SHAPE, cell, **ROWS_BLOCKS)
+    c["fused_lstm"] = desc(2, 2048, 2048, 2, LSTM, bn=2, bc=64, bk=64)     # BF = 8, the fused body: alternating chunks
+    c["odd_gru"] = desc(3, 1053, 1053, 2, GRU, bn=3, bc=13, bk=13)         # BF = 3, chunks of 351 = 10 * 32 + 31, alternating
     return c
 
 
+ROWS_SHAPE, ROWS_BLOCKS = (130, 40, 136, 2), dict(bn=13, bc=8, bk=17)
 COMPUTE_CASES = _compute_cases()
+# The forced BF = 2 on one block of C: C / bc / BF = 0 blocks per chunk, so no w.x at all. NOT captured: the unmodified reference ends
+# with a segmentation fault here (its batch-reduce kernel is called with a count of zero; with the same bc = 2048 and one block per
+# chunk -- K = 512 -- it runs). What this engine computes there, bias + r.h, is therefore its own reading of the template's arithmetic,
+# held by the restatement alone.
+UNCAPTURED_CASES = {"rem_lstm": desc(2, 2048, 1024, 1, LSTM, bn=2, bc=2048, bk=512)}
+GPU_COMPUTE_CASES = dict(COMPUTE_CASES, **UNCAPTURED_CASES)
 SPECIAL_CASES = {"special_" + CELL_NAMES[cell]: desc(4, 12, 16, 2, cell, bn=2, bc=4, bk=8) for cell in (RELU, LSTM, GRU)}
+SPECIAL_CASES["special_rows_lstm"] = desc(*ROWS_SHAPE, LSTM, **ROWS_BLOCKS)  # and a NaN and an Inf in the second tile both ways
+SPECIAL_ROWS_PLANTED = {"nan": (70, 130), "inf": (100, 131)}              # (row, column) of hp at step 0
 STATUS_CASES = {
     "st_mixed_dt": desc(4, 4, 4, 1, LSTM, dt=F32, dt_out=BF16), "st_i32": desc(4, 4, 4, 1, LSTM, dt=4), "st_bf16": desc(16, 16, 16, 1, LSTM, dt=BF16),
     "st_T0": desc(4, 4, 4, 0, GRU), "st_packed_lstm": desc(8, 32, 48, 2, LSTM, bn=4, bc=16, bk=16, bfmt=FMT_NCPACKED, ffmt=FMT_CKPACKED),
@@ -396,6 +419,50 @@ STATUS_CASES = {
 
 # threads = 3 on four row blocks (tests/test_rnn_gpu.py)
 THREAD_CASES = {"threads_" + CELL_NAMES[cell]: desc(8, 12, 20, 2, cell, bn=2, bc=4, bk=5, threads=3) for cell in (TANH, LSTM, GRU)}
+# threads = 3 on twenty row blocks of 13: rows [0, 91), [91, 182), [182, 260), each across a tile boundary, two from the middle of a tile
+THREAD_CASES.update({"rowshares_" + CELL_NAMES[cell]: desc(260, 40, 136, 2, cell, threads=3, **ROWS_BLOCKS) for cell in (TANH, LSTM, GRU)})
+
+# past the grid limits of kernels/rnn.hip (tests/launch_limits.py: rnn_steps, rnn_rows_per_share) and just below 2^31 elements
+LIMIT_CASES = {
+    "steps_tanh": desc(2, 3, 5, 65537, TANH, bn=2, bc=3, bk=5),                       # two trips of the split plan's first launch
+    "manyrows_relu": desc(65538 * 64, 1, 1, 1, RELU, bn=65538 * 32, bc=1, bk=1),   # 65538 tiles of rows: one share is refused, two run
+}
+WIDE_PERIOD = 1240  # rows of the seeded block the wide case repeats: a multiple of bn, no multiple of 64
+WIDE_CASE = desc(((1 << 31) - 1) // (2 * 72) // WIDE_PERIOD * WIDE_PERIOD, 8, 72, 2, RELU, bn=40, bc=8, bk=72, threads=4)
+
+
+def wide_period():
+    """(inputs, outputs) of one period of the wide case: a layer of WIDE_PERIOD rows (rows are independent recurrences)"""
+    d = dict(WIDE_CASE, N=WIDE_PERIOD, threads=1)
+    t = inputs("wide_relu", d)
+    return d, t, forward(Handle(d), t)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_expected(name):
+    """(inputs, outputs, the transcendentals evaluated) of steps_tanh, computed once"""
+    d = LIMIT_CASES[name]
+    t, seen = inputs(name, d), []
+    return t, forward(Handle(d), t, log=seen), seen
+
+
+def fma_once(a, b, c):
+    """dnn_common.fma with its rare halfway cases put right: where the float64 sum lies exactly between two floats and was itself
+    rounded, the error of that rounding (exact: TwoSum) says which way the single rounding goes"""
+    a, b, c = (np.asarray(v, dtype=np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    tie = ((s.view(np.int64) & 0x1fffffff) == 0x10000000) & (err != 0)
+    s = np.where(tie, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def forward_c1k1(t):
+    """a simple ReLU cell with C = K = 1 and one step, all rows at once: z = fma(r, hp, fma(w, x, b)); returns (h, z)"""
+    z = fma_once(t["r"].reshape(()), t["hp"][0].reshape(-1), fma_once(t["w"].reshape(()), t["x"][0].reshape(-1), t["b"].reshape(())))
+    return relu(z).reshape(1, -1, 1), z.reshape(1, -1, 1)
 
 
 def sweep_cases():
@@ -437,13 +504,15 @@ def inputs(name, d):
         for q in range(1, h.G):
             b[q * d["K"] + 5], b[q * d["K"] + 6] = 100.0 + q, -100.0 - q
         t["w"][:, 7] = 0.0  # products with +-Inf and NaN there: 0 * Inf
+    if name == "special_rows_lstm":  # beyond the first tile both ways: the poison has to stay in its row
+        hp[(0,) + SPECIAL_ROWS_PLANTED["nan"]], hp[(0,) + SPECIAL_ROWS_PLANTED["inf"]] = np.nan, np.inf
     return t
 
 
 @functools.lru_cache(maxsize=None)
 def expected(name, log=False):
-    """(inputs, outputs[, the transcendentals evaluated]) of a captured case, computed once"""
-    d = captured_cases()[name]
+    """(inputs, outputs[, the transcendentals evaluated]) of a captured (or uncaptured compute) case, computed once"""
+    d = dict(captured_cases(), **UNCAPTURED_CASES)[name]
     t = inputs(name, d)
     seen = [] if log else None
     out = forward(Handle(d), t, log=seen)

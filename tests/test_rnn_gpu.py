@@ -9,6 +9,7 @@ import threading
 import numpy as np
 import pytest
 
+import launch_limits as ll
 import rnn_common as rc
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,9 @@ def keys_of(d):
 
 
 def launches_of(d, h, split):
-    return (2 if d["cell"] == rc.GRU else 1) * h.T + (1 if split and h.T > 0 else 0)
+    """one launch per step (GRU: two) and, in the split plan, one ahead of them per 65535 steps"""
+    trip = ll.per_trip("rnn_steps")
+    return (2 if d["cell"] == rc.GRU else 1) * h.T + ((h.T + trip - 1) // trip if split else 0)
 
 
 def split_legal(d, h):
@@ -105,10 +108,11 @@ def clean_env():
         os.environ.pop(k, None)
 
 
-@pytest.mark.parametrize("name", sorted(rc.COMPUTE_CASES))
+@pytest.mark.parametrize("name", sorted(rc.GPU_COMPUTE_CASES))
 def test_fwd_bit_equal(xs, torch_gpu, name):
-    """every captured compute case: all tensors of the pass, the default plan and its launch count"""
-    d = rc.COMPUTE_CASES[name]
+    """every captured compute case (and rem_lstm, which the reference cannot run): all tensors of the pass, the default plan and its
+    launch count"""
+    d = rc.GPU_COMPUTE_CASES[name]
     t, out = rc.expected(name)
     layer = Layer(xs, torch_gpu, d, t)
     before = layer.count()
@@ -131,12 +135,16 @@ def test_special_values(xs, torch_gpu, name):
         layer.check(t, out, nan_class=True)
         h = layer.result("h")
         assert np.any(np.isnan(h)) and np.any(np.isfinite(h))
+        if name == "special_rows_lstm":  # beyond the first tile both ways: the NaN fills its row of step 0 and no other row has one
+            h = h.reshape(d["max_T"], d["N"], d["K"])
+            assert np.all(np.isnan(h[0, rc.SPECIAL_ROWS_PLANTED["nan"][0]])) and np.all(np.isfinite(h[:, 3:])[:, np.arange(3, d["N"]) != rc.SPECIAL_ROWS_PLANTED["nan"][0]])
         layer.close()
 
 
-@pytest.mark.parametrize("name", ["blk_" + n for n in rc.CELL_NAMES.values()] + ["k72_gru", "k72_lstm", "k72_tanh", "seq_gru", "fbias_lstm", "bf_gru"])
+@pytest.mark.parametrize("name", ["blk_" + n for n in rc.CELL_NAMES.values()] + ["k72_gru", "k72_lstm", "k72_tanh", "seq_gru", "fbias_lstm", "bf_gru"]
+                         + ["rows_" + n for n in rc.CELL_NAMES.values()] + ["fused_lstm", "rem_lstm"])
 def test_plans_give_the_same_bits(xs, torch_gpu, name):
-    d = rc.COMPUTE_CASES[name]
+    d = rc.GPU_COMPUTE_CASES[name]
     t, out = rc.expected(name)
     for plan in ("split", "whole"):
         os.environ["LIBXSMM_AMD_RNN_PLAN"] = plan
@@ -149,7 +157,7 @@ def test_plans_give_the_same_bits(xs, torch_gpu, name):
         layer.close()
 
 
-@pytest.mark.parametrize("name", sorted(THREAD_CASES))
+@pytest.mark.parametrize("name", sorted(n for n in THREAD_CASES if n.startswith("threads_")))
 def test_threads_in_reverse_order_on_three_streams(xs, torch_gpu, name):
     """threads = 3 on four row blocks: shares of two, two and none, issued in reverse order on streams of their own, give the bits of
     threads = 1; a logical thread beyond desc.threads launches nothing"""
@@ -180,6 +188,43 @@ def test_threads_in_reverse_order_on_three_streams(xs, torch_gpu, name):
         if tid == 1:  # the rows of the other share hold their fill
             got = layer.result("h").reshape(d["max_T"], d["N"], d["K"])
             assert got[:, 4:].tobytes() == out["h"][:, 4:].tobytes() and np.all(got[:, :4].view(np.uint32) == 0xffffffff)
+    assert status == {0: 0, 1: 0, 2: 0}
+    layer.check(t, out)
+    layer.close()
+
+
+@pytest.mark.parametrize("name", sorted(n for n in THREAD_CASES if n.startswith("rowshares_")))
+def test_row_shares_across_tiles_in_reverse_order(xs, torch_gpu, name):
+    """threads = 3 on twenty row blocks of 13: rows [0, 91), [91, 182) and [182, 260), every share across a tile boundary and two of
+    them from the middle of a tile, issued in reverse order on streams of their own, give the bits of threads = 1; after each share
+    (the middle one too) only its rows are written anew and all rows not yet issued hold their fill"""
+    torch = torch_gpu
+    d = THREAD_CASES[name]
+    t = rc.inputs(name, d)
+    out = rc.forward(rc.Handle(dict(d, threads=1)), t)
+    layer = Layer(xs, torch, d, t)
+    assert layer.h.shares() == [(0, 91), (91, 182), (182, 260)]
+    before = layer.count()
+    assert 0 == layer.run(rc.FWD, 0, 3) == layer.run(rc.FWD, 5, 45)
+    assert 0 == layer.count() - before
+    torch.cuda.synchronize()
+    status = {}
+
+    def share(tid):
+        s = torch.cuda.Stream()
+        layer.L.libxsmm_amd_set_stream(C.c_void_p(s.cuda_stream))
+        status[tid] = layer.run(rc.FWD, 0, tid)
+        s.synchronize()
+        layer.L.libxsmm_amd_set_stream(None)
+
+    for tid in (2, 1, 0):
+        wk = threading.Thread(target=share, args=(tid,))
+        wk.start()
+        wk.join()
+        n0 = layer.h.shares()[tid][0]  # after every share: its rows and those of the shares before it are written, all others hold the fill
+        for key in rc.written(d["cell"]):
+            got = layer.result(key).reshape(d["max_T"], d["N"], d["K"])
+            assert got[:, n0:].tobytes() == out[key][:, n0:].tobytes() and np.all(got[:, :n0].view(np.uint32) == 0xffffffff), (key, tid)
     assert status == {0: 0, 1: 0, 2: 0}
     layer.check(t, out)
     layer.close()

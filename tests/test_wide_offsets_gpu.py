@@ -6,11 +6,17 @@ elements (its offsets are 32-bit): it runs on the largest ones it accepts, an in
 The operands are built on the device and never travel whole. Each case checks (i) a sample gathered to the host against the
 family's host reference -- everywhere the call writes where that is small, otherwise at least 256 places that include the
 first and the last element and the neighbours of offset 2^31 --, (ii) canaries: what the call must not touch, compared on the
-device in slabs, and (iii) a property of the whole array where there is one. A case needs up to 20 GiB and skips only where
-torch.cuda.mem_get_info() shows less free memory than it needs; on an MI355X none does."""
+device in slabs, and (iii) a property of the whole array where there is one. A case needs up to 20 GiB (the RNN cell layer with its
+three state tensors of 8 GiB: 26 GiB) and skips only where torch.cuda.mem_get_info() shows less free memory than it needs; on an
+MI355X none does.
+
+The RNN cell layer refuses tensors of 2^31 elements as well; its case has states just below that, whose second step begins just below
+byte 2^32 and ends near byte 2^33. Its rows are independent recurrences, so the tensors repeat one seeded block of rows and every
+period of what the pass writes is compared on the device with the restatement of that block."""
 import ctypes as C
 import glob
 import os
+import time
 
 import numpy as np
 import pytest
@@ -21,6 +27,7 @@ import lowp_gemm_common as lg
 import packed_common as pk
 import pool_common as pc
 import quant_common as qc
+import rnn_common as rc
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -30,8 +37,8 @@ W31 = 1 << 31
 SLAB = 1 << 28  # elements compared at once on the device
 
 
-def need(torch, nbytes):
-    assert nbytes <= 20 * GiB
+def need(torch, nbytes, most=20 * GiB):
+    assert nbytes <= most
     free = torch.cuda.mem_get_info()[0]
     if free < nbytes + GiB:
         pytest.skip("%.1f GiB free, the case needs %.1f" % (free / GiB, nbytes / GiB + 1))
@@ -538,6 +545,73 @@ def test_conv_filter_below_2_31_elements(xs, torch_gpu, part):
         assert bit_sum(torch, w) == before and bands_intact(bw) and bands_intact(bt)
     assert np.all(scratch == 0)
     conv_close(xs, handle, tensors)
+
+
+# ---- RNN cell: hidden state, internal state and previous state just below 2^31 elements ------------------------------------------------
+def periods_that_differ(torch, bits, want, steps, reps):
+    """bits: [steps][reps][period] as int32, want: [steps][1][period]; the indices of the periods that are not want, slab by slab"""
+    v, bad = bits.view(steps, reps, -1), []
+    step = max(1, SLAB // (steps * v.shape[2]))
+    for r0 in range(0, reps, step):
+        ok = (v[:, r0:r0 + step] == want).all(dim=2).all(dim=0)
+        bad += (r0 + torch.nonzero(~ok).view(-1)).tolist()
+    return bad
+
+
+def test_rnn_state_below_2_31_elements(xs, torch_gpu):
+    """A ReLU cell with two steps, C = 8, K = 72 and as many rows as max_T * N * K < 2^31 allows in whole periods of 1240: step 1 of h,
+    of z and of the chains the launch of bias + w.x leaves begins 242176 bytes below byte 2^32 (more the layer does not accept: it
+    refuses 2^31 elements) and ends near byte 2^33. Four logical threads, all run, in reverse order: every share stays below the
+    row-tile limit. x and hp repeat one seeded block of 1240 rows; every period of h and z is compared with the restatement of that
+    block as uint32, the last one, the ones across the share boundaries and the one that holds byte 2^32 by name."""
+    torch, L = torch_gpu, xs.lib()
+    d = rc.WIDE_CASE
+    N, Cc, K, T, P = d["N"], d["C"], d["K"], d["max_T"], rc.WIDE_PERIOD
+    reps, n_state, n_x = N // P, T * N * K, T * N * Cc
+    assert W31 - (1 << 20) <= n_state < W31 and reps * P == N and (1 << 32) - (1 << 20) < N * K * 4 < 1 << 32 and n_state * 4 > (1 << 33) - (1 << 22)
+    need(torch, (3 * n_state + n_x) * 4 + GiB, most=27 * GiB)
+    t0 = time.time()
+    dp, tp, op = rc.wide_period()
+    handle, st = xs.rnn_create(N, Cc, K, T, d["cell"], d["bn"], d["bc"], d["bk"], d["threads"])
+    shares = rc.Handle(d).shares()
+    assert handle and 0 == st and len(shares) == 4 and all(n1 - n0 <= ll.threshold("rnn_rows_per_share") for n0, n1 in shares)
+    on_device = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()  # noqa: E731
+    want = {key: on_device(a).view(T, 1, -1) for key, a in (("x", tp["x"]), ("hp", tp["hp"]), ("h", op["h"]), ("z", op["z"]))}
+    bx, x = banded(torch, n_x, torch.float32, 0.0)
+    bhp, hp = banded(torch, n_state, torch.float32, 0.0)
+    x.view(torch.int32).view(T, reps, -1).copy_(want["x"])
+    hp.view(torch.int32).view(T, reps, -1).copy_(want["hp"])
+    bh, h_bits, h = poisoned(torch, n_state)
+    bz, z_bits, z = poisoned(torch, n_state)
+    assert z.data_ptr() % 64 == 0
+    small = {key: torch.from_numpy(tp[key]).cuda() for key in ("w", "r", "b")}
+    tensors = [xs.rnn_bind_new(handle, rc.IN_TYPE.get(key, rc.OUT_TYPE.get(key)), v)
+               for key, v in (("x", x), ("hp", hp), ("w", small["w"]), ("r", small["r"]), ("b", small["b"]), ("h", h))]
+    assert 0 == L.libxsmm_dnn_rnncell_bind_internalstate(handle, rc.FWD, xs.dptr(z))
+    before = L.libxsmm_amd_launch_count()
+    torch.cuda.synchronize()
+    t1 = time.time()
+    for tid in (3, 2, 1, 0):
+        assert 0 == xs.rnn_execute(handle, rc.FWD, 0, tid), tid
+    torch.cuda.synchronize()
+    t2 = time.time()
+    assert xs.last_kernel() == "rnn_g1" and 4 * (T + 1) == L.libxsmm_amd_launch_count() - before
+    named = {"the last period": reps - 1, "the period of step 1 that holds byte 2^32": ((1 << 30) - N * K) // K // P}
+    named.update({"the period across the boundary of shares %d and %d (row %d)" % (i, i + 1, shares[i][1]): shares[i][1] // P for i in range(3)})
+    assert all(0 <= p < reps for p in named.values()) and all(shares[i][1] % P for i in range(3))
+    for key, bits in (("h", h_bits), ("z", z_bits)):
+        for what, p in named.items():
+            assert bool((bits.view(T, reps, -1)[:, p] == want[key][:, 0]).all()), "%s: %s (period %d of %d) differs" % (key, what, p, reps)
+        bad = periods_that_differ(torch, bits, want[key], T, reps)
+        assert not bad, "%s: %d of %d periods differ, the first ones %r (named: %r)" % (key, len(bad), reps, bad[:8], named)
+    for key, v in (("x", x), ("hp", hp)):  # what the pass reads
+        assert not periods_that_differ(torch, v.view(torch.int32), want[key], T, reps), key
+    assert all(np.array_equal(small[key].cpu().numpy().view(np.uint32), tp[key].view(np.uint32)) for key in small)
+    assert bands_intact(bx) and bands_intact(bhp) and bands_intact(bh) and bands_intact(bz)
+    for tensor in tensors:
+        L.libxsmm_dnn_destroy_tensor(tensor)
+    assert 0 == L.libxsmm_dnn_destroy_rnncell(handle)
+    print("rnn wide: fill %.2f s, four shares %.2f s, compare %.2f s" % (t1 - t0, t2 - t1, time.time() - t2))
 
 
 # ---- packed kernels: a pack of 2^21 elements, a thousand packs -----------------------------------------------------------------------
