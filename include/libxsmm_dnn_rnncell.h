@@ -1,5 +1,5 @@
 /* libxsmm_dnn_rnncell.h -- the RNN cell layer of the reference's DNN interface on the GPU: the forward pass of the five cell
- * types (RNN with ReLU, sigmoid or tanh; LSTM; GRU) in fp32, activations in the plain NC format and filters in CK (reference:
+ * types (RNN with ReLU, sigmoid or tanh; LSTM; GRU), and the backward and update passes of all but the GRU (at the end), in fp32, activations in the plain NC format and filters in CK (reference:
  * include/libxsmm_dnn_rnncell.h:37-93, src/libxsmm_dnn_rnncell.c, src/libxsmm_dnn_rnncell_forward.c:218-272,
  * src/libxsmm_dnn_elementwise.c and src/template/libxsmm_dnn_rnncell_st_{rnn,lstm,gru}_fwd_nc_ck_generic.tpl.c with the two LSTM
  * bodies ..._lstm_fwd_nc_kcck_{diffused,fused}.tpl.c). Line numbers below refer to the reference's header unless a file is named.
@@ -44,7 +44,7 @@
  * dereferences it (get_scratch_size, bind_scratch) gives _ERR_INVALID_HANDLE. None of these touches a device.
  *
  * execute_st checks, in this order and all before any device is asked for: NULL handle (_ERR_INVALID_HANDLE); a kind other than
- * FWD (_ERR_INVALID_KIND: BWD, UPD, BWDUPD and ALL are not built here); a format pair other than NC / CK
+ * FWD goes to the backward checks below (ALL and unknown kinds: _ERR_INVALID_KIND); a format pair other than NC / CK
  * (_ERR_INVALID_FORMAT_GENERAL, the reference's status for an unknown pair); an unknown cell type (_ERR_INVALID_RNN_TYPE); an
  * unbound tensor the cell's FWD reads or writes, the internal state of a simple cell among them (_ERR_DATA_NOT_BOUND; the
  * reference dereferences NULL); non-positive N, C, K or threads, or a tensor of 2^31 elements or more (_ERR_GENERAL);
@@ -61,7 +61,37 @@
  *      same bits. LIBXSMM_AMD_RNN_PLAN=split is ignored where the order does not allow it.
  *   4. Memory: as for the other layers -- tensors the GPU reaches are processed in place and the call does not wait; a
  *      host-visible tensor makes the call complete on return; pageable host memory is staged, and every staged tensor the pass
- *      writes travels back whole. */
+ *      writes travels back whole.
+ *
+ * BWD, UPD and BWDUPD of the simple cells and the LSTM (src/template/libxsmm_dnn_rnncell_st_{rnn,lstm}_bwdupd_nc_ck_generic.tpl.c,
+ * ..._lstm_bwdupd_nc_kcck_core.tpl.c without LIBXSMM_RNN_CELL_AVX512), bit for bit like the forward pass and with the same
+ * reservation. Every sum of products is one fmaf chain; every elementwise multiply, add and subtraction is rounded on its own.
+ *   Simple cells: delta[T-1] = act'(z) * dh; for t < T-1, delta[t][n][k] = dh[t][n][k] continued by the chain over c ascending of
+ *     r[k][c] * delta[t+1][n][c], then multiplied by act'(z[t]). act': ReLU (z < 0) ? 0 : 1; sigmoid (1 - s) * s with s as in the
+ *     forward pass; tanh 1 - t * t with t = (float)tanh((double)z).
+ *   LSTM: dout = dh[T-1], or (+0.0 continued by the chain R^T . [di, dci, df, dp] of step t+1) + dh[t]; then, with dcp starting
+ *     from dcs: dcp = dcp + (dout * o) * (1 - co * co); dci = (dcp * i) * (1 - ci * ci); di = (dcp * ci) * (i * (1 - i));
+ *     df = (dcp * cs[t-1]) * (f * (1 - f)) (csp at t = 0); dp = (dout * co) * (o * (1 - o)); dcp = f * dcp. GRADIENT_CS_PREV holds
+ *     the running dcp and in the end the result; GRADIENT_HIDDEN_STATE_PREV is the chain of step 0 (stored without an add). Both
+ *     use step 0 of their tensors and are written by every kind.
+ *   Chain order over the G * K filter columns (the LSTM's dx, dout and dhp): for each chunk KB = 0 .. BF-1 the gates i, c, f, o in
+ *     turn, each over the K / BF indices of the chunk. BF depends on K alone: 1; for K in (1024, 2048] the largest BF <= 8 that
+ *     divides K / bk; above 2048 the largest such BF <= 16. libxsmm_amd_rnn_bwd_segments returns the list.
+ *   dx[t][n][c] (BWD, BWDUPD) = +0.0 continued by the chain over the filter columns of w[c][q] * delta[t][n][q]; steps >= the
+ *     sequence length are not touched. dw[c][q] and dr[c][q] (UPD, BWDUPD) = +0.0 continued by one chain over the steps descending
+ *     and, inside a step, the rows ascending of delta[t][n][q] * x[t][n][c], respectively h[t-1][n][c] (hp at t = 0 -- also with a
+ *     single step, where the reference's simple-cell template reads before h). db[q] = +0.0 plus delta[t][n][q] in the same order.
+ *   Checks, after the NULL handle and all before any device is asked for: the GRU, ALL and unknown kinds: _ERR_INVALID_KIND; a
+ *     handle with no GRADIENT_* tensor bound: _ERR_INVALID_KIND (the answer from before these passes existed; the reference checks
+ *     nothing and dereferences NULL); the format pair; then _ERR_DATA_NOT_BOUND for anything the templates read or write under
+ *     the kind: r, dh and z (LSTM: csp, cs, i, f, o, ci, co, dcs, dcsp, dhp) always, w and dx for BWD, x, hp, h, dw, dr, db for
+ *     UPD; the extents and tid - start_thread < 0 as for FWD (_ERR_GENERAL); a share of more than 65535 * 64 rows (_ERR_GENERAL,
+ *     nothing is written).
+ *   Threads. BWD divides the rows of the minibatch as FWD does. dw, dr and db sum over all rows and there is no barrier between
+ *     calls: with UPD and BWDUPD logical thread 0 launches the whole pass, the others launch nothing and return _SUCCESS.
+ *   The deltas of all steps live in [max_T][N][G*K] floats of device memory owned by the handle (allocated by its first backward
+ *     call, freed by destroy); the caller's scratch stays unused. Launches: one per step, one for the LSTM's dhp, one for dx per
+ *     65535 steps, and three for dw, dr, db -- a function of the sequence length and the kind alone. */
 #ifndef LIBXSMM_DNN_RNNCELL_H
 #define LIBXSMM_DNN_RNNCELL_H
 
@@ -133,5 +163,10 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_rnncell_execute_st(libxsmm_dnn_rnncell
  *  (same list; its r operand is o). Writes up to `capacity` triples (operand pair: 0 = x / w, 1 = h / r; first row of w or r; number
  *  of rows) to `segments` and returns how many the list has (0: bc or bk is not positive or does not divide). */
 LIBXSMM_API int libxsmm_amd_rnn_segments(libxsmm_dnn_rnncell_type cell_type, int C, int K, int bc, int bk, int phase, int* segments, int capacity);
+
+/** This engine's own, host only: the order in which the backward passes walk the G * K filter columns (the LSTM's dx, dout and dhp
+ *  reductions; a simple cell has one segment of K). Writes up to `capacity` pairs (first column, number of columns) to `segments` and
+ *  returns how many the list has (0: bk is not positive or does not divide K, or the cell has no backward pass here). */
+LIBXSMM_API int libxsmm_amd_rnn_bwd_segments(libxsmm_dnn_rnncell_type cell_type, int K, int bk, int* segments, int capacity);
 
 #endif /* LIBXSMM_DNN_RNNCELL_H */

@@ -466,6 +466,7 @@ def _declare(L):
     sig("libxsmm_dnn_rnncell_get_sequence_length", i, vp, up)
     sig("libxsmm_dnn_rnncell_execute_st", u, vp, i, i, i)
     sig("libxsmm_amd_rnn_segments", i, i, i, i, i, i, i, c_int_p, i)
+    sig("libxsmm_amd_rnn_bwd_segments", i, i, i, i, c_int_p, i)
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
@@ -1178,3 +1179,10 @@ def rnn_segments(cell_type, Cc, K, bc, bk, phase=0):
     buf = (C.c_int * (3 * 64))()
     n = lib().libxsmm_amd_rnn_segments(cell_type, Cc, K, bc, bk, phase, buf, 64)
     return [(buf[3 * j], buf[3 * j + 1], buf[3 * j + 2]) for j in range(n)]
+
+
+def rnn_bwd_segments(cell_type, K, bk):
+    """libxsmm_amd_rnn_bwd_segments; returns the list of (first column, columns)"""
+    buf = (C.c_int * (2 * 64))()
+    n = lib().libxsmm_amd_rnn_bwd_segments(cell_type, K, bk, buf, 64)
+    return [(buf[2 * j], buf[2 * j + 1]) for j in range(n)]

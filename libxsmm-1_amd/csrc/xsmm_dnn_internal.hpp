@@ -88,6 +88,37 @@ struct RnnArgs {
 };
 int launch_rnn(const RnnArgs& args, void* stream, const char** name); // returns hipError_t as int
 
+// RNN cell layer, backward and update (xsmm_dnn_rnn.cpp, kernels/rnn_bwd.hip). The deltas of a pass live in a handle-owned buffer
+// [step][row][ld], ld = G * K, the gates side by side in the filters' column order (LSTM: i, c, f, o).
+constexpr int RNN_BWD_MAX_SEG = 64; // four gates times the largest BF
+enum RnnBwdEpilogue : int { RNN_BWD_EPI_STORE = 0 /* out = the chain */, RNN_BWD_EPI_SIMPLE /* delta = (dh continued by the chain) * act'(z) */,
+  RNN_BWD_EPI_LSTM /* dout = the chain + dh; dcsp and the four deltas */ };
+struct RnnBwdSeg { int start, len; }; // columns of the filter row and of the delta row, in chain order
+// out[row][m] = start continued by, for every segment, the chain over its columns q of filt[m][q] * delta[row][q]
+struct RnnBwdChainArgs {
+  const float* filt;   // [M][ld]: w (M = C) or r (M = K)
+  const float* delta;  // [row][ld], nz steps zd apart: what is reduced (unused with nseg = 0)
+  float* out;          // EPI_STORE: [row][M], nz steps zo apart
+  int M, ld, n0, n1, nz; long long zd, zo;
+  int epi, act, last;  // act: the simple cell's type; last: step T - 1 (dout is dh alone, the LSTM starts from dcs)
+  const float* dh; const float* z; // the step's, [row][K]
+  float* dstep;        // the step's deltas, [row][ld]
+  const float* gi; const float* gf; const float* go; const float* gci; const float* gco; const float* csprev; const float* dcs; // LSTM, [row][K]
+  float* dcsp;         // LSTM: the running dcp, [row][K]
+  int nseg; RnnBwdSeg seg[RNN_BWD_MAX_SEG];
+};
+int launch_rnn_bwd_chain(const RnnBwdChainArgs& args, void* stream, const char** name);
+// out[m][j] = +0.0 continued by one chain over the steps descending and the rows ascending of act_t[row][m] * delta_t[row][j]
+struct RnnBwdWeightArgs {
+  const float* act;    // [step][row][M]: x (M = C) or h (M = K)
+  const float* act0;   // shift: what step 0 multiplies (hp)
+  const float* delta;  // [step][row][ld]
+  float* out;          // [M][ld]
+  int M, ld, N, T, shift; // shift 1: step t multiplies act[t - 1]
+};
+int launch_rnn_bwd_weight(const RnnBwdWeightArgs& args, void* stream, const char** name);
+int launch_rnn_bwd_bias(const float* delta, float* db, int ld, int N, int T, void* stream, const char** name); // db[j] = +0.0 + delta in the same order
+
 // ---- what the layers share on the host (xsmm_dnn_layer.cpp) ---------------------------------------------------------------
 // A layer provides slot_of(handle*, type) at global scope (the tensor pointer a type binds; nullptr for a type it does not
 // bind), its create_tensor_datalayout and its execute_st; the rest of its API forwards to the templates below.
@@ -117,7 +148,7 @@ bool thread_share(long long work, int threads, int ltid, long long* b0, long lon
 // (slot 6 of the calling thread), carved up at 256-byte offsets in the order in which they are asked for, and are uploaded.
 struct Operand { void* dev; void* host; size_t bytes; size_t offset; }; // host: nullptr unless staged
 struct Staging {
-  Operand op[16]; int n = 0; size_t total = 0; bool wait = false;
+  Operand op[24]; int n = 0; size_t total = 0; bool wait = false;
   const Operand* add(const libxsmm_dnn_tensor* t); // (dev is valid after place)
   bool place();                                    // false: no memory, or a copy failed
   // after the launches: the staged ones of the operands the pass wrote (nullptr: skipped) travel back, and the stream is idle on

@@ -1,6 +1,7 @@
 // xsmm_dnn_rnn.cpp -- the RNN cell layer (include/libxsmm_dnn_rnncell.h): handle, layouts, scratch, internal state and tensor
 // binding as in the reference, and the forward pass of libxsmm_dnn_rnncell_execute_st as launches of kernels/rnn.hip, one per step
-// (GRU: two) plus, in the split plan, one ahead of them.
+// (GRU: two) plus, in the split plan, one ahead of them; BWD, UPD and BWDUPD of the simple cells and the LSTM as launches of
+// kernels/rnn_bwd.hip (execute_backward).
 //
 // Reference: src/libxsmm_dnn_rnncell.c (create :48-137, layouts :155-841, scratch :844-1700, internal state :1703-1928, binding
 // :1931-2187, sequence length :2190-2217, execute :2220-2258), src/libxsmm_dnn_rnncell_forward.c:218-272 and the templates
@@ -12,6 +13,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 using namespace xsmm;
 
@@ -26,6 +28,7 @@ struct libxsmm_dnn_rnncell { // the fields of src/libxsmm_main.h's libxsmm_dnn_r
   libxsmm_dnn_tensor* it; libxsmm_dnn_tensor* ft; libxsmm_dnn_tensor* ot; libxsmm_dnn_tensor* cit; libxsmm_dnn_tensor* cot;
   void* scratch_base; // as bound (never dereferenced)
   void* internal_z;   // aligned to 64
+  float* deltas;      // device, [max_T][N][G * K]: the deltas of a backward pass (allocated by the first one, freed by destroy)
 };
 
 // the tensor a type binds; nullptr: not one of the 23 RNN types (at global scope: checked_slot finds it by its argument)
@@ -154,6 +157,7 @@ LIBXSMM_API libxsmm_dnn_rnncell* libxsmm_dnn_create_rnncell(libxsmm_dnn_rnncell_
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_destroy_rnncell(const libxsmm_dnn_rnncell* handle)
 { // :140-152
   if (nullptr == handle) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
+  if (nullptr != handle->deltas) dev_free(handle->deltas); // (only a backward pass on a device ever sets it)
   free(const_cast<libxsmm_dnn_rnncell*>(handle));
   return LIBXSMM_DNN_SUCCESS;
 }
@@ -353,10 +357,167 @@ LIBXSMM_API libxsmm_blasint libxsmm_dnn_rnncell_get_sequence_length(libxsmm_dnn_
   return nullptr != h ? h->T : 0;
 }
 
+namespace {
+
+// The chain order of the backward reductions over the G * K filter columns (lstm bwdupd template :255-270, core template :205-292):
+// for every chunk KB of K/BF indices the gates i, c, f, o in turn; BF depends on K alone. Adjacent pieces are one segment.
+int build_bwd_segments(int cell, int K, int bk, RnnBwdSeg* seg)
+{
+  int n = 0;
+  const auto add = [&](int start, int len) {
+    if (len <= 0) return;
+    if (n > 0 && seg[n - 1].start + seg[n - 1].len == start) { seg[n - 1].len += len; return; }
+    seg[n].start = start; seg[n].len = len; ++n;
+  };
+  if (K < 1 || bk < 1 || 0 != K % bk) return 0;
+  if (is_simple(cell)) { add(0, K); return n; }
+  if (LIBXSMM_DNN_RNNCELL_LSTM != cell) return 0;
+  const int kblocks = K / bk;
+  int bf = 1;
+  if (K > 1024 && K <= 2048) { bf = 8; while (0 != kblocks % bf) --bf; }
+  if (K > 2048) { bf = 16; while (0 != kblocks % bf) --bf; }
+  const int len = kblocks / bf * bk;
+  for (int kb = 0; kb < bf; ++kb) for (int q = 0; q < 4; ++q) add(q * K + kb * len, len);
+  return n;
+}
+
+std::mutex delta_lock; // (one for all handles: it is held for an allocation, once per handle)
+
+// BWD, UPD and BWDUPD of the simple cells and the LSTM. Launches: one per step (the recurrence), the LSTM's dhp,
+// dx of all steps (one per 65535 steps), and dw, dr, db: a function of the sequence length and the kind alone.
+libxsmm_dnn_err_t execute_backward(libxsmm_dnn_rnncell* h, libxsmm_dnn_compute_kind kind, int start_thread, int tid)
+{
+  const bool bwd = (LIBXSMM_DNN_COMPUTE_KIND_BWD == kind || LIBXSMM_DNN_COMPUTE_KIND_BWDUPD == kind);
+  const bool upd = (LIBXSMM_DNN_COMPUTE_KIND_UPD == kind || LIBXSMM_DNN_COMPUTE_KIND_BWDUPD == kind);
+  if (!bwd && !upd) return LIBXSMM_DNN_ERR_INVALID_KIND;
+  const libxsmm_dnn_rnncell_desc& d = h->desc;
+  const int cell = (int)d.cell_type;
+  const bool simple = is_simple(cell), lstm = LIBXSMM_DNN_RNNCELL_LSTM == cell;
+  if (!simple && !lstm) return LIBXSMM_DNN_ERR_INVALID_KIND; // (the GRU's backward is not built)
+  if (nullptr == h->dxt && nullptr == h->dcsp && nullptr == h->dhp && nullptr == h->dw && nullptr == h->dr && nullptr == h->db && nullptr == h->dcs && nullptr == h->dht) {
+    return LIBXSMM_DNN_ERR_INVALID_KIND; // (no gradient tensor at all: the answer from before these passes existed)
+  }
+  if (LIBXSMM_DNN_TENSOR_FORMAT_NC != d.buffer_format || LIBXSMM_DNN_TENSOR_FORMAT_CK != d.filter_format) return LIBXSMM_DNN_ERR_INVALID_FORMAT_GENERAL;
+  // what the templates read and write under this kind
+  if (nullptr == h->r || nullptr == h->dht) return LIBXSMM_DNN_ERR_DATA_NOT_BOUND;
+  if (simple && nullptr == h->internal_z) return LIBXSMM_DNN_ERR_DATA_NOT_BOUND;
+  if (lstm && (nullptr == h->csp || nullptr == h->cst || nullptr == h->it || nullptr == h->ft || nullptr == h->ot || nullptr == h->cit || nullptr == h->cot
+    || nullptr == h->dcs || nullptr == h->dcsp || nullptr == h->dhp)) return LIBXSMM_DNN_ERR_DATA_NOT_BOUND;
+  if (bwd && (nullptr == h->w || nullptr == h->dxt)) return LIBXSMM_DNN_ERR_DATA_NOT_BOUND;
+  if (upd && (nullptr == h->xt || nullptr == h->hp || nullptr == h->ht || nullptr == h->dw || nullptr == h->dr || nullptr == h->db)) return LIBXSMM_DNN_ERR_DATA_NOT_BOUND;
+  const int G = gates_of(cell);
+  const long long N = d.N, C = d.C, K = d.K, maxT = d.max_T, limit = 1LL << 31;
+  if (N < 1 || C < 1 || K < 1 || d.threads < 1) return LIBXSMM_DNN_ERR_GENERAL;
+  if (maxT * N * C >= limit || maxT * N * K >= limit || C * G * K >= limit || K * G * K >= limit) return LIBXSMM_DNN_ERR_GENERAL;
+  const int ltid = tid - start_thread;
+  if (ltid < 0) return LIBXSMM_DNN_ERR_GENERAL;
+  const int T = h->T;
+  // the recurrence and dx own rows as the forward does; dw, dr and db sum over all rows, and there is no barrier between calls: with
+  // UPD or BWDUPD logical thread 0 launches the whole pass and the others have nothing to do
+  long long b0 = 0, b1 = N / h->bn;
+  if (upd) { if (0 != ltid) return LIBXSMM_DNN_SUCCESS; }
+  else if (!thread_share(N / h->bn, d.threads, ltid, &b0, &b1)) return LIBXSMM_DNN_SUCCESS;
+  if (T < 1) return LIBXSMM_DNN_SUCCESS;
+  const int n0 = (int)(b0 * h->bn), n1 = (int)(b1 * h->bn);
+  if (((long long)(n1 - n0) + 63) / 64 > 65535) return LIBXSMM_DNN_ERR_GENERAL; // (more row tiles than a grid has: nothing is written)
+  RnnBwdChainArgs g; memset(&g, 0, sizeof(g));
+  g.nseg = build_bwd_segments(cell, (int)K, h->bk, g.seg);
+
+  if (!device_ready()) { fail_no_device("libxsmm_dnn_rnncell_execute_st"); return LIBXSMM_DNN_ERR_GENERAL; }
+  void* const stream = device().stream;
+  const long long ld = G * K, nk = N * K, nc = N * C, nld = N * ld;
+  float* deltas;
+  {
+    const std::lock_guard<std::mutex> guard(delta_lock);
+    if (nullptr == h->deltas) h->deltas = static_cast<float*>(dev_alloc((size_t)maxT * (size_t)nld * sizeof(float)));
+    deltas = h->deltas;
+  }
+  if (nullptr == deltas) return LIBXSMM_DNN_ERR_GENERAL;
+  libxsmm_dnn_tensor_datalayout zl; memset(&zl, 0, sizeof(zl));
+  libxsmm_dnn_tensor_dimtype zt[1] = { LIBXSMM_DNN_TENSOR_DIMTYPE_K };
+  unsigned int zs[1] = { (unsigned int)(maxT * N * K) };
+  zl.dim_type = zt; zl.dim_size = zs; zl.num_dims = 1; zl.datatype = LIBXSMM_DNN_DATATYPE_F32;
+  libxsmm_dnn_tensor ztensor; ztensor.layout = &zl; ztensor.data = h->internal_z; ztensor.scf = 0;
+  Staging s;
+  const Operand* const orr = s.add(h->r); const Operand* const odh = s.add(h->dht);
+  const Operand *oz = nullptr, *ow = nullptr, *odx = nullptr, *ox = nullptr, *ohp = nullptr, *oh = nullptr, *odw = nullptr, *odr = nullptr, *odb = nullptr;
+  const Operand *ocsp = nullptr, *ocs = nullptr, *oi = nullptr, *of = nullptr, *oo = nullptr, *oci = nullptr, *oco = nullptr, *odcs = nullptr, *odcsp = nullptr, *odhp = nullptr;
+  if (simple) oz = s.add(&ztensor);
+  if (lstm) {
+    ocsp = s.add(h->csp); ocs = s.add(h->cst); oi = s.add(h->it); of = s.add(h->ft); oo = s.add(h->ot); oci = s.add(h->cit); oco = s.add(h->cot);
+    odcs = s.add(h->dcs); odcsp = s.add(h->dcsp); odhp = s.add(h->dhp);
+  }
+  if (bwd) { ow = s.add(h->w); odx = s.add(h->dxt); }
+  if (upd) { ox = s.add(h->xt); ohp = s.add(h->hp); oh = s.add(h->ht); odw = s.add(h->dw); odr = s.add(h->dr); odb = s.add(h->db); }
+  if (!s.place()) return LIBXSMM_DNN_ERR_GENERAL;
+  const auto f32 = [](const Operand* o) { return static_cast<float*>(dev_of(o)); };
+  for (const Operand* o : { orr, odh, oz, ow, odx, ox, ohp, oh, odw, odr, odb, ocsp, ocs, oi, of, oo, oci, oco, odcs, odcsp, odhp }) {
+    if (nullptr != o && 0 != reinterpret_cast<uintptr_t>(o->dev) % sizeof(float)) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  const auto chain = [&](const RnnBwdChainArgs& a) { const char* name = ""; const int e = launch_rnn_bwd_chain(a, stream, &name); return launched(name, e); };
+
+  g.n0 = n0; g.n1 = n1; g.ld = (int)ld; g.act = cell;
+  for (int j = T - 1; j >= 0; --j) { // the recurrence: the deltas of step j from those of step j + 1
+    RnnBwdChainArgs a = g;
+    a.filt = f32(orr); a.M = (int)K; a.nz = 1;
+    a.last = (T - 1 == j) ? 1 : 0;
+    if (0 != a.last) a.nseg = 0;
+    a.delta = deltas + (long long)(j + 1 < maxT ? j + 1 : j) * nld; // (not read at the last step)
+    a.dstep = deltas + (long long)j * nld;
+    a.dh = f32(odh) + j * nk;
+    if (simple) { a.epi = RNN_BWD_EPI_SIMPLE; a.z = f32(oz) + j * nk; }
+    else {
+      a.epi = RNN_BWD_EPI_LSTM;
+      a.gi = f32(oi) + j * nk; a.gf = f32(of) + j * nk; a.go = f32(oo) + j * nk; a.gci = f32(oci) + j * nk; a.gco = f32(oco) + j * nk;
+      a.csprev = (0 == j) ? f32(ocsp) : f32(ocs) + (j - 1) * nk;
+      a.dcs = f32(odcs); a.dcsp = f32(odcsp);
+    }
+    if (!chain(a)) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  if (lstm) { // dhp: the chain of step 0, stored without an add
+    RnnBwdChainArgs a = g;
+    a.epi = RNN_BWD_EPI_STORE; a.filt = f32(orr); a.M = (int)K; a.nz = 1; a.delta = deltas; a.out = f32(odhp);
+    if (!chain(a)) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  if (bwd) { // dx of all steps: no dependence between them
+    for (int s0 = 0; s0 < T; s0 += 65535) {
+      RnnBwdChainArgs a = g;
+      a.epi = RNN_BWD_EPI_STORE; a.filt = f32(ow); a.M = (int)C;
+      a.nz = (T - s0 < 65535) ? (T - s0) : 65535; a.zd = nld; a.zo = nc;
+      a.delta = deltas + (long long)s0 * nld; a.out = f32(odx) + s0 * nc;
+      if (!chain(a)) return LIBXSMM_DNN_ERR_GENERAL;
+    }
+  }
+  if (upd) {
+    const char* name = "";
+    RnnBwdWeightArgs a; memset(&a, 0, sizeof(a));
+    a.delta = deltas; a.ld = (int)ld; a.N = (int)N; a.T = T;
+    a.act = f32(ox); a.M = (int)C; a.out = f32(odw); a.shift = 0;
+    int e = launch_rnn_bwd_weight(a, stream, &name);
+    if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
+    a.act = f32(oh); a.act0 = f32(ohp); a.M = (int)K; a.out = f32(odr); a.shift = 1; // (step 0 multiplies hp, also with one step: 8r)
+    e = launch_rnn_bwd_weight(a, stream, &name);
+    if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
+    e = launch_rnn_bwd_bias(deltas, f32(odb), (int)ld, (int)N, T, stream, &name);
+    if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  return s.finish({ odx, odw, odr, odb, odcsp, odhp }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
+}
+
+} // namespace
+
+LIBXSMM_API int libxsmm_amd_rnn_bwd_segments(libxsmm_dnn_rnncell_type cell_type, int K, int bk, int* segments, int capacity)
+{
+  RnnBwdSeg seg[RNN_BWD_MAX_SEG];
+  const int n = build_bwd_segments((int)cell_type, K, bk, seg);
+  for (int i = 0; i < n && i < capacity && nullptr != segments; ++i) { segments[2 * i] = seg[i].start; segments[2 * i + 1] = seg[i].len; }
+  return n;
+}
+
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_rnncell_execute_st(libxsmm_dnn_rnncell* h, libxsmm_dnn_compute_kind kind, int start_thread, int tid)
 { // :2220-2258 and src/libxsmm_dnn_rnncell_forward.c:218-272
   if (nullptr == h) return LIBXSMM_DNN_ERR_INVALID_HANDLE;
-  if (LIBXSMM_DNN_COMPUTE_KIND_FWD != kind) return LIBXSMM_DNN_ERR_INVALID_KIND; // (BWD, UPD, BWDUPD: not built; ALL and the rest: the reference's answer)
+  if (LIBXSMM_DNN_COMPUTE_KIND_FWD != kind) return execute_backward(h, kind, start_thread, tid); // (ALL and the rest: the reference's answer, _ERR_INVALID_KIND)
   const libxsmm_dnn_rnncell_desc& d = h->desc;
   if (LIBXSMM_DNN_TENSOR_FORMAT_NC != d.buffer_format || LIBXSMM_DNN_TENSOR_FORMAT_CK != d.filter_format) return LIBXSMM_DNN_ERR_INVALID_FORMAT_GENERAL;
   const int cell = (int)d.cell_type;

@@ -1,0 +1,261 @@
+"""The backward and update passes of the RNN cell layer without a GPU: the restatement of tests/rnn_bwd_common.py against what the
+reference returned (tests/golden/rnn_bwd.npz, written by tools/golden/rnn_bwd_capture.py from the unmodified reference under
+LIBXSMM_TARGET=hsw), the backward segment list against a table read from the templates, a float64 guard of what the capture computes,
+the new statuses of execute_st, the condition on the inputs that lets the GPU tests compare bits, and the compilation of
+kernels/rnn_bwd.hip for gfx950 without scratch memory."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import rnn_common as rc
+import rnn_bwd_common as rb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(os.path.join(rc.GOLDEN, "rnn_bwd.npz"))
+
+
+def test_the_file_holds_the_cases_of_the_common_module(golden):
+    for name, d in rb.captured_cases().items():
+        assert list(golden[name + "/desc"]) == [d[k] for k in rc.DESC_FIELDS] + [d["seq"], d["seed"]]
+        assert list(golden[name + "/meta"]) == [rc.Handle(d).status, 0, 0, 0, 0]
+    assert not any(key.startswith(name + "/") for name in rb.UNCAPTURED_CASES for key in golden.files)
+    assert os.path.getsize(os.path.join(rc.GOLDEN, "rnn_bwd.npz")) < 512 * 1024
+
+
+@pytest.mark.parametrize("kind", rb.KINDS, ids=lambda k: rb.KIND_NAMES[k])
+@pytest.mark.parametrize("name", sorted(rb.captured_cases()))
+def test_restatement_equals_capture(golden, name, kind):
+    """bit for bit, every gradient tensor (a large one through its CRC-32); what a kind does not write, and the steps of dx beyond the
+    sequence length, keep their fill, in the capture as in the restatement"""
+    d = rb.captured_cases()[name]
+    t, out = rb.expected(name, kind)
+    assert list(golden[name + "/in_crc"]) == [rc.crc(t[key]) for key in rb.read(d["cell"])], "the inputs are not those of the capture"
+    crcs, untouched = golden["%s/%d/crc" % (name, kind)], golden["%s/%d/untouched" % (name, kind)]
+    for i, key in enumerate(rb.GRADS):
+        assert bool(untouched[i]) == (key not in rb.written(d["cell"], kind)), key
+        stored = "%s/%d/%s" % (name, kind, key)
+        if stored in golden.files:
+            assert np.array_equal(out[key].reshape(-1).view(np.uint32), golden[stored].view(np.uint32)), key
+        assert rc.crc(out[key]) == crcs[i], key
+    T = rc.Handle(d).T
+    if "dx" in rb.written(d["cell"], kind):
+        assert np.all(out["dx"][T:].view(np.uint32) == 0xffffffff)
+        if name not in rb.SPECIAL_CASES:
+            assert not np.any(out["dx"][:T].view(np.uint32) == 0xffffffff)
+    for key in ("dcsp", "dhp"):  # the first step's slot alone is written
+        assert np.all(out[key][1:].view(np.uint32) == 0xffffffff)
+
+
+# The backward templates' blocking depends on K alone (lstm bwdupd template :255-270): K with bk = 16 -> BF
+BF_TABLE = {1024: 1, 1040: 5, 2048: 8, 2064: 3}
+
+
+def test_segment_list_against_the_table(xs):
+    for K, bf in BF_TABLE.items():
+        assert bf == rb.bwd_blocking_factor(K, K // 16)
+        n = K // bf
+        want = [(0, 4 * K)] if bf == 1 else [(q * K + kb * n, n) for kb in range(bf) for q in range(4)]  # per chunk: i, c, f, o
+        assert want == xs.rnn_bwd_segments(rc.LSTM, K, 16)
+        for cell in (rc.RELU, rc.SIGMOID, rc.TANH):
+            assert [(0, K)] == xs.rnn_bwd_segments(cell, K, 16)
+        assert [] == xs.rnn_bwd_segments(rc.GRU, K, 16)
+    for name, bf in (("bf5_lstm", 5), ("bf12_lstm", 12)):
+        d = rb.COMPUTE_CASES[name]
+        seg = xs.rnn_bwd_segments(rc.LSTM, d["K"], d["bk"])
+        assert bf == rb.bwd_blocking_factor(d["K"], d["K"] // d["bk"]) and len(seg) == 4 * bf and all(s[1] == d["K"] // bf for s in seg)
+        assert [s[0] for s in seg[:5]] == [0, d["K"], 2 * d["K"], 3 * d["K"], d["K"] // bf]
+    assert [] == xs.rnn_bwd_segments(rc.LSTM, 30, 7)
+
+
+def act_prime64(cell, z):
+    z = np.float64(z)
+    if cell == rc.RELU:
+        return 0.0 if z < 0 else 1.0
+    if cell == rc.SIGMOID:
+        s = 1.0 / (1.0 + np.exp(-z))
+        return (1.0 - s) * s
+    return 1.0 - np.tanh(z) ** 2
+
+
+@pytest.mark.parametrize("cell", rb.CELLS, ids=lambda c: rc.CELL_NAMES[c])
+def test_one_element_of_each_kind_in_float64(golden, cell):
+    """guards that the capture computes what it is believed to: one dw, one dx and one delta element recomputed naively in float64,
+    within the bound of an fp32 chain of n terms, n * 2^-24 * sum |a * b|"""
+    name = "one_" + rc.CELL_NAMES[cell]
+    d = rb.COMPUTE_CASES[name]
+    t, out = rb.expected(name, rb.BWDUPD)
+    for key in ("dx", "dw"):
+        assert np.array_equal(out[key].reshape(-1).view(np.uint32), golden["%s/%d/%s" % (name, rb.BWDUPD, key)].view(np.uint32))
+    u, T, K, N = 2.0 ** -24, rc.Handle(d).T, d["K"], d["N"]
+    delta = out["delta"].astype(np.float64)
+    n, c, j = 3, 5, 6 + (K if cell == rc.LSTM else 0)  # a row, an input feature, a filter column (LSTM: of the c gate)
+    w, r, x = (t[key].astype(np.float64) for key in ("w", "r", "x"))
+    terms = w[c] * delta[1, n]                                 # dx[1][n][c]: G * K products
+    assert abs(out["dx"][1, n, c] - terms.sum()) <= terms.size * u * np.abs(terms).sum()
+    terms = x[:T, :, c] * delta[:T, :, j]                      # dw[c][j]: T * N products
+    assert abs(out["dw"][c, j] - terms.sum()) <= terms.size * u * np.abs(terms).sum()
+    if cell == rc.LSTM:  # di of the last step (no chain): (dcs + dh o (1 - co^2)) ci i (1 - i); twelve roundings, each term at its magnitude
+        k, s = 7, T - 1
+        i, o, ci, co = (np.float64(t[key][s, n, k]) for key in ("i", "o", "ci", "co"))
+        dcs, dh = np.float64(t["dcs"][0, n, k]), np.float64(t["dh"][s, n, k])
+        want = (dcs + dh * o * (1 - co * co)) * ci * i * (1 - i)
+        mag = (abs(dcs) + abs(dh * o) * (1 + co * co)) * abs(ci) * abs(i) * (1 + abs(i))
+        assert abs(out["delta"][s, n, k] - want) <= 12 * u * mag
+    else:  # delta of step T - 2: (dh + sum r[k][c] delta[T - 1][c]) act'(z): K products, the start, act' (at most 1) and the last multiply
+        k, s = 7, T - 2
+        terms = np.concatenate(([np.float64(t["dh"][s, n, k])], r[k] * delta[s + 1, n]))
+        a = act_prime64(cell, t["z"][s, n, k])
+        assert abs(out["delta"][s, n, k] - terms.sum() * a) <= (K + 5) * u * np.abs(terms).sum() * max(abs(a), 1.0)
+
+
+def bind_all(xs, handle, buf, cell, skip=()):
+    """every tensor a backward pass may touch, on one small buffer (nothing is ever read)"""
+    types = [rc.IN_TYPE.get(k, rc.OUT_TYPE.get(k)) for k in rc.read(cell) + rc.written(cell) if k != "z"]
+    types += [rb.GRAD_TYPE[k] for k in ("dx", "dw", "dr", "db", "dh")] + ([rb.GRAD_TYPE[k] for k in ("dcs", "dcsp", "dhp")] if cell == rc.LSTM else [])
+    return {ty: xs.rnn_bind_new(handle, ty, buf) for ty in types if ty not in skip}
+
+
+# what each kind needs bound: the tensors the templates read or write under it
+NEEDS = {
+    "simple": {rb.BWD: ("r", "dh", "w", "dx"), rb.UPD: ("r", "dh", "x", "hp", "h", "dw", "dr", "db")},
+    "lstm": {rb.BWD: ("r", "dh", "csp", "cs", "i", "f", "o", "ci", "co", "dcs", "dcsp", "dhp", "w", "dx"),
+             rb.UPD: ("r", "dh", "csp", "cs", "i", "f", "o", "ci", "co", "dcs", "dcsp", "dhp", "x", "hp", "h", "dw", "dr", "db")},
+}
+TYPE_OF = dict(rc.IN_TYPE, **rc.OUT_TYPE, **rb.GRAD_TYPE)
+
+
+def test_new_statuses_answer_before_any_device_probe(xs):
+    """this machine may have no GPU at all: every refusal of a backward kind, and the calls that have nothing to do, must answer"""
+    L = xs.lib()
+    buf = np.zeros(1 << 16, dtype=np.uint8)
+    for cell in rb.CELLS + (rc.GRU,):
+        d = rc.desc(4, 8, 8, 2, cell, bn=2, bc=4, bk=4, threads=2)
+        handle, st = xs.rnn_create(d["N"], d["C"], d["K"], d["max_T"], cell, d["bn"], d["bc"], d["bk"], d["threads"])
+        assert handle and 0 == st
+        for kind in rb.KINDS:  # no gradient tensor bound: as before these passes existed
+            assert rc.ERR_INVALID_KIND == xs.rnn_execute(handle, kind)
+        one = xs.rnn_bind_new(handle, rb.GRAD_TYPE["db"], buf)
+        for kind in (rc.ALL, 7):
+            assert rc.ERR_INVALID_KIND == xs.rnn_execute(handle, kind)
+        for kind in rb.KINDS:  # one gradient tensor: the pass looks for the rest (the GRU has no backward pass)
+            assert (rc.ERR_INVALID_KIND if cell == rc.GRU else rc.ERR_DATA_NOT_BOUND) == xs.rnn_execute(handle, kind)
+        tensors = bind_all(xs, handle, buf, cell, skip=(rb.GRAD_TYPE["db"],))
+        tensors[rb.GRAD_TYPE["db"]] = one
+        if cell == rc.GRU:
+            for kind in rb.KINDS:
+                assert rc.ERR_INVALID_KIND == xs.rnn_execute(handle, kind)
+        else:
+            simple = cell != rc.LSTM
+            if simple:
+                for kind in rb.KINDS:
+                    assert rc.ERR_DATA_NOT_BOUND == xs.rnn_execute(handle, kind)  # z: the internal state
+                assert 0 == L.libxsmm_dnn_rnncell_bind_internalstate(handle, rb.BWDUPD, xs.dptr(buf))
+            needs = NEEDS["simple" if simple else "lstm"]
+            for kind in rb.KINDS:
+                need = set(needs[rb.BWD] if kind != rb.UPD else ()) | set(needs[rb.UPD] if kind != rb.BWD else ())
+                for key, ty in TYPE_OF.items():
+                    if ty not in tensors:
+                        continue
+                    assert 0 == L.libxsmm_dnn_rnncell_release_tensor(handle, ty)
+                    if key in need:
+                        assert rc.ERR_DATA_NOT_BOUND == xs.rnn_execute(handle, kind), (kind, key)
+                    assert 0 == L.libxsmm_dnn_rnncell_bind_tensor(handle, tensors[ty], ty)
+                assert rc.ERR_GENERAL == xs.rnn_execute(handle, kind, 1, 0)  # logical thread -1
+            before = L.libxsmm_amd_launch_count()
+            assert 0 == xs.rnn_execute(handle, rb.BWD, 0, 2) == xs.rnn_execute(handle, rb.BWD, 3, 40)  # beyond desc.threads: nothing to do
+            assert 0 == xs.rnn_execute(handle, rb.UPD, 0, 1) == xs.rnn_execute(handle, rb.BWDUPD, 0, 1)  # all but thread 0 of an update
+            assert 0 == L.libxsmm_dnn_rnncell_set_sequence_length(handle, 0)
+            for kind in rb.KINDS:
+                assert 0 == xs.rnn_execute(handle, kind)  # no step: nothing to do
+            assert before == L.libxsmm_amd_launch_count() and not buf.any()
+        for tensor in tensors.values():
+            L.libxsmm_dnn_destroy_tensor(tensor)
+        assert 0 == L.libxsmm_dnn_destroy_rnncell(handle)
+    # the format check comes after the look for a gradient tensor and before the look for the rest
+    handle, st = xs.rnn_create(4, 8, 8, 2, rc.LSTM, 2, 4, 4, 1, buffer_format=rc.FMT_NCPACKED, filter_format=rc.FMT_CKPACKED)
+    assert handle
+    assert rc.ERR_INVALID_KIND == xs.rnn_execute(handle, rb.BWD)
+    tensor = xs.rnn_bind_new(handle, rb.GRAD_TYPE["db"], buf)
+    for kind in rb.KINDS:
+        assert rc.ERR_INVALID_FORMAT_GENERAL == xs.rnn_execute(handle, kind)
+    L.libxsmm_dnn_destroy_tensor(tensor)
+    assert 0 == L.libxsmm_dnn_destroy_rnncell(handle)
+    # a share of more than 65535 tiles of 64 rows is refused whole
+    d = rb.LIMIT_CASES["manyrows_relu"]
+    handle, st = xs.rnn_create(d["N"], d["C"], d["K"], d["max_T"], d["cell"], d["bn"], d["bc"], d["bk"], 1)
+    assert handle and 0 == st
+    tensors = bind_all(xs, handle, buf, d["cell"])
+    assert 0 == L.libxsmm_dnn_rnncell_bind_internalstate(handle, rb.BWD, xs.dptr(buf))
+    for kind in rb.KINDS:
+        assert rc.ERR_GENERAL == xs.rnn_execute(handle, kind)
+    assert not buf.any()
+    for tensor in tensors.values():
+        L.libxsmm_dnn_destroy_tensor(tensor)
+    assert 0 == L.libxsmm_dnn_destroy_rnncell(handle)
+
+
+def exact_distance_ulps(kind, arg, mid):
+    """|exp(arg) or tanh(arg) - mid| in fp64 ulps of the value, to more than fp64 precision: mpmath if it is there, else long double"""
+    try:
+        import mpmath
+        mpmath.mp.prec = 200
+        exact = mpmath.exp(mpmath.mpf(arg)) if kind == "exp" else mpmath.tanh(mpmath.mpf(arg))
+        ulp = mpmath.mpf(2) ** (int(mpmath.floor(mpmath.log(abs(exact), 2))) - 52)
+        return float(abs(exact - mpmath.mpf(mid)) / ulp)
+    except ImportError:
+        x = np.longdouble(arg)
+        exact = np.exp(x) if kind == "exp" else np.tanh(x)
+        return float(abs(exact - np.longdouble(mid)) / np.longdouble(np.spacing(np.float64(exact))))
+
+
+def test_no_transcendental_of_the_backward_pass_is_a_hard_case():
+    """A condition on the inputs (met by choosing seeds), not a tolerance: of every exp(-z) and tanh(z) the sigmoid and tanh cells'
+    backward evaluates in every captured, uncaptured, special and threads case, none lies within 64 fp64 ulps of a float rounding
+    boundary, so a device exp / tanh that differs from the host libm's by a few fp64 ulps still rounds to the same float. Flushed or
+    saturated results and non-finite arguments are exempt. (The ReLU cell and the LSTM evaluate none: the limit cases are ReLU cells.)"""
+    count, worst = 0, (np.inf, None)
+    for name, d in list(rb.all_cases().items()) + list(rb.THREAD_CASES.items()):
+        log = []
+        rb.backward(rc.Handle(dict(d, threads=1)), rb.cached_inputs(name), rb.BWD, log=log)
+        assert bool(log) == (d["cell"] in (rc.SIGMOID, rc.TANH))
+        for kind in ("exp", "tanh"):
+            arg = np.array([a for k, a in log if k == kind], dtype=np.float64)
+            count += arg.size
+            with np.errstate(all="ignore"):
+                v = np.exp(arg) if kind == "exp" else np.tanh(arg)
+                f = v.astype(np.float32)
+                live = np.isfinite(f) & (f != 0) & (np.abs(f) != 1) & np.isfinite(arg)
+                arg, v, f = arg[live], v[live], f[live]
+                f64 = f.astype(np.float64)
+                mids = [(f64 + np.nextafter(f, np.float32(side)).astype(np.float64)) / 2 for side in (-np.inf, np.inf)]
+                ulps = [np.abs(v - m) / np.spacing(np.abs(v)) for m in mids]
+            for m, u in zip(mids, ulps):
+                for idx in np.nonzero(u < 1024)[0]:
+                    dist = exact_distance_ulps(kind, float(arg[idx]), float(m[idx]))
+                    if dist < worst[0]:
+                        worst = (dist, (name, kind, float(arg[idx])))
+    assert count > 100000
+    assert worst[0] >= 64, worst
+
+
+def test_rnn_bwd_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    """the device code alone, to assembly: every kernel is there, none uses scratch memory or spills a register, the reductions run on
+    the matrix cores and the sigmoid's divide is the correctly rounded sequence"""
+    out = tmp_path / "rnn_bwd.s"
+    src = os.path.join(ROOT, "libxsmm-1_amd", "csrc", "kernels", "rnn_bwd.hip")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
+                    src, "-o", str(out)], check=True, capture_output=True)
+    text = out.read_text()
+    for kernel in ("rnn_bwd_chainILi0EE", "rnn_bwd_chainILi1EE", "rnn_bwd_chainILi2EE", "rnn_bwd_weight", "rnn_bwd_bias"):
+        assert kernel in text
+    assert "v_mfma_f32_32x32x2" in text and "v_div_fixup_f32" in text and "v_div_fmas_f32" in text
+    for field in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
+        values = [int(v) for v in re.findall(r"\.%s:\s*(\d+)" % field, text)]
+        assert len(values) == 5 and not any(values), (field, values)
