@@ -414,4 +414,27 @@ LIBXSMM_API int libxsmm_amd_matdiff_batch(libxsmm_matdiff_info* info, libxsmm_ma
   libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst,
   long long stride_ref, long long stride_tst, long long batch);
 
+/* ---- DNN tensor copy-in / copy-out (libxsmm_dnn_copyin_tensor / _copyout_tensor, see libxsmm_dnn_tensor.h) ------------------- */
+#include "libxsmm_dnn_tensor.h"
+/** The reference forms without their wait: the same checks in the same order and the same statuses, then both `tensor`'s
+ *  data and `data` must be memory the GPU reaches (device, pinned or managed); otherwise, or without a device, the call
+ *  returns LIBXSMM_DNN_ERR_GENERAL and writes nothing. Nothing is staged: one kernel is queued on the calling thread's
+ *  stream (libxsmm_amd_set_stream) and the call returns without waiting for it, so a consumer queued on that stream sees
+ *  the result. An empty tensor returns LIBXSMM_DNN_SUCCESS and launches nothing. Inside libxsmm_amd_defer_begin/end the
+ *  calls are not recorded: they seal the open burst and run in call order. Operands that overlap are undefined. */
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copyin_tensor_async(const libxsmm_dnn_tensor* tensor, const void* data, libxsmm_dnn_tensor_format in_format);
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copyout_tensor_async(const libxsmm_dnn_tensor* tensor, void* data, libxsmm_dnn_tensor_format out_format);
+/** The launch geometry of a copy between `layout` and `plain_format` (in != 0: copy-in), without a device: the status the copy
+ *  would give for that layout and format, and on LIBXSMM_DNN_SUCCESS
+ *    plan[0]  form: 0 the same order on both sides (channel tensors; activations of one pixel), 1 activation, 2 filter
+ *    plan[1]  bytes per element
+ *    plan[2]  independent blocks
+ *    plan[3]  rows per block on the plain side
+ *    plan[4]  contiguous run per row, in elements
+ *    plan[5]  rows of a block held in LDS per pass (fewer than plan[3] where a block is cut; 0: the copy does not go through LDS)
+ *    plan[6]  work items (tiles; 16-byte units of form 0; work-groups' worth of elements where plan[5] is 0 otherwise)
+ *    plan[7]  work-groups launched
+ *  The launcher takes its geometry from the same function. */
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copy_plan(const libxsmm_dnn_tensor_datalayout* layout, libxsmm_dnn_tensor_format plain_format, int in, long long plan[8]);
+
 #endif /* LIBXSMM_AMD_H */

@@ -155,13 +155,23 @@ LIBXSMM_API unsigned char libxsmm_dnn_get_qtensor_scf(const libxsmm_dnn_tensor* 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_set_qtensor_scf(libxsmm_dnn_tensor* tensor, const unsigned char scf);
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_destroy_tensor(const libxsmm_dnn_tensor* tensor);
 
-/** Zero, copy-in from and copy-out to a plain format (:384-390). Served: the layouts a fully-connected handle creates --
- *  activations (tensor_type input / output kinds) from / to LIBXSMM_DNN_TENSOR_FORMAT_NCHW, filters from / to _KCRS, blocked
- *  (_FORMAT_LIBXSMM, custom format 1) tensors of fp32 or bf16. Another plain format returns _ERR_UNSUPPORTED_SRC_FORMAT (in) /
- *  _DST_FORMAT (out), a tensor that is not blocked _ERR_UNSUPPORTED_DST_FORMAT (in) / _SRC_FORMAT (out), another data type
- *  _ERR_UNSUPPORTED_DATATYPE, another tensor type _ERR_INVALID_TENSOR -- the reference's statuses. These are host loops and no
- *  hot path: the calling thread's stream is waited for first, a tensor or plain buffer in plain device memory travels through
- *  a host image, and the call is complete on return. */
+/** Zero, copy-in from and copy-out to a plain format (:384-390). Served: blocked (_FORMAT_LIBXSMM) tensors of fp32 or bf16 --
+ *  activations (tensor_type input / output kinds, custom format 1) from / to LIBXSMM_DNN_TENSOR_FORMAT_NCHW, filters (custom
+ *  format 1) from / to _KCRS, and the thirteen channel tensor types (bias, beta, gamma, expectval, rcpstddev, variance, scalar)
+ *  from / to _NCHW (the reference's rule for them): the same order on both sides. Checked in this order, with the reference's
+ *  statuses: another tensor type _ERR_INVALID_TENSOR, another plain format _ERR_UNSUPPORTED_SRC_FORMAT (in) / _DST_FORMAT
+ *  (out), a tensor that is not blocked _ERR_UNSUPPORTED_DST_FORMAT (in) / _SRC_FORMAT (out), another data type (the integer
+ *  types: no layer here creates such layouts) _ERR_UNSUPPORTED_DATATYPE; then custom format 2 _ERR_NOT_IMPLEMENTED, a wrong
+ *  number of dimensions _ERR_INVALID_LAYOUT, NULL data _ERR_INVALID_TENSOR. An empty tensor is a success and nothing is
+ *  launched. Operands that overlap are undefined, as in the reference.
+ *  Where both the tensor and the plain buffer are memory the CPU addresses (pageable, pinned, managed), or there is no device,
+ *  the copy is a host loop (the calling thread's stream is waited for first if the GPU may still be writing an operand) and
+ *  nothing is launched. Where at least one of them is plain device memory, the permutation is one kernel on the calling thread's
+ *  stream (libxsmm_amd_set_stream): an operand in pageable memory is staged through library scratch, pinned or managed memory is
+ *  read or written in place, nothing waits before the launch (stream order carries the dependence on earlier work), and the
+ *  call waits at its end: it is complete on return. libxsmm_amd_dnn_copyin_tensor_async / _copyout_tensor_async
+ *  (libxsmm_amd.h) are the forms without that wait. Inside libxsmm_amd_defer_begin/end the calls are not recorded: they seal
+ *  the open burst and run in call order. */
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_zero_tensor(const libxsmm_dnn_tensor* tensor);
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_copyin_tensor(const libxsmm_dnn_tensor* tensor, const void* data, const libxsmm_dnn_tensor_format in_format);
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_copyout_tensor(const libxsmm_dnn_tensor* tensor, void* data, const libxsmm_dnn_tensor_format out_format);

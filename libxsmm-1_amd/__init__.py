@@ -397,6 +397,9 @@ def _declare(L):
     sig("libxsmm_dnn_zero_tensor", u, vp)
     sig("libxsmm_dnn_copyin_tensor", u, vp, vp, i)
     sig("libxsmm_dnn_copyout_tensor", u, vp, vp, i)
+    sig("libxsmm_amd_dnn_copyin_tensor_async", u, vp, vp, i)
+    sig("libxsmm_amd_dnn_copyout_tensor_async", u, vp, vp, i)
+    sig("libxsmm_amd_dnn_copy_plan", u, lp, i, i, C.POINTER(C.c_longlong))
     sig("libxsmm_dnn_create_fullyconnected", vp, FullyconnectedDesc, up)
     sig("libxsmm_dnn_destroy_fullyconnected", u, vp)
     sig("libxsmm_dnn_fullyconnected_create_tensor_datalayout", lp, vp, i, up)
@@ -975,6 +978,13 @@ def dnn_link_tensor(layout, data):
     st = C.c_uint(0xdead)
     t = lib().libxsmm_dnn_link_tensor(layout, dptr(data), C.byref(st))
     return t, st.value
+
+
+def dnn_copy_plan(layout, plain_format, copy_in=True):
+    """libxsmm_amd_dnn_copy_plan; returns (status, the eight slots or None)"""
+    plan = (C.c_longlong * 8)()
+    st = lib().libxsmm_amd_dnn_copy_plan(layout, plain_format, 1 if copy_in else 0, plan)
+    return st, ([int(x) for x in plan] if 0 == st else None)
 
 
 def fc_bind_new(handle, ttype, data):

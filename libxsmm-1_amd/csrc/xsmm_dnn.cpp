@@ -3,10 +3,11 @@
 //
 // Reference: src/libxsmm_dnn.c:70-189 (errors, type sizes), :330-360 (link), :1000-1203 (layouts and tensors), :1206-1570
 // (copies, with src/template/libxsmm_dnn_tensor_{buffer_copy_{in,out}_nchw,filter_copy_{in,out}_kcrs}.tpl.c). Handles are
-// plain host structures and no function here but the three that touch tensor data asks for a device. Those three are not
-// a hot path: they are host loops over the tensor where the CPU addresses it (pageable, pinned, managed memory; the
-// calling thread's stream is waited for first if the GPU may still be writing it), and the same loops over a staged host
-// image where it cannot (plain device memory), complete on return either way.
+// plain host structures and no function here but those that touch tensor data asks for a device. Copy-in and copy-out are host
+// loops over the tensor where the CPU addresses both operands (pageable, pinned, managed memory; the calling thread's stream is
+// waited for first if the GPU may still be writing them) and one launch of kernels/dnn_copy.hip on the calling thread's stream
+// where an operand is plain device memory; the reference forms are complete on return either way, the
+// libxsmm_amd_*_async forms do not wait.
 #include "xsmm_dnn_internal.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -298,31 +299,99 @@ void copy_filter(char* blocked, char* plain, const unsigned int d[7], size_t ts,
     }
 }
 
-// in: plain -> tensor; otherwise tensor -> plain. The statuses are the reference's (:1206-1362, :1407-1570); the layouts served
-// are those a fully-connected handle creates (custom format 1; fp32 and bf16).
-libxsmm_dnn_err_t copy_tensor(const libxsmm_dnn_tensor* tensor, void* plain, libxsmm_dnn_tensor_format format, bool in)
+bool is_channel(libxsmm_dnn_tensor_type t) { return LIBXSMM_DNN_REGULAR_CHANNEL_BIAS <= t && t <= LIBXSMM_DNN_CHANNEL_SCALAR; } // the 13 of :1300-1312
+
+// What a copy between a layout and a plain format moves, or the status the reference gives instead (:1206-1362, :1407-1570: the
+// tensor type, the plain format, the tensor's format, the data type; then what is not provided here). Channel tensors (bias,
+// beta, gamma, statistics; template/libxsmm_dnn_tensor_bias_copy_{in,out}_nchw.tpl.c) have the same order on both sides:
+// fmb * bfm * lpb elements, the plain format is NCHW (the reference's rule).
+struct CopyShape { int form; unsigned int d[7]; size_t ts; };
+
+libxsmm_dnn_err_t copy_shape(const libxsmm_dnn_tensor_datalayout& l, libxsmm_dnn_tensor_format format, bool in, CopyShape* c)
+{
+  const libxsmm_dnn_err_t bad_plain = in ? LIBXSMM_DNN_ERR_UNSUPPORTED_SRC_FORMAT : LIBXSMM_DNN_ERR_UNSUPPORTED_DST_FORMAT;
+  const libxsmm_dnn_err_t bad_tensor = in ? LIBXSMM_DNN_ERR_UNSUPPORTED_DST_FORMAT : LIBXSMM_DNN_ERR_UNSUPPORTED_SRC_FORMAT;
+  const bool act = is_activation(l.tensor_type), fil = is_filter(l.tensor_type), chan = is_channel(l.tensor_type);
+  if (!act && !fil && !chan) return LIBXSMM_DNN_ERR_INVALID_TENSOR;
+  if (format != (fil ? LIBXSMM_DNN_TENSOR_FORMAT_KCRS : LIBXSMM_DNN_TENSOR_FORMAT_NCHW)) return bad_plain;
+  if (0 == (l.format & LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM)) return bad_tensor;
+  if (LIBXSMM_DNN_DATATYPE_F32 != l.datatype && LIBXSMM_DNN_DATATYPE_BF16 != l.datatype) return LIBXSMM_DNN_ERR_UNSUPPORTED_DATATYPE;
+  for (unsigned int& x : c->d) x = 0;
+  c->ts = libxsmm_dnn_typesize(l.datatype);
+  if (chan) {
+    if (l.num_dims != (LIBXSMM_DNN_DATATYPE_BF16 == l.datatype ? 3u : 2u)) return LIBXSMM_DNN_ERR_INVALID_LAYOUT;
+    c->form = DNN_COPY_FLAT; c->d[0] = 1;
+    for (unsigned int dim = 0; dim < l.num_dims; ++dim) c->d[0] *= l.dim_size[dim];
+    return LIBXSMM_DNN_SUCCESS;
+  }
+  if (LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM_1 != l.custom_format) return LIBXSMM_DNN_ERR_NOT_IMPLEMENTED;
+  c->form = act ? DNN_COPY_ACT : DNN_COPY_FIL;
+  return (act ? activation_dims(l, c->d) : filter_dims(l, c->d)) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_INVALID_LAYOUT;
+}
+
+// The geometry of a shape. dnn_copy_geom searches the LDS pitch, which costs the host tens of microseconds -- as much as the launch
+// of a small tensor takes -- and a network repeats a handful of shapes: the last eight are kept per thread.
+const DnnCopyGeom& geom_of(const CopyShape& c)
+{
+  struct Entry { CopyShape shape; DnnCopyGeom geom; bool used; };
+  static thread_local Entry cache[8] = {};
+  static thread_local unsigned int next = 0;
+  for (const Entry& e : cache) {
+    if (e.used && e.shape.form == c.form && e.shape.ts == c.ts && 0 == memcmp(e.shape.d, c.d, sizeof(c.d))) return e.geom;
+  }
+  Entry& e = cache[next++ % 8];
+  e.shape = c; e.geom = dnn_copy_geom(c.form, c.d, (int)c.ts); e.used = true;
+  return e.geom;
+}
+
+// The copy on the GPU: at least one operand is plain device memory (or the form is the one that does not wait). An operand in
+// pageable memory travels through scratch slot 0 -- only one can, the other is device memory. Nothing waits before the launch:
+// the stream orders the copy behind what was queued before. wait: complete on return.
+libxsmm_dnn_err_t copy_on_device(const CopyShape& c, void* tensor_data, int kind_tensor, void* plain, int kind_plain, size_t bytes, bool in, bool wait)
+{
+  void* const stream = device().stream; // (launches what is open on the thread inside libxsmm_amd_defer_begin/end: call order)
+  const DnnCopyGeom& g = geom_of(c);
+  void* const src = in ? plain : tensor_data;
+  void* const dst = in ? tensor_data : plain;
+  void* dsrc = src; void* ddst = dst;
+  if (0 == ((in ? kind_plain : kind_tensor) & 1)) {
+    dsrc = scratch(0, bytes);
+    if (nullptr == dsrc || 0 != h2d(dsrc, src, bytes)) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  else if (0 == ((in ? kind_tensor : kind_plain) & 1)) { // (every element is written: nothing travels to the device first)
+    ddst = scratch(0, bytes);
+    if (nullptr == ddst) return LIBXSMM_DNN_ERR_GENERAL;
+  }
+  const char* name = "dnn_copy";
+  const int e = launch_dnn_copy(g, in ? ddst : dsrc, in ? dsrc : ddst, in, stream, &name);
+  if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
+  if (ddst != dst && 0 != d2h(dst, ddst, bytes)) return LIBXSMM_DNN_ERR_GENERAL;
+  return (!wait || 0 == stream_sync()) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
+}
+
+// in: plain -> tensor; otherwise tensor -> plain. async: libxsmm_amd_dnn_copy{in,out}_tensor_async.
+libxsmm_dnn_err_t copy_tensor(const libxsmm_dnn_tensor* tensor, void* plain, libxsmm_dnn_tensor_format format, bool in, bool async)
 {
   if (nullptr == tensor || nullptr == tensor->layout) return LIBXSMM_DNN_ERR_INVALID_TENSOR;
   const libxsmm_dnn_tensor_datalayout& l = *tensor->layout;
-  const libxsmm_dnn_err_t bad_plain = in ? LIBXSMM_DNN_ERR_UNSUPPORTED_SRC_FORMAT : LIBXSMM_DNN_ERR_UNSUPPORTED_DST_FORMAT;
-  const libxsmm_dnn_err_t bad_tensor = in ? LIBXSMM_DNN_ERR_UNSUPPORTED_DST_FORMAT : LIBXSMM_DNN_ERR_UNSUPPORTED_SRC_FORMAT;
-  const bool act = is_activation(l.tensor_type), fil = is_filter(l.tensor_type);
-  if (!act && !fil) return LIBXSMM_DNN_ERR_INVALID_TENSOR; // (bias and statistics tensors belong to layers that are not provided)
-  if (format != (act ? LIBXSMM_DNN_TENSOR_FORMAT_NCHW : LIBXSMM_DNN_TENSOR_FORMAT_KCRS)) return bad_plain;
-  if (0 == (l.format & LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM)) return bad_tensor;
-  if (LIBXSMM_DNN_DATATYPE_F32 != l.datatype && LIBXSMM_DNN_DATATYPE_BF16 != l.datatype) return LIBXSMM_DNN_ERR_UNSUPPORTED_DATATYPE;
-  if (LIBXSMM_DNN_TENSOR_FORMAT_LIBXSMM_1 != l.custom_format) return LIBXSMM_DNN_ERR_NOT_IMPLEMENTED;
-  unsigned int d[7] = { 0, 0, 0, 0, 0, 0, 0 };
-  if (!(act ? activation_dims(l, d) : filter_dims(l, d))) return LIBXSMM_DNN_ERR_INVALID_LAYOUT;
+  CopyShape c;
+  const libxsmm_dnn_err_t status = copy_shape(l, format, in, &c);
+  if (LIBXSMM_DNN_SUCCESS != status) return status;
   if (nullptr == plain || nullptr == tensor->data) return LIBXSMM_DNN_ERR_INVALID_TENSOR;
-  libxsmm_dnn_err_t status = LIBXSMM_DNN_SUCCESS;
-  const size_t ts = libxsmm_dnn_typesize(l.datatype);
-  size_t bytes = ts;
+  size_t bytes = c.ts;
   for (unsigned int dim = 0; dim < l.num_dims; ++dim) bytes *= l.dim_size[dim];
   if (0 == bytes) return status;
+  const int kt = device_ready() ? pointer_kind(tensor->data) : 0, kp = device_ready() ? pointer_kind(plain) : 0;
+  if (async) { // both operands where the GPU reaches them, nothing staged, no wait
+    if (0 == (kt & 1) || 0 == (kp & 1)) return LIBXSMM_DNN_ERR_GENERAL;
+    return copy_on_device(c, tensor->data, kt, plain, kp, bytes, in, false);
+  }
+  if (1 == kt || 1 == kp) return copy_on_device(c, tensor->data, kt, plain, kp, bytes, in, true); // (plain device memory: the CPU cannot address it)
   HostView tv, pv;
   if (!tv.open(tensor->data, bytes, !in) || !pv.open(plain, bytes, in)) return LIBXSMM_DNN_ERR_GENERAL;
-  if (act) copy_activation(tv.ptr, pv.ptr, d, ts, in); else copy_filter(tv.ptr, pv.ptr, d, ts, in);
+  if (DNN_COPY_FLAT == c.form) { if (in) memcpy(tv.ptr, pv.ptr, bytes); else memcpy(pv.ptr, tv.ptr, bytes); }
+  else if (DNN_COPY_ACT == c.form) copy_activation(tv.ptr, pv.ptr, c.d, c.ts, in);
+  else copy_filter(tv.ptr, pv.ptr, c.d, c.ts, in);
   if (!(in ? tv.commit() : pv.commit())) return LIBXSMM_DNN_ERR_GENERAL;
   return status;
 }
@@ -331,12 +400,34 @@ libxsmm_dnn_err_t copy_tensor(const libxsmm_dnn_tensor* tensor, void* plain, lib
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_copyin_tensor(const libxsmm_dnn_tensor* tensor, const void* data, const libxsmm_dnn_tensor_format in_format)
 {
-  return copy_tensor(tensor, const_cast<void*>(data), in_format, true);
+  return copy_tensor(tensor, const_cast<void*>(data), in_format, true, false);
 }
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_copyout_tensor(const libxsmm_dnn_tensor* tensor, void* data, const libxsmm_dnn_tensor_format out_format)
 {
-  return copy_tensor(tensor, data, out_format, false);
+  return copy_tensor(tensor, data, out_format, false, false);
+}
+
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copyin_tensor_async(const libxsmm_dnn_tensor* tensor, const void* data, libxsmm_dnn_tensor_format in_format)
+{
+  return copy_tensor(tensor, const_cast<void*>(data), in_format, true, true);
+}
+
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copyout_tensor_async(const libxsmm_dnn_tensor* tensor, void* data, libxsmm_dnn_tensor_format out_format)
+{
+  return copy_tensor(tensor, data, out_format, false, true);
+}
+
+LIBXSMM_API libxsmm_dnn_err_t libxsmm_amd_dnn_copy_plan(const libxsmm_dnn_tensor_datalayout* layout, libxsmm_dnn_tensor_format plain_format, int in, long long plan[8])
+{
+  if (nullptr == layout || nullptr == plan) return LIBXSMM_DNN_ERR_INVALID_TENSOR;
+  CopyShape c;
+  const libxsmm_dnn_err_t status = copy_shape(*layout, plain_format, 0 != in, &c);
+  if (LIBXSMM_DNN_SUCCESS != status) return status;
+  const DnnCopyGeom& g = geom_of(c); // (what copy_on_device hands to the launcher)
+  plan[0] = g.form; plan[1] = g.ts; plan[2] = g.blocks; plan[3] = g.J; plan[4] = g.L; plan[5] = 0 != g.lds ? g.jn : 0;
+  plan[6] = g.items; plan[7] = g.grid;
+  return status;
 }
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_zero_tensor(const libxsmm_dnn_tensor* tensor)

@@ -6,6 +6,7 @@
 #include "xsmm_internal.hpp"
 #include "../../include/libxsmm_amd.h"
 #include "../../include/libxsmm_dnn.h"
+#include "kernels/dnn_copy_plan.h"
 
 #include <initializer_list>
 
@@ -118,6 +119,10 @@ struct RnnBwdWeightArgs {
 };
 int launch_rnn_bwd_weight(const RnnBwdWeightArgs& args, void* stream, const char** name);
 int launch_rnn_bwd_bias(const float* delta, float* db, int ld, int N, int T, void* stream, const char** name); // db[j] = +0.0 + delta in the same order
+
+// tensor copy-in / copy-out (xsmm_dnn.cpp, kernels/dnn_copy.hip): one launch moves the whole tensor between its blocked side and its
+// plain side (in: plain -> blocked), both memory the GPU reaches, aligned to their element; g comes from dnn_copy_geom
+int launch_dnn_copy(const DnnCopyGeom& g, void* blocked, void* plain, bool in, void* stream, const char** name); // returns hipError_t as int
 
 // ---- what the layers share on the host (xsmm_dnn_layer.cpp) ---------------------------------------------------------------
 // A layer provides slot_of(handle*, type) at global scope (the tensor pointer a type binds; nullptr for a type it does not
