@@ -2,7 +2,7 @@
 // highest byte address its A, B and C operands touch, reduced on the device over the call's index or pointer arrays.
 //
 // Batch calls recorded inside a libxsmm_amd_defer_begin/end bracket leave as fused launches whose groups run side by side
-// (xsmm_gemm.cpp: batch_flush_record), which is only right for calls that neither write the same C blocks nor read what
+// (xsmm_batch_record.cpp: batch_flush_record), which is only right for calls that neither write the same C blocks nor read what
 // another one writes. Where the arrays live in host memory the host forms the hulls while it stages them; arrays in device
 // memory are walked here -- 12 bytes per product, read once, coalesced (consecutive lanes take consecutive entries).
 #include "smm_common.cuh"

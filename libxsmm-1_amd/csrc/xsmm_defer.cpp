@@ -45,7 +45,7 @@ namespace xsmm {
 
 namespace {
 
-// WHAT IS OPEN ON THIS THREAD. Calls are recorded in three forms -- a burst (this file), a record of batch calls (xsmm_gemm.cpp),
+// WHAT IS OPEN ON THIS THREAD. Calls are recorded in three forms -- a burst (this file), a record of batch calls (xsmm_batch_record.cpp),
 // a record of spmdm block calls (xsmm_sparse.cpp) -- and everything recorded has to reach the stream in call order. So at most
 // one kind is open at a time: record_begin(kind) launches whatever else is open before kind opens, and whoever asks for the
 // stream (device()) launches what is open. record_flush() takes the kind off BEFORE it runs the kind's flush function: the

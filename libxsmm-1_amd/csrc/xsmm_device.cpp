@@ -273,7 +273,7 @@ void* index_upload(const void* src, size_t bytes) { return index_upload_on(devic
 void* index_upload_on(void* stream, const void* src, size_t bytes)
 {
   // An entry that was filled but not committed is waited for and taken over when the ring comes round to it: whoever holds
-  // commits back -- the record of batch calls inside a bracket (xsmm_gemm.cpp: MERGE_MAX_UPLOADS), until its flush has queued
+  // commits back -- the record of batch calls inside a bracket (xsmm_batch_record.cpp: MERGE_MAX_UPLOADS), until its flush has queued
   // the launches -- must keep its entries plus whatever is staged during that flush below INDEX_UPLOAD_RING (run_groups
   // stages nothing today: its tables travel as kernel arguments).
   IndexStage& e = tl_index_ring[tl_index_next++ % INDEX_RING];

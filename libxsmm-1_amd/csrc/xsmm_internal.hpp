@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <functional>
 #include <string>
+#include <vector>
 
 #include "../../include/libxsmm.h"
 
@@ -82,11 +83,56 @@ constexpr int FLAG_SLOT_BLOCKS = 512; // work-groups of the C ordering check (ea
 int launch_c_order_check(const SmmBatch& args, int* d_out, void* stream);
 int launch_defer_gate(unsigned long long* word, unsigned long long* count_out, void* stream); // see xsmm_defer.cpp
 int launch_smm_generic(const SmmBatch& s, void* stream, const char** name);
+int launch_smm_special(const SmmBatch& s, void* stream, const char** name); // returns -1 if no specialised variant applies
+
+// ---- the batch front end: launch chain, resolver and staging (xsmm_batch.cpp), recorders (xsmm_batch_record.cpp), thunks (xsmm_call.cpp)
+// Where the operands of a call live: pointer_kind of each, asked in turn and only while all before it are GPU-reachable (what
+// the first one that is not says about the others does not matter to any caller). One driver query per operand per call.
+struct Kernel;
+struct Residency {
+  int a, b, c;
+  bool device() const { return 0 != (a & b & c & 1); }            // the GPU reaches all three
+  int visible() const { return 0 != ((a | b | c) & 2) ? 1 : 0; }  // the CPU addresses one of them as well: the call waits at its end
+};
+Residency classify(const void* a, const void* b, const void* c);
+// host_visible: -1 = look at the operands (a driver query each), 0 = the caller knows they are plain device memory, 1 = some
+// operand is memory the CPU addresses as well (the call waits for the stream)
+int run_smm(const SmmBatch& s, int host_visible = -1);
+int run_groups(std::vector<SmmBatch>& groups);
+void launch_failed(const char* name, int hip_error);      // the one message of a launch that failed
+size_t span_a(const SmmBatch& s);                         // elements touched by one A operand (span_b, span_c: B, C)
+size_t span_b(const SmmBatch& s);
+size_t span_c(const SmmBatch& s);
+const int* device_indexes(const int* idx, int index_stride, long long n, bool* ok); // an index array as the GPU reads it (uploaded if need be)
+// Pointer arrays through the pinned ring, on `stream` (device().stream; a recorder passes the stream as it is: asking for it would
+// launch the record): s.a, s.b, s.c become the uploaded copies, the steps those of tight arrays. false: an upload failed (the
+// caller's commit releases the entries).
+bool upload_pointer_arrays(SmmBatch& s, void* stream, const void* a, size_t na, const void* b, size_t nb, const void* c, size_t nc);
+// Host spans into the thread's scratch slots 3, 4, 5 (a NULL span is left out); dev receives the device copies. false: failed.
+bool stage_in(const void* const host[3], const size_t bytes[3], char* dev[3]);
+int stage_out(void* host_c, const void* dev_c, size_t bytes); // C back where it came from (waits for the stream); 0: done
+int batch_execute(SmmBatch s, libxsmm_blasint index_base, libxsmm_blasint index_stride,
+  const libxsmm_blasint* stride_a, const libxsmm_blasint* stride_b, const libxsmm_blasint* stride_c,
+  const void* a, const void* b, void* c, long long begin, long long end, bool nosync);
+int lowp_batch_execute(const Kernel* k, libxsmm_blasint index_base, libxsmm_blasint index_stride,
+  const libxsmm_blasint* stride_a, const libxsmm_blasint* stride_b, const libxsmm_blasint* stride_c,
+  const void* a, const void* b, void* c, long long begin, long long end);
+int batch_order_env();                                    // LIBXSMM_AMD_BATCH_ORDER: 1 relaxed, -1 strict, 0 not set
+extern thread_local int tl_relaxed_order;                 // > 0: inside an entry point whose reference path is multi-threaded
+bool relaxed_order(int ntasks, libxsmm_blasint index_stride, const void* c);
+SmmBatch from_descriptor(const libxsmm_gemm_descriptor& d);
+SmmBatch lowp_from_descriptor(const libxsmm_gemm_descriptor& d, float scf);
+int lowp_launch(const SmmBatch& s);
+int single_execute(SmmBatch s, const void* a, const void* b, void* c); // one operand triple, wherever it lives
+bool try_record(const libxsmm_gemm_descriptor& d, const void* a, const void* b, void* c); // auto-batch: true if the call was recorded
+bool record_batch_call(const Kernel* k, libxsmm_blasint index_base, libxsmm_blasint index_stride,
+  const libxsmm_blasint* stride_a, const libxsmm_blasint* stride_b, const libxsmm_blasint* stride_c,
+  const void* a, const void* b, void* c, libxsmm_blasint batchsize, int ntasks);
 // ---- calls recorded for later inside the opt-in bracket (xsmm_defer.cpp) --------------------------------------------------
 // What is open on the calling thread: at most one kind, kept by xsmm_defer.cpp alone.
 enum OpenKind : int { OPEN_NONE = 0,
   OPEN_BURST,   // per-call kernels or per-panel operator calls behind a gate on the stream (xsmm_defer.cpp)
-  OPEN_BATCH,   // recorded libxsmm_gemm_batch calls (xsmm_gemm.cpp)
+  OPEN_BATCH,   // recorded libxsmm_gemm_batch calls (xsmm_batch_record.cpp)
   OPEN_SPMDM }; // recorded spmdm block calls (xsmm_sparse.cpp)
 OpenKind record_open();
 void record_begin(OpenKind kind);         // launches whatever other kind is open, then kind is open (nothing to do if it is already)

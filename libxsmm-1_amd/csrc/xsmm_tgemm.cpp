@@ -168,7 +168,7 @@ bool tgemm_route(int typesize, int flags, int m, int n, int k, int lda, int ldb,
 {
   static const bool enabled = []() { const char* const e = getenv("LIBXSMM_AMD_TGEMM"); return nullptr != e && 0 != atoi(e); }();
   if (!enabled || 1.0 != alpha || (0.0 != beta && 1.0 != beta)) return false;
-  // large: where a single product leaves the SMM kernels today (xsmm_gemm.cpp: single_execute)
+  // large: where a single product leaves the SMM kernels today (xsmm_call.cpp: single_execute)
   if (!(2.0 * m * n * k >= 2.0 * 256 * 256 * 256 && m >= 64 && n >= 64 && k >= 32)) return false;
   const bool ta = (0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_A)), tb = (0 != (flags & LIBXSMM_GEMM_FLAG_TRANS_B));
   if (lda < (ta ? k : m) || ldb < (tb ? n : k) || ldc < m) return false;

@@ -1,6 +1,6 @@
 """The launch chains of dense batches, as the tests of the alternatives assume them.
 
-A batch call walks a chain (csrc/xsmm_gemm.cpp:run_smm): the alternatives of the matrix-core tier of its plan, the hand-written
+A batch call walks a chain (csrc/xsmm_batch.cpp:run_smm): the alternatives of the matrix-core tier of its plan, the hand-written
 kernels (kernels/smm_special.hip), the alternatives of the specialised tier, the generic kernel; 16-bit inputs: the alternatives of
 their plan, then the pre-compiled kernel (kernels/smm_lowp.hip). The first link that is ready serves, "with the same bits". CASES
 names batches and, for each, the whole chain: per link which kernel libxsmm_amd_last_kernel names and how many generated kernels

@@ -3,8 +3,8 @@ The rule that cuts them is a pure function, libxsmm_amd_merge_segments, and is c
 address hulls, and against a restatement of the rule in Python on random tables.
 
 hulls: per call (a_lo, a_hi, b_lo, b_hi, c_lo, c_hi), half-open byte ranges. A call joins the open segment unless its C meets the
-A, B or C of a member, or its A or B meets the C of a member (the rule of the grouped pointer batches, csrc/xsmm_gemm.cpp:
-try_grouped_pointer_batches); otherwise it opens a new segment.
+A, B or C of a member, or its A or B meets the C of a member (the rule of the grouped pointer batches as well,
+csrc/xsmm_batch.hpp: merge_segments, used by csrc/xsmm_gemm.cpp: try_grouped_pointer_batches); otherwise it opens a new segment.
 """
 import ctypes as C
 import os
@@ -102,6 +102,37 @@ def test_random_tables_against_the_restated_rule(xs):
         assert want[1] == sorted(want[1]) and want[1][0] == 0 and want[1][-1] == want[0] - 1
         cuts += want[0] - 1
     assert cuts > 400  # (the tables do exercise the rule)
+
+
+def no_pair_meets(hulls):
+    """the rule the grouped pointer batches used to state on their own: the groups may be fused if no group's C meets another
+    group's A or B, or the C of a later group"""
+    meet = lambda x, y: x[0] < y[1] and y[0] < x[1]
+    a = lambda h: (h[0], h[1]); b = lambda h: (h[2], h[3]); c = lambda h: (h[4], h[5])
+    for x, hx in enumerate(hulls):
+        for y, hy in enumerate(hulls):
+            if x != y and (meet(c(hx), a(hy)) or meet(c(hx), b(hy)) or (x < y and meet(c(hx), c(hy)))):
+                return False
+    return True
+
+
+def test_one_segment_says_no_pair_meets(xs):
+    """the groups of ?gemm_batch are fused on "one segment"; that must be the old "no pair of groups meets", on every table"""
+    rng = np.random.default_rng(7051)
+    fused = split = 0
+    for trial in range(600):
+        n = int(rng.integers(2, 9))
+        space = int(rng.choice([600, 3000, 40000]))  # most tables conflict ... hardly any does
+        hulls = []
+        for _ in range(n):
+            ranges = []
+            for _ in range(3):
+                lo = int(rng.integers(0, space)); ranges.append((lo, lo + int(rng.integers(1, 120))))
+            hulls.append(call(*ranges))
+        want = no_pair_meets(hulls)
+        assert (1 == xs.merge_segments(hulls)[0]) == want, (trial, hulls)
+        fused += want; split += not want
+    assert fused > 100 and split > 100  # (both answers are exercised)
 
 
 def test_a_plan_without_a_flush_is_empty(xs):

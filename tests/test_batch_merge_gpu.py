@@ -1,6 +1,6 @@
 """Batch calls inside a libxsmm_amd_defer_begin/end bracket (GPU): a caller's loop of libxsmm_gemm_batch calls, one per shape
 (samples/cp2k/cp2k.cpp:328-360), is recorded and leaves as fused launches -- segments of calls that are independent of each
-other, in call order (include/libxsmm_amd.h; csrc/xsmm_gemm.cpp: record_batch_call / batch_flush_record; the address hulls of
+other, in call order (include/libxsmm_amd.h; csrc/xsmm_batch_record.cpp: record_batch_call / batch_flush_record; the address hulls of
 calls whose arrays live in device memory: csrc/kernels/batch_hull.hip).
 
 Every case issues the same sequence of calls twice, on fresh copies of the operands: outside the bracket (a launch per call, as
