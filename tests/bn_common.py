@@ -3,6 +3,7 @@ over logical threads, seeded inputs, and the arithmetic contract of include/libx
 fuse combinations, fp32 and bf16) as plain array code. Shared by tests/test_bn_cpu.py, tests/test_bn_gpu.py and
 tools/golden/bn_capture.py; the reference's own answers are in tests/golden/bn.npz and tests/test_bn_cpu.py holds this file
 against them bit for bit."""
+import functools
 import os
 import zlib
 
@@ -202,22 +203,50 @@ def _by_block(h, a):
     return np.tile(a, (h.d["N"], 1))[:, None, None, :]
 
 
-def forward(h, t, fused=False):
+WRONG = ("statistics over the strided pixels", "nhw as the strided count", "block off by one under the wrap", "add at output coordinates",
+         "relu in bwd by dout")  # what forward / backward (wrong=...) can get wrong on purpose
+
+
+def touched_blocks(h, ltid, wrong=None):
+    """the channel blocks of the items of logical thread ltid's share: the share computes the statistics of these, over all images.
+    wrong: as the engine derives them (a run from b0 % blocks on that may wrap, or all blocks once the share is as long as an
+    image), with the block after the wrap off by one"""
+    b0, b1 = h.share(ltid)
+    blocks = h.blocksifm
+    if wrong != "block off by one under the wrap":
+        return sorted({item % blocks for item in range(b0, b1)})
+    if b1 - b0 >= blocks:
+        return list(range(blocks))
+    return [fm if fm < blocks else (fm + 1) % blocks for fm in (b0 % blocks + j for j in range(b1 - b0))]
+
+
+def _share(h, ltid, wrong):
+    """(the items [b0, b1) a pass applies to, the channel blocks whose statistics it computes); ltid None: everything"""
+    if ltid is None:
+        return (0, h.work()), list(range(h.blocksifm))
+    return h.share(ltid), touched_blocks(h, ltid, wrong)
+
+
+def forward(h, t, fused=False, ltid=None, wrong=None):
     """FWD on the dict of tensors t, in place: the interior of out is written and, with OPS_BN, mean, rstd and var.
     fused=True: sumsq += x * x and ... * rstd + beta as one rounding each (the form the reference's build does not have; for the
-    test that tells them apart)."""
+    test that tells them apart). ltid: the share of that logical thread only -- out of its items, and the statistics of the
+    channel blocks those items belong to (over all images; the bits are those of one thread). wrong: one of WRONG, a mistake made
+    on purpose (for tests/test_bn_sweep_cpu.py, which shows that its float64 comparison rejects each of them)."""
     d = h.d
     ops = d["fuse_ops"]
     iph, ipw, oph, opw, H, W = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"], d["H"], d["W"]
     xin = as_f32(h, t["x"])[:, iph:iph + H, ipw:ipw + W, :]
     nhw, recp = _nhw(d)
+    (b0, b1), blocks = _share(h, ltid, wrong)
     with np.errstate(all="ignore"):
-        if ops & OPS_BN:
+        if ops & OPS_BN and blocks:
+            over = xin[:, ::d["u"], ::d["v"], :] if wrong == "statistics over the strided pixels" else xin
             s = np.zeros((h.work(), 16), dtype=np.float32)
             sq = np.zeros((h.work(), 16), dtype=np.float32)
-            for hi in range(H):           # every pixel, hi ascending, then wi ascending
-                for wi in range(W):
-                    v = xin[:, hi, wi, :]
+            for hi in range(over.shape[1]):           # every pixel, hi ascending, then wi ascending
+                for wi in range(over.shape[2]):
+                    v = over[:, hi, wi, :]
                     s = s + v
                     sq = fma(v, v, sq) if fused else sq + v * v
             s, sq = s.reshape(d["N"], h.blocksifm, 16), sq.reshape(d["N"], h.blocksifm, 16)
@@ -229,36 +258,48 @@ def forward(h, t, fused=False):
             mean = recp * ts
             var = recp * tq - mean * mean
             rstd = (1.0 / np.sqrt(var.astype(np.float64) + np.float64(np.float32(1e-7)))).astype(np.float32)
-            t["mean"][...], t["rstd"][...], t["var"][...] = mean, rstd, var
+            t["mean"][blocks], t["rstd"][blocks], t["var"][blocks] = mean[blocks], rstd[blocks], var[blocks]
         xs = xin[:, ::d["u"], ::d["v"], :]
         gamma, beta, mean, rstd = (_by_block(h, t[k]) for k in ("gamma", "beta", "mean", "rstd"))
         part = gamma * (xs - mean)
         o = fma(part, rstd, beta) if fused else part * rstd + beta
         if ops & OPS_ELTWISE:
-            o = o + as_f32(h, t["add"])[:, iph:iph + H:d["u"], ipw:ipw + W:d["v"], :]
+            if wrong == "add at output coordinates":
+                o = o + as_f32(h, t["add"])[:, iph:iph + h.ofh, ipw:ipw + h.ofw, :]
+            else:
+                o = o + as_f32(h, t["add"])[:, iph:iph + H:d["u"], ipw:ipw + W:d["v"], :]
         if ops & OPS_RELU:
             o = np.where(o < np.float32(0.0), np.float32(0.0), o)
-    t["out"][:, oph:oph + h.ofh, opw:opw + h.ofw, :] = stored(h, o)
+    t["out"][b0:b1, oph:oph + h.ofh, opw:opw + h.ofw, :] = stored(h, o)[b0:b1]
 
 
-def backward(h, t):
+def backward(h, t, ltid=None, wrong=None):
     """BWD on the dict of tensors t, in place: the strided pixels of din and, with OPS_BN, dgamma, dbeta, the RELU select
-    stored back into dout and the strided pixels of dadd"""
+    stored back into dout and the strided pixels of dadd. ltid: the share of that logical thread only -- din of its items; dgamma
+    and dbeta of the channel blocks those items belong to, and the select and dadd of those blocks' items in all images. wrong:
+    as in forward."""
     d = h.d
     ops = d["fuse_ops"]
     iph, ipw, oph, opw, H, W, u, v = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"], d["H"], d["W"], d["u"], d["v"]
     xs = as_f32(h, t["x"])[:, iph:iph + H:u, ipw:ipw + W:v, :]
     nhw, recp = _nhw(d)
+    if wrong == "nhw as the strided count":
+        nhw = np.float32(d["N"] * h.ofh * h.ofw)
+        recp = np.float32(1.0) / nhw
+    (b0, b1), blocks = _share(h, ltid, wrong)
     gamma, mean, rstd = (_by_block(h, t[k]) for k in ("gamma", "mean", "rstd"))
     inner = (slice(None), slice(oph, oph + h.ofh), slice(opw, opw + h.ofw), slice(None))
     strided = (slice(None), slice(iph, iph + H, u), slice(ipw, ipw + W, v), slice(None))
     with np.errstate(all="ignore"):
-        if ops & OPS_BN:
+        if ops & OPS_BN and blocks:
+            mine = np.isin(np.arange(h.work()) % h.blocksifm, blocks)[:, None, None, None]  # the items of the touched blocks
             if ops & OPS_RELU:   # (a -0.0 output counts as zero; the element's bits are kept otherwise)
                 zero = as_f32(h, t["out"])[inner] == np.float32(0.0)
-                t["dout"][inner] = np.where(zero, np.zeros((), dtype=t["dout"].dtype), t["dout"][inner])
+                if wrong == "relu in bwd by dout":
+                    zero = as_f32(h, t["dout"])[inner] <= np.float32(0.0)
+                t["dout"][inner] = np.where(zero & mine, np.zeros((), dtype=t["dout"].dtype), t["dout"][inner])
             if ops & OPS_ELTWISE:
-                t["dadd"][strided] = t["dout"][inner]
+                t["dadd"][strided] = np.where(mine, t["dout"][inner], t["dadd"][strided])
             g = as_f32(h, t["dout"])[inner]
             dg = np.zeros((h.work(), 16), dtype=np.float32)
             db = np.zeros((h.work(), 16), dtype=np.float32)
@@ -273,11 +314,11 @@ def backward(h, t):
             for img in range(d["N"]):
                 tg = tg + dg[img]
                 tb = tb + db[img]
-            t["dgamma"][...], t["dbeta"][...] = tg, tb
+            t["dgamma"][blocks], t["dbeta"][blocks] = tg[blocks], tb[blocks]
         g = as_f32(h, t["dout"])[inner]
         dgamma, dbeta = _by_block(h, t["dgamma"]), _by_block(h, t["dbeta"])
         din = gamma * rstd * recp * (nhw * g - (dbeta + (xs - mean) * dgamma * rstd))
-    t["din"][strided] = stored(h, din)
+    t["din"][strided][b0:b1] = stored(h, din)[b0:b1]
 
 
 def filled(shape, dtype):
@@ -320,3 +361,217 @@ def written(d, kind):
 
 def load_golden():
     return np.load(os.path.join(GOLDEN, "bn.npz"))
+
+
+# ---- the seeded sweep: descriptors nobody picked --------------------------------------------------------------------------------
+SWEEP_SEED, SWEEP_CASES = 11, 40
+SWEEP_CHANNELS = (16, 24, 32, 48, 64, 80)
+RELU_NEAR_ZERO = 0.01  # the share of a case's outputs that the float64 comparison may leave out because the ReLU's argument is within its bound of 0
+U24, BF16_CUT = 2.0 ** -24, 2.0 ** -7  # the unit roundoff of fp32; what a truncation to bf16 takes off at most, relative
+
+
+def _draw(rng):
+    pick = lambda lo, hi: int(rng.integers(lo, hi + 1))  # noqa: E731
+    u, v = pick(1, 3), pick(1, 3)
+    H, W = (u * pick(10, 14), v * pick(10, 14)) if pick(0, 7) == 0 else (u * pick(1, 6), v * pick(1, 6))
+    pin, pout = (pick(0, 2), pick(0, 2)), (pick(0, 2), pick(0, 2))
+    return desc(H, W, N=pick(1, 5), C=SWEEP_CHANNELS[pick(0, 5)], u=u, v=v, pin=pin, pout=pout, ops=FUSE_COMBINATIONS[pick(0, 7)],
+                dt=(F32, BF16)[pick(0, 1)], threads=pick(1, 5))
+
+
+def sweep_start(name, d):
+    """the tensors of a case before the passes: seeded inputs, destinations of ones bits"""
+    h = Handle(d)
+    t = inputs(name, d)
+    seeded = tuple(t)
+    for key in KEYS:
+        if key not in t:
+            t[key] = filled(h.shape(key), elem_dtype(h) if key in ("out", "din", "dadd") else np.float32)
+    t["dout_in"] = t["dout"].copy()
+    t["seeded"] = seeded
+    return t
+
+
+def sweep_cases_from(seed):
+    rng = np.random.default_rng(seed)
+    out = {}
+    while len(out) < SWEEP_CASES:
+        d = _draw(rng)
+        h = Handle(d)
+        if h.status != SUCCESS or SUCCESS != h.execute_status(FWD, BINDABLE) or SUCCESS != h.execute_status(BWD, BINDABLE):
+            continue
+        name = "sweep_%02d" % len(out)
+        want = contract64(h, sweep_start(name, d))
+        if not all(np.all(np.isfinite(bound)) for _, bound, _ in want.values()) or np.mean(~want["out"][2]) >= RELU_NEAR_ZERO:
+            continue
+        out[name] = d
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases():
+    """name -> desc: SWEEP_CASES descriptors drawn from SWEEP_SEED. A draw that create or execute_status refuses is left out; one
+    whose ReLU leaves RELU_NEAR_ZERO or more of the outputs uncompared, or whose derived bound is not finite (a variance that its own
+    bound cannot tell from -epsilon), is replaced by the next draw. tests/test_bn_sweep_cpu.py counts what the set holds; the seed is
+    the first from 0 up that passes that census."""
+    return sweep_cases_from(SWEEP_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_expected(name):
+    """all thirteen tensors of a sweep case after FWD and BWD, each pass as the shares of its logical threads in reverse order, with
+    dout_in and seeded as expected() has them (computed once, shared: read only)"""
+    d = sweep_cases()[name]
+    h = Handle(d)
+    t = sweep_start(name, d)
+    for ltid in reversed(range(d["threads"])):
+        forward(h, t, ltid=ltid)
+    for ltid in reversed(range(d["threads"])):
+        backward(h, t, ltid=ltid)
+    for a in t.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return t
+
+
+def gamma_n(n):
+    """n roundings of relative size 2^-24 each, compounded: (1 + 2^-24)^n - 1 <= n * 2^-24 / (1 - n * 2^-24)"""
+    n = np.asarray(n, dtype=np.float64)
+    return n * U24 / (1 - n * U24)
+
+
+# An fp32 operation on operands known to within ea and eb: the exact operation moves by what the operands are off, and the rounding of
+# the computed result, which lies within that of the exact one, adds 2^-24 of its magnitude. Nothing here is first order only.
+def _rounded(v, e):
+    return e + U24 * (np.abs(v) + e)
+
+
+def _add64(a, ea, b, eb):
+    return a + b, _rounded(a + b, ea + eb)
+
+
+def _sub64(a, ea, b, eb):
+    return a - b, _rounded(a - b, ea + eb)
+
+
+def _mul64(a, ea, b, eb):
+    return a * b, _rounded(a * b, np.abs(a) * eb + np.abs(b) * ea + ea * eb)
+
+
+def _sum64(v, e, axes, roundings):
+    """an fp32 sum of terms known to within e, none of which passes through more than `roundings` rounded additions"""
+    return v.sum(axis=axes), e.sum(axis=axes) + gamma_n(roundings) * (np.abs(v).sum(axis=axes) + e.sum(axis=axes))
+
+
+def contract64(h, t):
+    """key -> (value, bound, compared) for every tensor the two passes write: the layer's contract (include/
+    libxsmm_dnn_fusedbatchnorm.h) in float64, written from that text and not from forward / backward above. out,
+    dout: interior; din, dadd: the strided pixels; all as [item][ofh][ofw][16]; the channel tensors as [block][16].
+
+    What differs from a textbook batch-norm and is part of the contract:
+      * the statistics run over ALL N * H * W pixels, even with a stride; out, din, dadd, dgamma and dbeta cover the strided pixels;
+      * din is scaled with the full nhw = N * H * W, not with the number of strided pixels;
+      * var = sumsq / nhw - mean^2 (biased), rstd = 1 / sqrt(var + (double)1e-7f);
+      * ReLU in BWD is decided by out == 0 (here: by the float64 argument being <= 0), and the selected dout is stored back;
+      * with BNSCALE mean, rstd, dgamma and dbeta are given: BWD writes din alone, from dout as it is (no select, no dadd);
+      * of C = 24 only the first block of 16 channels exists.
+
+    Bounds: every fp32 operation is followed through as (value, error) by the rules above (_add64, _sub64, _mul64, _sum64), in the
+    order kernels/bn.hip documents. sum and sumsq: chains of H * W terms per image from +0.0, then N images from +0.0, so a term
+    meets at most H * W + N - 2 roundings (0 + v is exact). mean = fl(recp * sum) with recp = fl(1 / nhw) (nhw < 2^24 is exact).
+    var = fl(fl(recp * sumsq) - fl(mean * mean)): the error of either product enters whole, which is the cancellation. rstd: the
+    interval var +- e_var is carried through 1 / sqrt(. + eps), plus the final rounding to fp32 (the double arithmetic's 2^-52
+    is added as 2^-50). Apply: ((gamma * (x - mean)) * rstd) + beta (+ add). dgamma, dbeta: sums of ((x - mean) * dout) * rstd and
+    dout over ofh * ofw + N - 2 roundings. din: ((gamma * rstd) * recp) * (nhw * dout - (dbeta + ((x - mean) * dgamma) * rstd)).
+    A bf16 store cuts off below 2^-7 * (|value| + bound), added last.
+    compared: False where the float64 ReLU argument lies within its bound of 0, so that the two sides may fall on either side of
+    it: in out, and with OPS_BN in dout, dadd and din of the same element; its whole term |dout| and |((x - mean) * dout) * rstd|
+    joins the bound of its channel's dbeta and dgamma, and through them that of din."""
+    d = h.d
+    ops, N, blocks, H, W, u, v = d["fuse_ops"], d["N"], h.blocksifm, d["H"], d["W"], d["u"], d["v"]
+    iph, ipw, oph, opw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
+    stats, relu, elt = bool(ops & OPS_BN), bool(ops & OPS_RELU), bool(ops & OPS_ELTWISE)
+    f64 = lambda a: as_f32(h, a).astype(np.float64)  # noqa: E731
+    per_chan = lambda a: a.reshape((N, blocks) + a.shape[1:])  # noqa: E731 ([image][block][row][column][16])
+    by_item = lambda a: np.tile(a, (N, 1))[:, None, None, :]  # noqa: E731
+    x_all = f64(t["x"])[:, iph:iph + H, ipw:ipw + W, :]
+    xs = x_all[:, ::u, ::v, :]
+    nhw = float(N * H * W)
+    recp, e_recp = 1.0 / nhw, U24 / nhw
+    res = {}
+    if stats:
+        X = per_chan(x_all)
+        total, e_total = _sum64(X, np.zeros_like(X), (0, 2, 3), max(H * W + N - 2, 0))
+        mean, e_mean = _mul64(recp, e_recp, total, e_total)
+        sq, e_sq = _mul64(X, 0.0, X, 0.0)
+        sumsq, e_sumsq = _sum64(sq, e_sq, (0, 2, 3), max(H * W + N - 2, 0))
+        first, e_first = _mul64(recp, e_recp, sumsq, e_sumsq)
+        second, e_second = _mul64(mean, e_mean, mean, e_mean)
+        var, e_var = _sub64(first, e_first, second, e_second)
+        eps = float(np.float32(1e-7))
+        rstd = 1.0 / np.sqrt(var + eps)
+        with np.errstate(all="ignore"):
+            low = var - e_var + eps
+            e_rstd = np.where(low > 0, np.maximum(1.0 / np.sqrt(np.where(low > 0, low, 1.0)) - rstd, rstd - 1.0 / np.sqrt(var + e_var + eps)), np.inf)
+        e_rstd = _rounded(rstd, e_rstd + 2.0 ** -50 * rstd)
+        yes = np.ones(mean.shape, dtype=bool)
+        res["mean"], res["var"], res["rstd"] = (mean, e_mean, yes), (var, e_var, yes), (rstd, e_rstd, yes)
+    else:
+        mean, rstd = t["mean"].astype(np.float64), t["rstd"].astype(np.float64)
+        e_mean, e_rstd = np.zeros_like(mean), np.zeros_like(rstd)
+    gam, beta = t["gamma"].astype(np.float64), t["beta"].astype(np.float64)
+    cut = (lambda a, e: e) if h.f32 else (lambda a, e: e + BF16_CUT * (np.abs(a) + e))
+    # FWD apply
+    centred, e_centred = _sub64(xs, 0.0, by_item(mean), by_item(e_mean))
+    o, e = _mul64(by_item(gam), 0.0, centred, e_centred)
+    o, e = _mul64(o, e, by_item(rstd), by_item(e_rstd))
+    o, e = _add64(o, e, by_item(beta), 0.0)
+    if elt:
+        o, e = _add64(o, e, f64(t["add"])[:, iph:iph + H:u, ipw:ipw + W:v, :], 0.0)
+    compared = np.abs(o) > e if relu else np.ones(o.shape, dtype=bool)
+    positive = o > 0
+    if relu:
+        o = np.maximum(o, 0.0)
+    res["out"] = (o, cut(o, e), compared)
+    # BWD
+    raw = f64(t["dout"])[:, oph:oph + h.ofh, opw:opw + h.ofw, :]
+    g, settled = raw, np.ones(raw.shape, dtype=bool)
+    if stats:
+        if relu:
+            g, settled = np.where(positive, raw, 0.0), compared
+            res["dout"] = (g, np.zeros_like(g), settled)
+        if elt:
+            res["dadd"] = (g, np.zeros_like(g), settled)
+        term, e_term = _mul64(centred, e_centred, raw, 0.0)
+        term, e_term = _mul64(term, e_term, by_item(rstd), by_item(e_rstd))
+        kept = positive if relu else np.ones(raw.shape, dtype=bool)
+        roundings = max(h.ofh * h.ofw + N - 2, 0)
+        dgamma, e_dgamma = _sum64(per_chan(np.where(kept, term, 0.0)), per_chan(np.where(kept, e_term, 0.0)), (0, 2, 3), roundings)
+        dbeta, e_dbeta = _sum64(per_chan(g), np.zeros_like(per_chan(g)), (0, 2, 3), roundings)
+        e_dgamma = e_dgamma + per_chan(np.where(settled, 0.0, np.abs(term) + e_term)).sum(axis=(0, 2, 3))
+        e_dbeta = e_dbeta + per_chan(np.where(settled, 0.0, np.abs(raw))).sum(axis=(0, 2, 3))
+        yes = np.ones(dgamma.shape, dtype=bool)
+        res["dgamma"], res["dbeta"] = (dgamma, e_dgamma, yes), (dbeta, e_dbeta, yes)
+    else:
+        dgamma, dbeta = t["dgamma"].astype(np.float64), t["dbeta"].astype(np.float64)
+        e_dgamma, e_dbeta = np.zeros_like(dgamma), np.zeros_like(dbeta)
+    scale, e_scale = _mul64(by_item(gam), 0.0, by_item(rstd), by_item(e_rstd))
+    scale, e_scale = _mul64(scale, e_scale, recp, e_recp)
+    lead, e_lead = _mul64(nhw, 0.0, g, 0.0)
+    part, e_part = _mul64(centred, e_centred, by_item(dgamma), by_item(e_dgamma))
+    part, e_part = _mul64(part, e_part, by_item(rstd), by_item(e_rstd))
+    part, e_part = _add64(by_item(dbeta), by_item(e_dbeta), part, e_part)
+    inner, e_inner = _sub64(lead, e_lead, part, e_part)
+    din, e_din = _mul64(scale, e_scale, inner, e_inner)
+    res["din"] = (din, cut(din, e_din), settled)
+    return res
+
+
+def interior(h, key, a):
+    """the elements of a tensor of sweep_expected() that contract64 computes, in its index order"""
+    d = h.d
+    if key in ("out", "dout"):
+        return as_f32(h, a)[:, d["pad_h_out"]:d["pad_h_out"] + h.ofh, d["pad_w_out"]:d["pad_w_out"] + h.ofw, :]
+    if key in ("din", "dadd"):
+        return as_f32(h, a)[:, d["pad_h_in"]:d["pad_h_in"] + d["H"]:d["u"], d["pad_w_in"]:d["pad_w_in"] + d["W"]:d["v"], :]
+    return a

@@ -2,6 +2,7 @@
 over logical threads, and the expected outputs, which come from the CPU oracle (one orc.smm per pass over the whole reduction
 length, fma, beta = 0, on the de-blocked plain matrices). Shared by tests/test_fc_cpu.py, tests/test_fc_gpu.py and
 tools/golden/fc_capture.py; the reference's own answers are in tests/golden/fc.npz."""
+import functools
 import os
 
 import numpy as np
@@ -52,8 +53,13 @@ def all_cases():
 
 
 # ---- handle rules (src/libxsmm_dnn_fullyconnected.c:46-136) ---------------------------------------------------------------------
+WRONG = ("block factors swapped", "non-dividing block kept")  # what Handle(wrong=...) can get wrong on purpose
+
+
 class Handle:
-    def __init__(self, d):
+    def __init__(self, d, wrong=None):
+        """wrong: one of WRONG, a mistake made on purpose (for tests/test_fc_sweep_cpu.py, which shows that its float64 comparison
+        rejects each of them)"""
         self.d = d
         self.status = SUCCESS
         self.ok = False
@@ -69,11 +75,14 @@ class Handle:
         self.ifmblock = self.ofmblock = self.fm_lp_block = self.blocksifm = self.blocksofm = 0
         if self.packed:
             self.bn, self.bc, self.bk = d["bn"], d["bc"], d["bk"]
-            if N % self.bn:
+            if wrong == "block factors swapped":
+                self.bc, self.bk = self.bk, self.bc
+            # (a block of zero or below divides nothing: the reference would trap on the modulo, this engine falls back as for any misfit)
+            if (self.bn <= 0 or N % self.bn) and wrong != "non-dividing block kept":
                 self.bn, self.status = N, WARN_N
-            if C % self.bc:
+            if (self.bc <= 0 or C % self.bc) and wrong != "non-dividing block kept":
                 self.bc, self.status = C, WARN_C
-            if K % self.bk:
+            if (self.bk <= 0 or K % self.bk) and wrong != "non-dividing block kept":
                 self.bk, self.status = K, WARN_K
         else:
             if C % 16 == 0 and K % 16 == 0:
@@ -259,3 +268,70 @@ def dtype_of(h, t):
 
 def load_golden():
     return np.load(os.path.join(GOLDEN, "fc.npz"))
+
+
+# ---- the seeded sweep: descriptors nobody picked --------------------------------------------------------------------------------
+SWEEP_SEED, SWEEP_CASES = 10, 32
+SWEEP_C, SWEEP_K = (16, 32, 48, 64), (16, 32, 48, 80, 1000)
+U24, BF16_RNE = 2.0 ** -24, 2.0 ** -8  # the unit roundoff of fp32; that of a round-to-nearest-even store to bf16 (8 significant bits: half of a spacing of 2^-7)
+
+
+def _draw(rng, packed):
+    pick = lambda lo, hi: int(rng.integers(lo, hi + 1))  # noqa: E731
+    N = pick(65, 150) if pick(0, 5) == 0 else pick(1, 40)
+    if packed:
+        C, K = pick(1, 80), pick(1, 80)
+        blk = lambda n: int(rng.choice([0, 1, n] + [q for q in range(2, n + 1) if n % q == 0] + [n + 1, 7]))  # noqa: E731 (as rnn_common.sweep_cases)
+        return desc(N, C, K, "B", bn=blk(N), bc=blk(C), bk=blk(K), threads=pick(1, 5))
+    return desc(N, SWEEP_C[pick(0, 3)], SWEEP_K[pick(0, 4)], "L", dt=("f32", "bf16")[pick(0, 1)], threads=pick(1, 5))
+
+
+def sweep_cases_from(seed):
+    rng = np.random.default_rng(seed)
+    out = {}
+    while len(out) < SWEEP_CASES:
+        d = _draw(rng, len(out) % 2 == 0)   # the packed format and the custom one in turn
+        h = Handle(d)
+        if not h.ok or any(SUCCESS != h.execute_status(kind, TENSOR_TYPES) for kind in (FWD, BWD, UPD)):
+            continue                        # (a handle that answers WARN_* is kept and runs)
+        out["sweep_%02d" % len(out)] = d
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases():
+    """name -> desc: SWEEP_CASES descriptors drawn from SWEEP_SEED, half in the packed format in fp32 with block factors drawn from
+    divisors and non-divisors (0 among them), half in the custom format in fp32 or bf16-in / fp32-out. A draw that create or
+    execute_status refuses is left out. tests/test_fc_sweep_cpu.py counts what the set holds; the seed is the first from 0 up that
+    passes that census."""
+    return sweep_cases_from(SWEEP_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_expected(name):
+    """(handle restatement, plain inputs, the six tensors' expected contents) of a sweep case (computed once, shared: read only)"""
+    d = sweep_cases()[name]
+    h = Handle(d)
+    x, w, dy = plain_inputs(name, d)
+    want = tensors(h, x, w, dy)
+    for a in (x, w, dy) + tuple(want.values()):
+        a.setflags(write=False)
+    return h, (x, w, dy), want
+
+
+def contract64(d, x, w, dy):
+    """key -> (value, bound, compared) for y [N][K], dx [N][C] and dw [K][C]: the layer's contract (include/
+    libxsmm_dnn_fullyconnected.h) as three float64 matrix products of the plain operands, y = x w^T, dx = dy w,
+    dw = dy^T x. Bounds: each element is a chain of n fused multiply-adds from +0.0 over the whole reduction length (n = C, K, N),
+    n roundings of relative size 2^-24 compounded: n * 2^-24 / (1 - n * 2^-24) * sum|a * b|. With bf16 inputs the products are
+    exact in fp32 and the bound still holds; dx and dw are then stored to bf16 by round-to-nearest-even, half a unit of its 8
+    significant bits: 2^-8 * (|value| + bound) more. compared is all True: the layer has no decision."""
+    gam = lambda n: n * U24 / (1 - n * U24)  # noqa: E731
+    x, w, dy = (np.asarray(a, dtype=np.float64) for a in (x, w, dy))
+    res = {"y": (x @ w.T, gam(d["C"]) * (np.abs(x) @ np.abs(w).T)), "dx": (dy @ w, gam(d["K"]) * (np.abs(dy) @ np.abs(w))),
+           "dw": (dy.T @ x, gam(d["N"]) * (np.abs(dy).T @ np.abs(x)))}
+    if d["datatype_in"] == BF16:
+        for key in ("dx", "dw"):
+            value, bound = res[key]
+            res[key] = (value, bound + BF16_RNE * (np.abs(value) + bound))
+    return {key: (value, bound, np.ones(value.shape, dtype=bool)) for key, (value, bound) in res.items()}

@@ -2,6 +2,7 @@
 logical threads, seeded inputs, and the arithmetic contract of include/libxsmm_dnn_pooling.h (FWD and BWD, MAX and AVG, fp32
 and bf16) as plain array code. Shared by tests/test_pool_cpu.py, tests/test_pool_gpu.py and tools/golden/pool_capture.py; the
 reference's own answers are in tests/golden/pool.npz and tests/test_pool_cpu.py holds this file against them bit for bit."""
+import functools
 import os
 import zlib
 
@@ -123,7 +124,8 @@ class Handle(FmHandle):
 
     def execute_status(self, kind, bound, ltid=0):
         """what execute_st returns before anything is computed (bound: the tensor types that are bound). Up to
-        ERR_UNSUPPORTED_POOLING the reference's order; the last three checks are this engine's own."""
+        ERR_UNSUPPORTED_POOLING the reference's order; the last four checks are this engine's own (the last of them: sizes below
+        1, among them an output plane that the floor of a window larger than the padded plane leaves empty)."""
         d = self.d
         if kind not in (FWD, BWD):
             return ERR_INVALID_KIND
@@ -139,6 +141,10 @@ class Handle(FmHandle):
         if d["pooling_type"] == MAX and d["datatype_mask"] != I32:
             return ERR_UNSUPPORTED_DATATYPE
         if not self.runnable():
+            return ERR_GENERAL
+        if min(d["N"], d["H"], d["W"], d["R"], d["S"], d["u"], d["v"], self.ofh, self.ofw) < 1 \
+                or min(d["pad_h"], d["pad_w"], d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]) < 0 \
+                or d["H"] * d["W"] >= 1 << 27 or self.ofh * self.ofw >= 1 << 27:
             return ERR_GENERAL
         return SUCCESS
 
@@ -168,22 +174,31 @@ def inputs(name, d):
 
 
 # ---- the arithmetic contract ---------------------------------------------------------------------------------------------------------
-def _windows(h):
+WRONG = ("ge", "clipped count", "pads swapped", "strides swapped", "mask on padded plane")  # what forward(wrong=...) can get wrong on purpose
+
+
+def _windows(h, wrong=None):
     """per (kh, kw): the outputs whose window position lies inside the plane, and the input coordinates it reads"""
     d = h.d
+    u, v, pad_h, pad_w = d["u"], d["v"], d["pad_h"], d["pad_w"]
+    if wrong == "pads swapped":
+        pad_h, pad_w = pad_w, pad_h
+    if wrong == "strides swapped":
+        u, v = v, u
     for kh in range(d["R"]):
-        hi = np.arange(h.ofh) * d["u"] - d["pad_h"] + kh
+        hi = np.arange(h.ofh) * u - pad_h + kh
         hv = np.nonzero((hi >= 0) & (hi < d["H"]))[0]
         for kw in range(d["S"]):
-            wi = np.arange(h.ofw) * d["v"] - d["pad_w"] + kw
+            wi = np.arange(h.ofw) * v - pad_w + kw
             wv = np.nonzero((wi >= 0) & (wi < d["W"]))[0]
             if hv.size and wv.size:
                 yield hv, wv, hi[hv], wi[wv]
 
 
-def forward(h, x, out, mask=None):
+def forward(h, x, out, mask=None, wrong=None):
     """FWD into the pre-filled destinations out (element type) and mask (int32, MAX only), in place: the interior of out and
-    the mask elements whose output found an input above -FLT_MAX are written, nothing else."""
+    the mask elements whose output found an input above -FLT_MAX are written, nothing else. wrong: one of WRONG, a mistake made
+    on purpose (for tests/test_pool_sweep_cpu.py, which shows that its float64 comparison rejects each of them)."""
     d = h.d
     iph, ipw, oph, opw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
     xin = as_f32(h, x)[:, iph:iph + d["H"], ipw:ipw + d["W"], :]
@@ -192,21 +207,25 @@ def forward(h, x, out, mask=None):
     if d["pooling_type"] == MAX:
         cur = np.full((work, h.ofh, h.ofw, 16), -FLT_MAX, dtype=np.float32)
         idx = np.full((work, h.ofh, h.ofw, 16), SENTINEL, dtype=np.int32)
-        for hv, wv, hi, wi in _windows(h):  # kh ascending, then kw ascending; a strict > replaces: the first maximum wins, a NaN never
+        for hv, wv, hi, wi in _windows(h, wrong):  # kh ascending, then kw ascending; a strict > replaces: the first maximum wins, a NaN never
             v = xin[:, hi[:, None], wi[None, :], :]
             here = ((hi[:, None] * d["W"] + wi[None, :]) * 16).astype(np.int32)[None, :, :, None] + lanes
+            if wrong == "mask on padded plane":
+                here = (((hi[:, None] + iph) * h.ifwp + wi[None, :] + ipw) * 16).astype(np.int32)[None, :, :, None] + lanes
             c, i = cur[:, hv[:, None], wv[None, :], :], idx[:, hv[:, None], wv[None, :], :]
-            won = v > c
+            won = v >= c if wrong == "ge" else v > c
             cur[:, hv[:, None], wv[None, :], :] = np.where(won, v, c)
             idx[:, hv[:, None], wv[None, :], :] = np.where(won, here, i)
         np.copyto(mask, idx, where=idx != SENTINEL)
         res = cur
     else:
         acc = np.zeros((work, h.ofh, h.ofw, 16), dtype=np.float32)
-        for hv, wv, hi, wi in _windows(h):
+        count = np.zeros((1, h.ofh, h.ofw, 1), dtype=np.float32)
+        for hv, wv, hi, wi in _windows(h, wrong):
             acc[:, hv[:, None], wv[None, :], :] = acc[:, hv[:, None], wv[None, :], :] + xin[:, hi[:, None], wi[None, :], :]
+            count[:, hv[:, None], wv[None, :], :] += 1
         recp = np.float32(1.0) / (np.float32(d["R"]) * np.float32(d["S"]))
-        res = acc * recp
+        res = acc * (np.float32(1.0) / np.maximum(count, 1) if wrong == "clipped count" else recp)
     out[:, oph:oph + h.ofh, opw:opw + h.ofw, :] = stored(h, res)
 
 
@@ -261,3 +280,140 @@ def expected(name, d, fused=False):
 
 def load_golden():
     return np.load(os.path.join(GOLDEN, "pool.npz"))
+
+
+# ---- the seeded sweep: descriptors nobody picked --------------------------------------------------------------------------------
+SWEEP_SEED, SWEEP_CASES = 2, 48
+SWEEP_CHANNELS = (16, 24, 32, 48, 64, 80)
+U24, BF16_CUT = 2.0 ** -24, 2.0 ** -7  # the unit roundoff of fp32; what a truncation to bf16 takes off at most, relative
+
+
+def gamma(n):
+    """n roundings of relative size 2^-24 each, compounded: (1 + 2^-24)^n - 1 <= n * 2^-24 / (1 - n * 2^-24)"""
+    n = np.asarray(n, dtype=np.float64)
+    return n * U24 / (1 - n * U24)
+
+
+def _draw(rng):
+    pick = lambda lo, hi: int(rng.integers(lo, hi + 1))  # noqa: E731
+    H, W = (pick(17, 40), pick(17, 40)) if pick(0, 7) == 0 else (pick(1, 12), pick(1, 12))
+    R, S, u, v = pick(1, 4), pick(1, 4), pick(1, 4), pick(1, 4)
+    pad_h, pad_w = pick(0, 3), pick(0, 3)
+    pin, pout = (pick(0, 2), pick(0, 2)), (pick(0, 2), pick(0, 2))
+    return desc(H, W, R, S, u, v, pad_h, pad_w, pin, pout, N=pick(1, 5), C=SWEEP_CHANNELS[pick(0, 5)], pool=(MAX, AVG)[pick(0, 1)],
+                dt=(F32, BF16)[pick(0, 1)], threads=pick(1, 5))
+
+
+def window_counts(h):
+    """[ofh][ofw]: the number of input elements inside each output's window (R * S where nothing clips it, 0 where it lies wholly
+    in the padding)"""
+    d = h.d
+    rows = [max(0, min(ho * d["u"] - d["pad_h"] + d["R"], d["H"]) - max(ho * d["u"] - d["pad_h"], 0)) for ho in range(h.ofh)]
+    cols = [max(0, min(wo * d["v"] - d["pad_w"] + d["S"], d["W"]) - max(wo * d["v"] - d["pad_w"], 0)) for wo in range(h.ofw)]
+    return np.outer(rows, cols)
+
+
+def sweep_cases_from(seed):
+    rng = np.random.default_rng(seed)
+    out = {}
+    while len(out) < SWEEP_CASES:
+        d = _draw(rng)
+        h = Handle(d)
+        bound = BINDABLE if d["pooling_type"] == MAX else BINDABLE[:4]
+        if h.status != SUCCESS or SUCCESS != h.execute_status(FWD, bound) or SUCCESS != h.execute_status(BWD, bound):
+            continue
+        if not window_counts(h).any():  # no window holds an input element: it would test nothing
+            continue
+        out["sweep_%02d" % len(out)] = d
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases():
+    """name -> desc: SWEEP_CASES descriptors drawn from SWEEP_SEED. A draw that create or execute_status refuses (an output plane
+    below 1 x 1) is left out, one in which no window holds an input element is drawn again. tests/test_pool_sweep_cpu.py counts
+    what the set holds; the seed is the first from 0 up that passes that census."""
+    return sweep_cases_from(SWEEP_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_expected(name):
+    """expected() of a sweep case (computed once, shared: read only)"""
+    t = expected(name, sweep_cases()[name])
+    for a in t.values():
+        if a is not None:
+            a.setflags(write=False)
+    return t
+
+
+def contract64(h, t):
+    """key -> (value, bound, compared) for out, mask (MAX) and din: the layer's contract (include/libxsmm_dnn_pooling.h, DESIGN.md
+    8h) in float64, window by window, written from that text and not from forward / backward above. Interior elements only,
+    [item][row][column][16]. compared is all True: pooling has no decision that rounding can flip (a tie falls alike on both sides).
+
+    MAX FWD   the maximum of the window's elements inside the plane; the first one in row order, then column order, wins (numpy's
+              argmax). bound 0: no rounding is involved, and a bf16 maximum is a bf16 number. A window without an element gives
+              -FLT_MAX as the element type stores it (bf16: cut to 0xff7f) and leaves the mask's sentinel.
+    AVG FWD   (sum of those elements) / (R * S), whatever the clipping. n elements cost n - 1 adds, the reciprocal is rounded
+              once and multiplied once: gamma(n + 1) * sum|x| / (R * S).
+    MAX BWD   an input element receives the dout of every output whose mask names it: t terms, t - 1 roundings (the first add
+              to +0.0 is exact): gamma(t - 1) * sum|dout|.
+    AVG BWD   it receives dout * (1 / (R * S)) from every output whose window covers it: the reciprocal, the product and t - 1
+              adds: gamma(t + 1) * sum|dout| / (R * S).
+    A bf16 store cuts off below 2^-7 * |what was computed| <= 2^-7 * (|value| + bound), added to the bound.
+    An input element no term reaches is +0.0: value 0, bound 0."""
+    d = h.d
+    H, W, R, S, u, v = d["H"], d["W"], d["R"], d["S"], d["u"], d["v"]
+    iph, ipw, oph, opw = d["pad_h_in"], d["pad_w_in"], d["pad_h_out"], d["pad_w_out"]
+    is_max = d["pooling_type"] == MAX
+    x = as_f32(h, t["x"]).astype(np.float64)[:, iph:iph + H, ipw:ipw + W, :]
+    g = as_f32(h, t["dout"]).astype(np.float64)[:, oph:oph + h.ofh, opw:opw + h.ofw, :]
+    work = h.work()
+    items, lanes = np.arange(work)[:, None], np.arange(16)[None, :]
+    out, out_bound = np.zeros((work, h.ofh, h.ofw, 16)), np.zeros((work, h.ofh, h.ofw, 16))
+    mask = np.full((work, h.ofh, h.ofw, 16), SENTINEL, dtype=np.int64)
+    din, din_abs, din_terms = np.zeros((work, H, W, 16)), np.zeros((work, H, W, 16)), np.zeros((work, H, W, 16), dtype=np.int64)
+    lowest = float(-FLT_MAX) if h.f32 else float(widen(truncate(np.array([-FLT_MAX])))[0])
+    for ho in range(h.ofh):
+        a0, a1 = max(ho * u - d["pad_h"], 0), min(ho * u - d["pad_h"] + R, H)
+        for wo in range(h.ofw):
+            b0, b1 = max(wo * v - d["pad_w"], 0), min(wo * v - d["pad_w"] + S, W)
+            if a0 >= a1 or b0 >= b1:
+                out[:, ho, wo, :] = lowest if is_max else 0.0
+                continue
+            win = x[:, a0:a1, b0:b1, :].reshape(work, -1, 16)
+            n = win.shape[1]
+            if is_max:
+                k = win.argmax(axis=1)
+                out[:, ho, wo, :] = np.take_along_axis(win, k[:, None, :], axis=1)[:, 0, :]
+                row, col = a0 + k // (b1 - b0), b0 + k % (b1 - b0)
+                mask[:, ho, wo, :] = (row * W + col) * 16 + lanes
+                np.add.at(din, (items, row, col, lanes), g[:, ho, wo, :])
+                np.add.at(din_abs, (items, row, col, lanes), np.abs(g[:, ho, wo, :]))
+                np.add.at(din_terms, (items, row, col, lanes), 1)
+            else:
+                out[:, ho, wo, :] = win.sum(axis=1) / (R * S)
+                out_bound[:, ho, wo, :] = gamma(n + 1) * np.abs(win).sum(axis=1) / (R * S)
+                din[:, a0:a1, b0:b1, :] += (g[:, ho, wo, :] / (R * S))[:, None, None, :]
+                din_abs[:, a0:a1, b0:b1, :] += (np.abs(g[:, ho, wo, :]) / (R * S))[:, None, None, :]
+                din_terms[:, a0:a1, b0:b1, :] += 1
+    din_bound = np.where(din_terms > 0, gamma(np.maximum(din_terms + (-1 if is_max else 1), 0)) * din_abs, 0.0)
+    if not h.f32:
+        din_bound = din_bound + BF16_CUT * (np.abs(din) + din_bound)
+        if not is_max:
+            out_bound = out_bound + BF16_CUT * (np.abs(out) + out_bound)
+    yes = np.ones(out.shape, dtype=bool)
+    res = {"out": (out, out_bound, yes), "din": (din, din_bound, np.ones(din.shape, dtype=bool)), "unreached": din_terms == 0}
+    if is_max:
+        res["mask"] = (mask, np.zeros(mask.shape), yes)
+    return res
+
+
+def interior(h, key, a):
+    """the elements of a tensor of expected() that contract64 computes, in its index order"""
+    d = h.d
+    if key == "out":
+        return as_f32(h, a)[:, d["pad_h_out"]:d["pad_h_out"] + h.ofh, d["pad_w_out"]:d["pad_w_out"] + h.ofw, :]
+    if key == "din":
+        return as_f32(h, a)[:, d["pad_h_in"]:d["pad_h_in"] + d["H"], d["pad_w_in"]:d["pad_w_in"] + d["W"], :]
+    return a

@@ -33,11 +33,13 @@ def case_data(name):
 class Layer:
     """a handle with six device tensors: inputs filled, destinations NaN between canaries"""
 
-    def __init__(self, xs, torch, name, threads=1, contents=None):
+    def __init__(self, xs, torch, name, threads=1, contents=None, sweep=False):
+        """sweep: name is a case of fc_common.sweep_cases(), which has its own number of threads"""
         self.xs, self.torch, self.L = xs, torch, xs.lib()
-        self.h, _, self.want = case_data(name)
+        self.h, _, self.want = fc.sweep_expected(name) if sweep else case_data(name)
         want = self.want if contents is None else contents
-        d = dict(fc.COMPUTE_CASES[name], threads=threads)
+        d = fc.sweep_cases()[name] if sweep else dict(fc.COMPUTE_CASES[name], threads=threads)
+        threads = d["threads"]
         self.handle, st = xs.fc_create(d["N"], d["C"], d["K"], d["bn"], d["bk"], d["bc"], threads, d["datatype_in"], d["datatype_out"],
                                        d["buffer_format"], d["filter_format"], d["fuse_ops"])
         assert self.handle and st == self.h.status
