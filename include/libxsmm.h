@@ -841,6 +841,19 @@ LIBXSMM_API int libxsmm_matdiff(libxsmm_matdiff_info* info, libxsmm_datatype dat
   const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst); /* :62 */
 LIBXSMM_API void libxsmm_matdiff_reduce(libxsmm_matdiff_info* output, const libxsmm_matdiff_info* input); /* :69 */
 LIBXSMM_API void libxsmm_matdiff_clear(libxsmm_matdiff_info* info);                                       /* :71 */
+/* Hash and byte compare (include/libxsmm_math.h:76-89). Operands that are all host memory take a host loop and launch nothing;
+ * with an operand in plain device memory the call runs on the GPU on the calling thread's stream, stages a pageable partner,
+ * waits and returns the value (libxsmm_amd.h has the forms that do not wait, and the batches). NULL with a size gives the
+ * answer of size 0 (one line on stderr if libxsmm_verbosity != 0). */
+/** CRC-32C (reflected polynomial 0x82F63B78) of `size` bytes; the register starts at `seed`, nothing is inverted. */
+LIBXSMM_API unsigned int libxsmm_hash(const void* data, unsigned int size, unsigned int seed);             /* :89 */
+/** 0 if the `size` bytes are equal, 1 otherwise. */
+LIBXSMM_API int libxsmm_memcmp(const void* a, const void* b, size_t size);                                 /* :86 */
+LIBXSMM_API unsigned char libxsmm_diff(const void* a, const void* b, unsigned char size);                  /* :76 */
+/** The index of the first of the `n` items of `bn` (`stride` bytes apart, size <= stride) that equals `a`, visited in the
+ *  order hint, hint + 1, ..., n - 1, 0, ..., hint - 1; `n` if none does. hint is taken modulo n; n == 0 returns 0. */
+LIBXSMM_API unsigned int libxsmm_diff_n(const void* a, const void* bn, unsigned char size, unsigned char stride,
+  unsigned int hint, unsigned int n);                                                                      /* :82 */
 /* prints a GEMM call's arguments to `ostream` (a FILE*), include/libxsmm_frontend.h:471-482; ostream == NULL (the
  * reference's MHD image dump of the operands) is a no-op here */
 LIBXSMM_API void libxsmm_gemm_print(void* ostream, libxsmm_gemm_precision precision, const char* transa, const char* transb,

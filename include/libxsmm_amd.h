@@ -414,6 +414,30 @@ LIBXSMM_API int libxsmm_amd_matdiff_batch(libxsmm_matdiff_info* info, libxsmm_ma
   libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst, const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst,
   long long stride_ref, long long stride_tst, long long batch);
 
+/* ---- hash and byte compare on operands in device memory (libxsmm_hash, libxsmm_memcmp, libxsmm_diff, libxsmm_diff_n) ---------- */
+/** The reference's four functions (libxsmm.h) run on the GPU whenever an operand is plain device memory. These are the forms
+ *  that do not wait, and the batches. All return EXIT_SUCCESS or EXIT_FAILURE; all arguments are checked before
+ *  any device is probed and a refused call writes nothing: a NULL result, a NULL operand of a call that has bytes to read, a
+ *  negative count or stride, ld < line_bytes with lines > 1, and, for the _async forms, a result the GPU does not reach. An
+ *  item is `lines` lines of `line_bytes` bytes, `ld` bytes apart, hashed or compared as the concatenation of its lines; the
+ *  bytes between line_bytes and ld are never read. Item i lies `i * stride` bytes after the first; stride == 0 is legal.
+ *  batch == 0 writes nothing; an empty item gives `seed` (0 for the compares) and launches nothing. Inside
+ *  libxsmm_amd_defer_begin/end these calls are not recorded: they seal the open burst and run in call order.
+ *
+ *  libxsmm_amd_hash_async: libxsmm_hash(data, size, seed) for any size_t size into `*result`, memory the GPU reaches (device,
+ *  pinned or managed); the last kernel writes it and nobody waits. */
+LIBXSMM_API int libxsmm_amd_hash_async(unsigned int* result, const void* data, size_t size, unsigned int seed);
+/** One hash per item into results[0 .. batch). `results` in plain host memory is complete on return; memory the GPU reaches
+ *  is written in stream order and nobody waits. */
+LIBXSMM_API int libxsmm_amd_hash_batch(unsigned int* results, const void* data, size_t line_bytes, long long lines, long long ld,
+  long long stride, long long batch, unsigned int seed);
+/** libxsmm_memcmp(a, b, size) into `*result` (0 or 1), memory the GPU reaches; nobody waits. */
+LIBXSMM_API int libxsmm_amd_memcmp_async(int* result, const void* a, const void* b, size_t size);
+/** 0 or 1 per item into results[0 .. batch). `first_diff` is NULL or receives the lowest index of a differing item, -1 if all
+ *  are equal. Either may be host or device memory, as for libxsmm_amd_hash_batch. */
+LIBXSMM_API int libxsmm_amd_memcmp_batch(int* results, long long* first_diff, const void* a, const void* b, size_t line_bytes,
+  long long lines, long long lda, long long ldb, long long stride_a, long long stride_b, long long batch);
+
 /* ---- DNN tensor copy-in / copy-out (libxsmm_dnn_copyin_tensor / _copyout_tensor, see libxsmm_dnn_tensor.h) ------------------- */
 #include "libxsmm_dnn_tensor.h"
 /** The reference forms without their wait: the same checks in the same order and the same statuses, then both `tensor`'s

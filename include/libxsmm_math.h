@@ -1,5 +1,5 @@
 /* libxsmm_math.h -- the reference splits its interface over several headers; nearly everything of its include/libxsmm_math.h
- * that this engine provides (matdiff, isqrt, icbrt, sexp2, shuffle) is declared in libxsmm.h, which includes this header as the
+ * that this engine provides (matdiff, hash, memcmp, diff, diff_n, isqrt, icbrt, sexp2, shuffle) is declared in libxsmm.h, which includes this header as the
  * reference's does. Declared here are the exact powers of two that the quantisation scale factors of libxsmm_dnn.h are
  * defined through (reference: include/libxsmm_math.h:135-144, src/libxsmm_math.c:462-520). They are host functions. */
 #ifndef LIBXSMM_MATH_H_COMPAT

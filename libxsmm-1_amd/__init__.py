@@ -473,6 +473,15 @@ def _declare(L):
     # matdiff on device operands
     sig("libxsmm_amd_matdiff_async", i, C.POINTER(MatdiffInfo), i, i, i, vp, vp, c_int_p, c_int_p)
     sig("libxsmm_amd_matdiff_batch", i, C.POINTER(MatdiffInfo), C.POINTER(MatdiffInfo), C.POINTER(ll), i, i, i, vp, vp, c_int_p, c_int_p, ll, ll, ll)
+    # hash and byte compare
+    sig("libxsmm_hash", u, vp, u, u)
+    sig("libxsmm_memcmp", i, vp, vp, C.c_size_t)
+    sig("libxsmm_diff", C.c_ubyte, vp, vp, C.c_ubyte)
+    sig("libxsmm_diff_n", u, vp, vp, C.c_ubyte, C.c_ubyte, u, u)
+    sig("libxsmm_amd_hash_async", i, vp, vp, C.c_size_t, u)
+    sig("libxsmm_amd_hash_batch", i, vp, vp, C.c_size_t, ll, ll, ll, ll, u)
+    sig("libxsmm_amd_memcmp_async", i, vp, vp, vp, C.c_size_t)
+    sig("libxsmm_amd_memcmp_batch", i, vp, vp, vp, vp, C.c_size_t, ll, ll, ll, ll, ll, ll)
     sig("libxsmm_amd_gemm_batch_groups", i, i, i, i, C.c_char_p, C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, vp, vp,
         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), c_int_p, i)
 
@@ -939,6 +948,42 @@ def matdiff_batch(ref, tst, dt, m, n, ldref, ldtst, stride_ref, stride_tst, batc
     rc = lib().libxsmm_amd_matdiff_batch(pinfo, pitems, C.byref(which), dt, m, n, dptr(ref), dptr(tst), iptr(ldref), iptr(ldtst),
                                          stride_ref, stride_tst, batch)
     return rc, out, (list(arr)[:batch] if arr is not None else None), which.value
+
+
+# ---- hash and byte compare (include/libxsmm.h, include/libxsmm_amd.h) -----------------------------------------------------------
+def hash(data, size, seed=0, result=None):
+    """libxsmm_hash of `size` bytes at data (tensor, array or address); result: memory the GPU reaches (a tensor of 4 bytes) --
+    the call is libxsmm_amd_hash_async then (any size_t size) and its status is returned instead"""
+    if result is not None:
+        return lib().libxsmm_amd_hash_async(dptr(result), dptr(data), size, seed)
+    return lib().libxsmm_hash(dptr(data), size, seed)
+
+
+def hash_batch(results, data, line_bytes, lines, ld, stride, batch, seed=0):
+    """libxsmm_amd_hash_batch; results: `batch` uint32 in host or device memory; returns the status"""
+    return lib().libxsmm_amd_hash_batch(dptr(results), dptr(data), line_bytes, lines, ld, stride, batch, seed)
+
+
+def memcmp(a, b, size, result=None):
+    """libxsmm_memcmp (0: equal, 1: not); result: memory the GPU reaches -- libxsmm_amd_memcmp_async, returns the status"""
+    if result is not None:
+        return lib().libxsmm_amd_memcmp_async(dptr(result), dptr(a), dptr(b), size)
+    return lib().libxsmm_memcmp(dptr(a), dptr(b), size)
+
+
+def memcmp_batch(results, a, b, line_bytes, lines, lda, ldb, stride_a, stride_b, batch, first_diff=None):
+    """libxsmm_amd_memcmp_batch; results: `batch` int32, first_diff: None or one int64, host or device memory; returns the status"""
+    return lib().libxsmm_amd_memcmp_batch(dptr(results), dptr(first_diff), dptr(a), dptr(b), line_bytes, lines, lda, ldb, stride_a, stride_b, batch)
+
+
+def diff(a, b, size):
+    """libxsmm_diff (size <= 255)"""
+    return lib().libxsmm_diff(dptr(a), dptr(b), size)
+
+
+def diff_n(a, bn, size, stride, hint, n):
+    """libxsmm_diff_n: the first item of bn equal to a in the order hint, ..., n - 1, 0, ..., hint - 1, or n"""
+    return lib().libxsmm_diff_n(dptr(a), dptr(bn), size, stride, hint, n)
 
 
 # ---- DNN tensors and the fully-connected layer (include/libxsmm_dnn.h, include/libxsmm_dnn_fullyconnected.h) ------------------

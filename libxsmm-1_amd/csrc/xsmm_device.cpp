@@ -20,7 +20,7 @@ std::atomic<unsigned long long> g_launches{0};
 thread_local const char* tl_last_kernel = "";
 
 struct Scratch { void* ptr = nullptr; size_t size = 0; void* stream = nullptr; bool used = false; };
-thread_local Scratch tl_scratch[8];
+thread_local Scratch tl_scratch[16];
 }
 
 // The engine's current stream is a per-thread setting (every entry point may be called from any thread, as in the
@@ -318,7 +318,7 @@ void index_upload_commit()
 
 void* scratch(int slot, size_t bytes)
 {
-  Scratch& s = tl_scratch[slot & 7];
+  Scratch& s = tl_scratch[slot & 15];
   // Launches are asynchronous: whatever was queued on the stream that used this buffer last may still be reading it.
   // (Scratch only serves the staging of host-resident operands -- the compatibility path -- so the wait costs nothing
   // on the device-resident path.)

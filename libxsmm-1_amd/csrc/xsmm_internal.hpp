@@ -404,6 +404,22 @@ int launch_matdiff_emit(const MatdiffRecord* rec, long long count, libxsmm_matdi
 bool matdiff_route(libxsmm_matdiff_info* info, libxsmm_datatype datatype, libxsmm_blasint m, libxsmm_blasint n, const void* ref, const void* tst,
   const libxsmm_blasint* ldref, const libxsmm_blasint* ldtst, int* rc);
 
+// hash and byte compare on device operands (xsmm_hash.cpp, kernels/hash.hip; the geometry is kernels/hash_plan.h)
+struct HashArgs {
+  const void* a; const void* b;           // memory the GPU reaches; b: the compare only
+  unsigned long long line_bytes;          // an item is `lines` lines of line_bytes bytes, lda / ldb bytes apart, taken as one run of bytes
+  long long lines, lda, ldb, stride_a, stride_b, batch;
+  long long item0;                        // the index of the first item of this launch in the caller's batch
+  unsigned int seed; int compare;         // compare: 0 / 1 per item instead of the hash
+};
+struct DiffKey { unsigned char b[256]; }; // the `a` of libxsmm_diff_n when it is host memory: it travels as a kernel argument
+// all return hipError_t as int; first: a workspace word that takes the lowest differing item (or NULL)
+int launch_hash_items(const HashArgs& a, unsigned int* results /* [batch] */, long long* first, void* stream);        // hash_small() items
+int launch_hash_units(const HashArgs& a /* one item */, unsigned int* partial /* [HASH_MAX_BLOCKS] */, unsigned int* result, long long* first, void* stream);
+int launch_hash_first(long long* first, long long* out, bool clear, void* stream); // clear: before the items; else *out = the index or -1
+int launch_diff_n(const DiffKey& key, const void* a /* NULL: the key */, const void* bn, unsigned int size, unsigned int stride, unsigned int hint, unsigned int n,
+  unsigned int* best /* workspace: the least (i - hint) mod n of a match, 0xffffffff if none */, void* stream);
+
 // fully-connected layer (xsmm_dnn_fc.cpp, kernels/fc.hip): D(i, j) = chain over r of P(i, r) * Q(r, j), blocked operands
 struct FcDim { int blk; long long outer, inner; }; // index x lies at (x / blk) * outer + (x % blk) * inner elements; a plain dimension: blk >= extent
 constexpr int FC_PLAIN = 1 << 30;         // blk of a dimension that is not blocked
