@@ -5,7 +5,11 @@ without LIBXSMM_RNN_CELL_AVX512) loop for loop -- every SMM or batch-reduce SMM 
 src/libxsmm_dnn_elementwise.c are evaluated with numpy in fp32, the transcendentals with the platform libm (rnn_common.sigmoid, tanh).
 tests/test_rnn_bwd_cpu.py holds all of it against the reference's captured outputs (tests/golden/rnn_bwd.npz, written by
 tools/golden/rnn_bwd_capture.py). The one liberty: the LSTM template accumulates dw and dr in a blocked scratch copy and reformats it
-at the end; here the same SMM calls write the plain tensor directly (no arithmetic differs)."""
+at the end; here the same SMM calls write the plain tensor directly (no arithmetic differs).
+
+Beside the restatement, and independent of it: contract64, a float64 definition of every gradient tensor written from the text of
+include/libxsmm_dnn_rnncell.h with derived error bounds (and forward64, the forward cell in the same terms), and sweep_cases, 32 seeded
+descriptors with their census."""
 import functools
 import zlib
 
@@ -203,6 +207,195 @@ def backward(h, t, kind, log=None):
     return out
 
 
+# ---- the float64 contract ------------------------------------------------------------------------------------------------------------
+# What include/libxsmm_dnn_rnncell.h says each tensor is, in float64 numpy on the plain tensors: no blocks, no segments, no oracle call.
+# Beside every value runs a bound of what the fp32 evaluation the header describes may be off by, derived and never measured:
+#   one rounded operation (multiply, add, subtract, divide, the float conversion of a double exp or tanh) on operands that are off by
+#     at most p in the result's terms: p + u * (|result| + p);
+#   a chain of L fused multiply-adds from a start s: with P the operands' errors carried through (|a| eb + ea |b| + ea eb, summed, + es),
+#     P + g * (|s| + sum |a| |b| + P), g = L u / (1 - L u): the order of the chain plays no part, so neither do blocks and segments;
+#   plain adds from +0.0 (db) are such a chain with a = 1; ReLU's derivative is exact; a transcendental of an argument that is itself
+#     off by e: |tanh'| <= 1 gives e, exp(-z) gives exp(-z) * expm1(e).
+# u = 2^-24. SLACK covers the float64 evaluation of the values and of the bounds themselves (chains of a few thousand terms at 2^-53,
+# the double exp and tanh of the libm at an ulp: below 2^-40 of any term that u multiplies).
+U32 = 2.0 ** -24
+SLACK = 1 + 2.0 ** -20
+# mistakes made on purpose in the definition (tests/test_rnn_bwd_cpu.py shows that the bounds reject each)
+WRONG = ("dr_from_h_of_the_step", "hp_not_used_at_step_0", "df_from_cs_of_the_step", "dw_c_and_f_columns_swapped", "dout_without_dh",
+         "dcsp_without_f", "act_prime_of_the_neighbouring_step", "db_without_the_last_step", "dx_over_r", "steps_beyond_seq",
+         "recurrence_over_r_untransposed", "dp_with_ci_for_co")
+
+
+class V:
+    """float64 values beside the bounds of what fp32 may be off by"""
+    __slots__ = ("v", "e")
+
+    def __init__(self, v, e=None):
+        self.v = np.asarray(v, dtype=np.float64)
+        self.e = np.zeros(self.v.shape) if e is None else np.asarray(e, dtype=np.float64)
+
+    def cols(self, a, b):
+        return V(self.v[:, a:b], self.e[:, a:b])
+
+
+def hcat(parts):
+    return V(np.concatenate([p.v for p in parts], axis=1), np.concatenate([p.e for p in parts], axis=1))
+
+
+def vcat(parts):
+    return V(np.concatenate([p.v for p in parts], axis=0), np.concatenate([p.e for p in parts], axis=0))
+
+
+class Rounding:
+    """the operations of the header's text at unit roundoff u"""
+
+    def __init__(self, u=U32):
+        self.u = u
+
+    def rounded(self, v, p):
+        return V(v, p + self.u * (np.abs(v) + p))
+
+    def mul(self, a, b):
+        return self.rounded(a.v * b.v, np.abs(a.v) * b.e + a.e * np.abs(b.v) + a.e * b.e)
+
+    def add(self, a, b):
+        return self.rounded(a.v + b.v, a.e + b.e)
+
+    def sub(self, a, b):
+        return self.rounded(a.v - b.v, a.e + b.e)
+
+    def chain(self, start, a, b):
+        """start (None: +0.0) continued by one fma chain over the inner dimension of a @ b"""
+        L = a.v.shape[-1]
+        g = L * self.u / (1 - L * self.u)
+        v, mag = a.v @ b.v, np.abs(a.v) @ np.abs(b.v)
+        p = np.abs(a.v) @ b.e + a.e @ np.abs(b.v) + a.e @ b.e
+        if start is not None:
+            v, mag, p = v + start.v, mag + np.abs(start.v), p + start.e
+        return V(v, p + g * (mag + p))
+
+    def sigmoid(self, z):
+        """1.0f / (1.0f + (float)exp((double)-z))"""
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = np.exp(-z.v)
+            den = self.add(V(1.0), self.rounded(e, e * np.expm1(z.e)))
+            return self.rounded(1 / den.v, np.where(den.v > den.e, den.e / (den.v * (den.v - den.e)), np.inf))
+
+    def tanh(self, z):
+        return self.rounded(np.tanh(z.v), z.e)
+
+    def act(self, cell, z):
+        if cell == RELU:
+            return V(np.where(z.v < 0, 0.0, z.v), z.e)
+        return self.sigmoid(z) if cell == SIGMOID else self.tanh(z)
+
+    def act_prime(self, cell, z):
+        """of an argument taken as exact"""
+        one = V(1.0)
+        if cell == RELU:
+            return V(np.where(z.v < 0, 0.0, 1.0))
+        if cell == SIGMOID:
+            s = self.sigmoid(z)
+            return self.mul(self.sub(one, s), s)
+        t = self.tanh(z)
+        return self.sub(one, self.mul(t, t))
+
+
+def forward64(h, t, u=U32):
+    """the forward cell of the header's text: key -> V of the steps below the sequence length, [T][N][K]; t: x, hp, w, r, b (csp)"""
+    d = h.d
+    K, T, cell = d["K"], h.T, d["cell"]
+    R = Rounding(u)
+    f = lambda key: np.asarray(t[key], dtype=np.float64)  # noqa: E731
+    x, b, both = f("x"), f("b"), V(np.concatenate([f("w"), f("r")], axis=0))
+    hprev = V(f("hp")[0])
+    steps = {key: [] for key in rc.written(cell)}
+    if h.simple():
+        for s in range(T):
+            z = R.chain(V(np.broadcast_to(b, hprev.v.shape)), hcat([V(x[s]), hprev]), both)
+            hprev = R.act(cell, z)
+            steps["z"].append(z)
+            steps["h"].append(hprev)
+    else:
+        start = V(b)
+        if d["forget_bias"] is not None:  # b_f + forget_bias: one rounded add
+            fb = np.zeros(4 * K)
+            fb[2 * K:3 * K] = np.float32(d["forget_bias"])
+            start = R.add(start, V(fb))
+        csprev = V(f("csp")[0])
+        for s in range(T):
+            pre = R.chain(V(np.broadcast_to(start.v, (x.shape[1], 4 * K)), np.broadcast_to(start.e, (x.shape[1], 4 * K))), hcat([V(x[s]), hprev]), both)
+            gi, gci, gf, go = R.sigmoid(pre.cols(0, K)), R.tanh(pre.cols(K, 2 * K)), R.sigmoid(pre.cols(2 * K, 3 * K)), R.sigmoid(pre.cols(3 * K, 4 * K))
+            csprev = R.add(R.mul(gf, csprev), R.mul(gi, gci))
+            co = R.tanh(csprev)
+            hprev = R.mul(go, co)
+            for key, val in (("i", gi), ("ci", gci), ("f", gf), ("o", go), ("cs", csprev), ("co", co), ("h", hprev)):
+                steps[key].append(val)
+    return {key: V(np.stack([s.v for s in val]), np.stack([s.e for s in val]) * SLACK) for key, val in steps.items() if val}
+
+
+def contract64(h, t, kind, wrong=None, u=U32):
+    """key -> (value, bound) of every gradient tensor the kind writes: dx [T][N][C] (the steps below the sequence length), dw, dr, db,
+    and of the LSTM dcsp and dhp [N][K] (step 0 of their tensors). t: the inputs, the forward pass's tensors and dh (LSTM: dcs), all taken
+    as exact (fp32 or float64). wrong: one of WRONG."""
+    d = h.d
+    N, C, K, cell = d["N"], d["C"], d["K"], d["cell"]
+    T = d["max_T"] if wrong == "steps_beyond_seq" else h.T
+    R, one = Rounding(u), V(1.0)
+    f = lambda key: np.asarray(t[key], dtype=np.float64)  # noqa: E731
+    x, w, r, dh, hp, hh = f("x"), f("w"), f("r"), f("dh"), f("hp")[0], f("h")
+    rec = V(r if wrong == "recurrence_over_r_untransposed" and h.simple() else r.T)  # [q][k]: sum over q of delta[n][q] * r[k][q]
+    delta, out = [None] * T, {}
+    if h.simple():
+        z = f("z")
+        for s in range(T - 1, -1, -1):
+            near = s - 1 if s > 0 else min(s + 1, T - 1)
+            ap = R.act_prime(cell, V(z[near if wrong == "act_prime_of_the_neighbouring_step" else s]))
+            if s == T - 1:
+                delta[s] = R.mul(ap, V(dh[s]))
+            else:
+                delta[s] = R.mul(R.chain(None if wrong == "dout_without_dh" else V(dh[s]), delta[s + 1], rec), ap)
+    else:
+        gates = [f(key) for key in ("i", "f", "o", "ci", "co")]
+        cs, csp, dcp = f("cs"), f("csp")[0], V(f("dcs")[0])
+        for j in range(T - 1, -1, -1):
+            gi, gf, go, gci, gco = (V(a[j]) for a in gates)
+            if j == T - 1:
+                dout = V(dh[j])
+            else:
+                dout = R.chain(None, delta[j + 1], rec)
+                if wrong != "dout_without_dh":
+                    dout = R.add(dout, V(dh[j]))
+            dcp = R.add(dcp, R.mul(R.mul(dout, go), R.sub(one, R.mul(gco, gco))))
+            dci = R.mul(R.mul(dcp, gi), R.sub(one, R.mul(gci, gci)))
+            di = R.mul(R.mul(dcp, gci), R.mul(gi, R.sub(one, gi)))
+            before = cs[j] if wrong == "df_from_cs_of_the_step" else (csp if j == 0 else cs[j - 1])
+            df = R.mul(R.mul(dcp, V(before)), R.mul(gf, R.sub(one, gf)))
+            dp = R.mul(R.mul(dout, gci if wrong == "dp_with_ci_for_co" else gco), R.mul(go, R.sub(one, go)))
+            if not (wrong == "dcsp_without_f" and j == 0):
+                dcp = R.mul(gf, dcp)
+            delta[j] = hcat([di, dci, df, dp])  # the filters' column order: i, c, f, o
+        if T > 0:
+            out["dcsp"], out["dhp"] = dcp, R.chain(None, delta[0], rec)
+    if T < 1:
+        return {}
+    filt = V((r[np.arange(C) % K] if wrong == "dx_over_r" else w).T)
+    dx = [R.chain(None, delta[s], filt) for s in range(T)]
+    out["dx"] = V(np.stack([s.v for s in dx]), np.stack([s.e for s in dx]))
+    before = lambda s: (np.zeros_like(hp) if wrong == "hp_not_used_at_step_0" else hp) if s == 0 else hh[s - 1]  # noqa: E731
+    order = range(T - 1, -1, -1)
+    deltas = vcat([delta[s] for s in order])
+    out["dw"] = R.chain(None, V(np.concatenate([x[s] for s in order], axis=0).T), deltas)
+    out["dr"] = R.chain(None, V(np.concatenate([hh[s] if wrong == "dr_from_h_of_the_step" else before(s) for s in order], axis=0).T), deltas)
+    if wrong == "dw_c_and_f_columns_swapped" and cell == LSTM:
+        swap = np.concatenate([np.arange(K), np.arange(2 * K, 3 * K), np.arange(K, 2 * K), np.arange(3 * K, 4 * K)])
+        out["dw"] = V(out["dw"].v[:, swap], out["dw"].e[:, swap])
+    summed = vcat([delta[s] for s in order if not (wrong == "db_without_the_last_step" and s == T - 1)] or [V(np.zeros((1, h.G * K)))])
+    db = R.chain(None, V(np.ones((1, summed.v.shape[0]))), summed)
+    out["db"] = V(db.v[0], db.e[0])
+    return {key: (out[key].v, out[key].e * SLACK) for key in written(cell, kind)}
+
+
 # ---- cases -------------------------------------------------------------------------------------------------------------------------
 def _compute_cases():
     c = {}
@@ -213,6 +406,9 @@ def _compute_cases():
     c["bf5_lstm"] = desc(2, 8, 1040, 2, LSTM, bn=2, bc=8, bk=208)           # BF = 5
     c["bf12_lstm"] = desc(2, 8, 2064, 2, LSTM, bn=2, bc=8, bk=172)          # BF = 12
     c["t1_lstm"] = desc(4, 12, 16, 1, LSTM, bn=2, bc=4, bk=8)               # a single step
+    # the segment walk: 129 = 4 * 32 + 1 columns a segment, so every segment ends in the vector-ALU tail and the matrix steps resume
+    c["oddseg8_lstm"] = desc(2, 8, 1032, 2, LSTM, bn=2, bc=8, bk=129)       # BF = 8: 32 segments
+    c["maxseg_lstm"] = desc(2, 8, 2064, 2, LSTM, bn=2, bc=8, bk=129)        # BF = 16: 64 segments, the capacity of the segment array
     return c
 
 
@@ -232,6 +428,70 @@ LIMIT_CASES = {
     "steps_relu": desc(2, 3, 5, 65537, RELU, bn=2, bc=3, bk=5),                      # the dx launch splits at 65535 steps
     "manyrows_relu": desc(4194432, 8, 8, 1, RELU, bn=2097216, bc=8, bk=8),         # 65538 tiles of rows: one share is refused, two run
 }
+
+
+# one handle run at the lengths 4, 1 and 3 in turn, and FWD followed by BWDUPD on one handle (tests/test_rnn_bwd_gpu.py): 37 rows (odd,
+# beyond one chunk of the weight reduction), K beyond one tile, blocks of 0 (64 divides nothing here: all three warnings)
+SEQ_CASES = {"seqlen_" + rc.CELL_NAMES[cell]: desc(37, 12, 70, 4, cell) for cell in (TANH, LSTM)}
+SEQ_LENGTHS = (4, 1, 3)
+
+
+# ---- the seeded sweep ---------------------------------------------------------------------------------------------------------------
+SWEEP_COUNT = 32
+SWEEP_THREADS = (1, 2, 3, 5)
+CENSUS = ("N > 64", "N odd and > 32", "K > 64", "C > 64", "seq < max_T", "seq == 1 with max_T > 1", "bn does not divide or is 0",
+          "bc does not divide or is 0", "bk does not divide or is 0", "a share begins inside a tile of 64 rows", "more threads than row blocks")
+
+
+def sweep_cases_from(seed):
+    """32 descriptors, 8 per cell, from one block of uniform numbers (one generator call a seed, so that looking for the seed is cheap);
+    per case in this order: N in 1..70; C, then K: one in four from 65..150, else 1..80; max_T in 1..4; seq from {unset, 1..max_T};
+    bn, bc, bk from the forward sweep's list (0, 1, n, the divisors of n from 2, n + 1, 7); threads from 1, 2, 3, 5"""
+    u = np.random.default_rng(seed).random((SWEEP_COUNT, 11))
+    pick = lambda x, seq: seq[min(int(x * len(seq)), len(seq) - 1)]  # noqa: E731
+    extent = lambda wide, x: pick(x, range(65, 151)) if wide < 0.25 else pick(x, range(1, 81))  # noqa: E731
+    blk = lambda x, n: pick(x, [0, 1, n] + [q for q in range(2, n + 1) if n % q == 0] + [n + 1, 7])  # noqa: E731
+    cases = {}
+    for idx in range(SWEEP_COUNT):
+        cell, r = CELLS[idx % 4], [float(v) for v in u[idx]]
+        N, Cc, K, T = pick(r[0], range(1, 71)), extent(r[1], r[2]), extent(r[3], r[4]), pick(r[5], range(1, 5))
+        cases["sweep%02d_%s" % (idx, rc.CELL_NAMES[cell])] = desc(N, Cc, K, T, cell, bn=blk(r[7], N), bc=blk(r[8], Cc), bk=blk(r[9], K),
+                                                                     threads=pick(r[10], SWEEP_THREADS), seq=pick(r[6], [-1] + list(range(1, T + 1))))
+    return cases
+
+
+def census(cases):
+    """per cell, what the sweep is for -> the number of its cases that have it"""
+    n = {cell: dict.fromkeys(CENSUS, 0) for cell in CELLS}
+    for d in cases.values():
+        h, c = rc.Handle(d), n[d["cell"]]
+        shares = [s for s in h.shares() if s[1] > s[0]]
+        c["N > 64"] += d["N"] > 64
+        c["N odd and > 32"] += d["N"] % 2 == 1 and d["N"] > 32
+        c["K > 64"] += d["K"] > 64
+        c["C > 64"] += d["C"] > 64
+        c["seq < max_T"] += 0 <= d["seq"] < d["max_T"]
+        c["seq == 1 with max_T > 1"] += d["seq"] == 1 and d["max_T"] > 1
+        for key, ext in (("bn", "N"), ("bc", "C"), ("bk", "K")):
+            c[key + " does not divide or is 0"] += d[key] == 0 or d[ext] % d[key] != 0
+        c["a share begins inside a tile of 64 rows"] += d["threads"] > 1 and any(s[0] % 64 for s in shares)
+        c["more threads than row blocks"] += d["threads"] > d["N"] // h.bn
+    return n
+
+
+def census_passes(cases):
+    return all(v >= 1 for c in census(cases).values() for v in c.values())
+
+
+# the first seed whose census passes and whose backward pass meets no hard transcendental (tests/test_rnn_bwd_cpu.py asserts both)
+SWEEP_SEED = 41
+# the seeds below SWEEP_SEED whose census passes, each with the transcendental that rules it out: (seed, case, "exp" or "tanh", argument)
+SWEEP_SEEDS_RULED_OUT = ()
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases():
+    return sweep_cases_from(SWEEP_SEED)
 
 
 def captured_cases():
@@ -271,17 +531,27 @@ def read(cell):
     return rc.read(cell) + rc.written(cell) + (("dh", "dcs") if cell == LSTM else ("dh",))
 
 
+def case(name):
+    """the descriptor of any named case that is computed"""
+    for cases in (all_cases(), THREAD_CASES, SEQ_CASES, sweep_cases()):
+        if name in cases:
+            return cases[name]
+    raise KeyError(name)
+
+
 @functools.lru_cache(maxsize=None)
-def expected(name, kind, threads1=True):
-    """(inputs, gradient tensors) of a case under a kind, computed once and left unchanged"""
-    d = dict(all_cases(), **THREAD_CASES)[name]
+def expected(name, kind, threads1=True, seq=None):
+    """(inputs, gradient tensors) of a case under a kind, computed once and left unchanged; seq: another sequence length on the same
+    inputs (the forward tensors of the case's own length, of which a shorter pass reads its first steps)"""
+    d = case(name)
     if threads1:
         d = dict(d, threads=1)
+    if seq is not None:
+        d = dict(d, seq=seq)
     t = cached_inputs(name)
     return t, backward(rc.Handle(d), t, kind)
 
 
 @functools.lru_cache(maxsize=None)
 def cached_inputs(name):
-    d = dict(all_cases(), **THREAD_CASES)[name]
-    return inputs(name, dict(d, threads=1))
+    return inputs(name, dict(case(name), threads=1))

@@ -269,3 +269,102 @@ def test_statuses_on_a_bound_layer(xs, torch_gpu):
         assert 0 == layer.run(rb.BWDUPD)
         layer.check(t, out, rb.BWDUPD)
         layer.close()
+
+
+# ---- the seeded sweep (rnn_bwd_common.sweep_cases) ---------------------------------------------------------------------------------------
+def check_bits(layer, t, out, kind, name):
+    """Layer.check, after a look at what the kind writes that says more where bits differ: whether the result is still inside the
+    float64 contract's bound (then an order of summation differs; else a formula or an address)"""
+    for key in rb.written(layer.d["cell"], kind):
+        got, want = layer.result(key), out[key].reshape(-1)
+        if rc.same_bits(got, want):
+            continue
+        one = rc.Handle(dict(layer.d, threads=1))
+        one.T = layer.h.T  # (the length the handle has now)
+        value, bound = rb.contract64(one, t, kind)[key]
+        part = got.reshape(out[key].shape)
+        part = part[:layer.h.T] if key == "dx" else (part[0] if key in ("dcsp", "dhp") else part)
+        inside = bool(np.all(np.abs(part.astype(np.float64) - value) <= bound))
+        bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
+        pytest.fail("%s %s: %s differs in %d of %d elements (first at %d: %r for %r); the result is %s the float64 contract's bound"
+                    % (name, rb.KIND_NAMES[kind], key, bad.size, want.size, bad[0], got[bad[0]], want[bad[0]], "inside" if inside else "OUTSIDE"))
+    layer.check(t, out, kind)
+
+
+@pytest.mark.parametrize("name", sorted(rb.sweep_cases()))
+def test_seeded_sweep(xs, torch_gpu, name):
+    """BWD, UPD and BWDUPD of a drawn descriptor on one handle, bit for bit against the restatement of one thread: every tensor, the
+    fill of what a kind does not write and of the steps beyond the sequence length, the scratch, the launch count. With threads > 1
+    BWD runs share by share in reverse order (a thread without a share launches nothing), UPD and BWDUPD through thread 0 alone."""
+    d = rb.sweep_cases()[name]
+    layer = Layer(xs, torch_gpu, d, rb.cached_inputs(name))
+    T, per = layer.h.T, lambda kind: rb.launches(d["cell"], kind, layer.h.T)  # noqa: E731
+    shares = layer.h.shares()
+    for kind in rb.KINDS:
+        t, out = rb.expected(name, kind)
+        layer.refill()
+        before = layer.count()
+        if kind == rb.BWD:
+            for tid in reversed(range(d["threads"])):
+                mark = layer.count()
+                assert 0 == layer.run(kind, 0, tid)
+                assert (per(kind) if shares[tid][1] > shares[tid][0] else 0) == layer.count() - mark, tid
+            assert per(kind) * sum(s[1] > s[0] for s in shares) == layer.count() - before
+        else:
+            for tid in reversed(range(1, d["threads"])):
+                assert 0 == layer.run(kind, 0, tid)
+            assert 0 == layer.count() - before
+            assert 0 == layer.run(kind, 0, 0)
+            assert per(kind) == layer.count() - before
+        assert xs.last_kernel().startswith("rnn_bwd_")
+        check_bits(layer, t, out, kind, name)
+        if "dx" in rb.written(d["cell"], kind):
+            dx = layer.result("dx").reshape(d["max_T"], -1)
+            assert np.all(dx[T:].view(np.uint32) == 0xffffffff) and not np.any(dx[:T].view(np.uint32) == 0xffffffff)
+    layer.close()
+
+
+@pytest.mark.parametrize("name", sorted(rb.SEQ_CASES))
+def test_sequence_length_changes_on_one_handle(xs, torch_gpu, name):
+    """BWDUPD at the lengths 4, 1 and 3 on one handle, whose delta buffer keeps the deltas of the longer run before: each result is
+    the restatement's at that length and a fresh handle's, bit for bit -- dw, dr and db sum the steps below the current length only --
+    and dx beyond the current length keeps what the refill put there"""
+    d = rb.SEQ_CASES[name]
+    t = rb.cached_inputs(name)
+    layer = Layer(xs, torch_gpu, d, t)
+    for length in rb.SEQ_LENGTHS:
+        _, out = rb.expected(name, rb.BWDUPD, True, length)
+        assert 0 == layer.L.libxsmm_dnn_rnncell_set_sequence_length(layer.handle, length)
+        layer.refill()
+        before = layer.count()
+        assert 0 == layer.run(rb.BWDUPD)
+        assert rb.launches(d["cell"], rb.BWDUPD, length) == layer.count() - before
+        layer.h.T = length
+        check_bits(layer, t, out, rb.BWDUPD, "%s at %d" % (name, length))
+        dx = layer.result("dx").reshape(d["max_T"], -1)
+        assert np.all(dx[length:].view(np.uint32) == 0xffffffff) and not np.any(dx[:length].view(np.uint32) == 0xffffffff)
+        fresh = Layer(xs, torch_gpu, dict(d, seq=length), t)
+        assert 0 == fresh.run(rb.BWDUPD)
+        for key in rb.GRADS:
+            assert layer.result(key).tobytes() == fresh.result(key).tobytes(), (length, key)
+        fresh.close()
+    layer.close()
+
+
+@pytest.mark.parametrize("name", sorted(rb.SEQ_CASES))
+def test_forward_then_backward_on_one_handle(xs, torch_gpu, name):
+    """FWD on the GPU into zeroed h, gates and z, then BWDUPD on the same handle and tensors (the internal state and the scratch were
+    bound for BWDUPD): the forward tensors and the gradients are the restatement's, bit for bit"""
+    d = rb.SEQ_CASES[name]
+    t, out = rb.expected(name, rb.BWDUPD)
+    zeroed = dict(t, **{key: np.zeros_like(t[key]) for key in rc.written(d["cell"])})
+    layer = Layer(xs, torch_gpu, d, zeroed)
+    layer.check(zeroed, out, None)
+    assert 0 == layer.run(rc.FWD)
+    assert xs.last_kernel().startswith("rnn_") and not xs.last_kernel().startswith("rnn_bwd_")
+    layer.check(t, out, None)  # the forward tensors as the restatement has them; no gradient tensor written yet
+    before = layer.count()
+    assert 0 == layer.run(rb.BWDUPD)
+    assert rb.launches(d["cell"], rb.BWDUPD, layer.h.T) == layer.count() - before
+    check_bits(layer, t, out, rb.BWDUPD, name)
+    layer.close()
