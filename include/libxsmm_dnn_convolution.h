@@ -48,6 +48,12 @@
  *   - tid - start_thread < 0 returns _ERR_GENERAL; a logical thread >= desc.threads, or one whose share is empty, returns
  *     _SUCCESS without a launch. FWD with _FUSE_BIAS and no bias bound, and BWD with _OPTION_BWD_NO_FILTER_TRANSPOSE and no
  *     REGULAR_FILTER_TRANS bound, return _ERR_DATA_NOT_BOUND (the reference dereferences NULL).
+ *   - The environment variable LIBXSMM_AMD_CONV_BWD=mfma (read per call) sends BWD to the matrix cores where u == v == 1, the
+ *     matrix cores are not switched off (LIBXSMM_AMD_MFMA, libxsmm_amd_set_mfma) and some pixel of dinput has all its K * R * S
+ *     terms: those pixels -- one rectangle inside the H x W interior, the whole plane for 1 x 1 without padding -- are computed
+ *     as an implicit GEMM, the frame around them and a physical rim as without the variable. The bits do not change; a call is
+ *     then up to two launches and one more per 65535 pixel tiles. LIBXSMM_AMD_CONV_TILE=64|128 forces the tile of FWD and of this
+ *     path. Unset, or in any other case, BWD is what it was (the default for now: DESIGN.md 8n).
  *
  * Threads. Work is N * K/ofmblock items (FWD), N * C/ifmblock (BWD), C/ifmblock * K/ofmblock (UPD), split as in the other layers:
  * logical thread ltid computes [ltid * chunk, min((ltid + 1) * chunk, work)), chunk = ceil(work / desc.threads). No chain crosses a

@@ -23,7 +23,8 @@
 //
 // BWD and UPD run on the vector ALU, one thread per element of dinput / dfilter, because the matrix instruction cannot leave a
 // term out for some of its elements (BWD) and because only C * K * R * S chains are independent (UPD): DESIGN.md 8n says what
-// that costs. Index arithmetic is per thread (a few divisions), the loops add strides.
+// that costs. Index arithmetic is per thread (a few divisions), the loops add strides. With LIBXSMM_AMD_CONV_BWD=mfma and
+// strides of 1 the pixels of dinput that have all their terms go to conv_bwd_mfma.hip and conv_bwd keeps the frame around them.
 //
 // Bounds. Every address is formed from indices that were compared against their extents first; an element outside its tile's
 // valid part, outside the share [w0, w1) or (FWD, logical padding) outside the input plane reads element 0 of its tensor and
@@ -193,6 +194,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_bwd(const ConvArgs g)
   if (item >= g.w1 || e >= (long long)ph * pw * g.ifmblock) return;
   const int pix = (int)(e / g.ifmblock), ifm2 = (int)(e - (long long)pix * g.ifmblock);
   const int by = pix / pw, bx = pix - by * pw; // in the buffer
+  if (by >= g.fy0 && by < g.fy1 && bx >= g.fx0 && bx < g.fx1) return; // conv_bwd_mfma.hip computes the full rectangle (empty: all zero)
   const int img = (int)(item / g.blocksifm), ifm1 = (int)(item - (long long)img * g.blocksifm);
   float* __restrict__ const din = static_cast<float*>(g.in);
   const float* __restrict__ const dout = static_cast<const float*>(g.out);
@@ -322,13 +324,21 @@ int launch_conv_fwd(const ConvArgs& g, void* stream, const char** name)
   return 128 == g.tile ? launch_fwd<128>(g, stream, *name) : launch_fwd<64>(g, stream, *name);
 }
 
-int launch_conv_bwd(const ConvArgs& g, void* stream, const char** name)
+int launch_conv_bwd(const ConvArgs& args, void* stream, const char** name)
 {
   *name = "conv_bwd";
+  ConvArgs g = args;
+  const bool mfma = conv_bwd_full_rect(&g); // LIBXSMM_AMD_CONV_BWD=mfma at stride 1: the pixels that have all their terms
+  const bool frame = !(mfma && 0 == g.fy0 && 0 == g.fx0 && g.ifhp == g.fy1 && g.ifwp == g.fx1);
   dim3 grid;
   if (!item_grid((long long)g.ifhp * g.ifwp * g.ifmblock, (long long)g.w1 - g.w0, &grid)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(conv_bwd, grid, dim3(NTHREADS), 0, (hipStream_t)stream, g);
-  return (int)hipGetLastError();
+  if (frame) { // everything, or what lies around the rectangle
+    hipLaunchKernelGGL(conv_bwd, grid, dim3(NTHREADS), 0, (hipStream_t)stream, g);
+    const int e = (int)hipGetLastError();
+    if (!mfma || 0 != e) return e;
+    note_launch(*name); // (the caller counts the last launch of the pass)
+  }
+  return launch_conv_bwd_mfma(g, stream, name); // disjoint elements, the same stream
 }
 
 int launch_conv_upd(const ConvArgs& g, void* stream, const char** name)

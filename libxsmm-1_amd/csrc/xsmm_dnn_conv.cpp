@@ -1,6 +1,6 @@
 // xsmm_dnn_conv.cpp -- the convolution layer (include/libxsmm_dnn_convolution.h): handle, layouts, scratch and tensor binding as
 // in the reference's generic path, and libxsmm_dnn_execute_st as one launch of kernels/conv.hip per call (FWD: one per slab of
-// 65535 pixel tiles).
+// 65535 pixel tiles; BWD with LIBXSMM_AMD_CONV_BWD=mfma: conv_bwd for the frame, then kernels/conv_bwd_mfma.hip slab by slab).
 //
 // Reference: src/libxsmm_dnn.c (create :191-308, layouts :363-997, trans_reg_filter :1571-1604, binding :1607-1717, scratch
 // :1720-2097, execute :2100-2235, the helpers :2238-2391), src/libxsmm_dnn_handle.c:61-167 (the scratch sizes of the generic path),
@@ -64,8 +64,8 @@ bool known_kind(libxsmm_dnn_compute_kind k)
   return LIBXSMM_DNN_COMPUTE_KIND_FWD == k || LIBXSMM_DNN_COMPUTE_KIND_BWD == k || LIBXSMM_DNN_COMPUTE_KIND_UPD == k || LIBXSMM_DNN_COMPUTE_KIND_ALL == k;
 }
 
-int tile_for(const libxsmm_dnn_layer* h, long long pixels)
-{
+int tile_for(int rows, long long pixels)
+{ // rows: K (FWD), C (BWD on the matrix cores)
   // LIBXSMM_AMD_CONV_TILE=64 / 128 forces a tile (read per call: tests and the benchmark compare both). Otherwise the rule of the
   // fully-connected layer: the largest tile that still gives every compute unit a work-group (no measurement stands behind it).
   const char* const e = getenv("LIBXSMM_AMD_CONV_TILE");
@@ -75,8 +75,8 @@ int tile_for(const libxsmm_dnn_layer* h, long long pixels)
     if (hipSuccess != hipGetDevice(&dev) || hipSuccess != hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev)) { (void)hipGetLastError(); n = 0; }
     return 0 < n ? n : 256;
   }();
-  const long long big = (((long long)h->desc.K + 127) / 128) * ((pixels + 127) / 128);
-  return (h->desc.K > 64 && big >= cus) ? 128 : 64;
+  const long long big = (((long long)rows + 127) / 128) * ((pixels + 127) / 128);
+  return (rows > 64 && big >= cus) ? 128 : 64;
 }
 
 void fill_args(const libxsmm_dnn_layer* h, ConvArgs* g)
@@ -281,10 +281,14 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_execute_st(libxsmm_dnn_layer* h, libxs
   int e;
   if (fwd) {
     g.bias_on = bias ? 1 : 0; g.relu = (0 != (d.fuse_ops & LIBXSMM_DNN_CONV_FUSE_RELU)) ? 1 : 0;
-    g.tile = tile_for(h, (long long)(b1 - 1 - b0 + h->blocksofm) / h->blocksofm * h->ofh * h->ofw);
+    g.tile = tile_for(d.K, (long long)(b1 - 1 - b0 + h->blocksofm) / h->blocksofm * h->ofh * h->ofw);
     e = launch_conv_fwd(g, stream, &name);
   }
-  else if (bwd) { g.flt_trans = trans ? 1 : 0; e = launch_conv_bwd(g, stream, &name); }
+  else if (bwd) { // (the tile is that of the matrix-core path, LIBXSMM_AMD_CONV_BWD=mfma: FWD's rule over the interior's pixels)
+    g.flt_trans = trans ? 1 : 0;
+    g.tile = tile_for(d.C, (long long)(b1 - 1 - b0 + h->blocksifm) / h->blocksifm * d.H * d.W);
+    e = launch_conv_bwd(g, stream, &name);
+  }
   else { // upd template :91-92
     const bool physical = (0 == g.logical);
     g.per_image = ((1 == d.R && 1 == d.S && physical) || (1 == d.u && 1 == d.v)) ? 0 : 1;

@@ -60,7 +60,9 @@ struct ConvArgs {
   int overwrite, bias_on, relu;           // OPTION_OVERWRITE; FWD: FUSE_BIAS, fuse_ops & FUSE_RELU
   int flt_trans;                          // BWD: flt is REGULAR_FILTER_TRANS
   int per_image;                          // UPD: the form with one chain per image and ordered adds
-  int tile;                               // FWD: 64 or 128
+  int tile;                               // FWD, BWD on the matrix cores: 64 or 128
+  int fy0, fy1, fx0, fx1;                 // BWD: the pixels that have all their terms, rows [fy0, fy1) x columns [fx0, fx1) of the dinput
+                                          // buffer, which kernels/conv_bwd_mfma.hip computes and conv_bwd skips; all zero: none
 };
 // one pass over the share, or the transposition of the whole filter (in: REGULAR_FILTER, out: REGULAR_FILTER_TRANS in g.flt / g.out);
 // each returns hipError_t as int
@@ -68,6 +70,10 @@ int launch_conv_fwd(const ConvArgs& args, void* stream, const char** name);
 int launch_conv_bwd(const ConvArgs& args, void* stream, const char** name);
 int launch_conv_upd(const ConvArgs& args, void* stream, const char** name);
 int launch_conv_trans_filter(const ConvArgs& args, void* stream, const char** name);
+// BWD on the matrix cores (kernels/conv_bwd_mfma.hip): the rectangle of args, filled if LIBXSMM_AMD_CONV_BWD=mfma asks for the path, the
+// strides are 1, the matrix cores are not switched off and the rectangle is not empty (else false, args untouched); its launch
+bool conv_bwd_full_rect(ConvArgs* args);
+int launch_conv_bwd_mfma(const ConvArgs& args, void* stream, const char** name);
 
 // RNN cell layer (xsmm_dnn_rnn.cpp, kernels/rnn.hip): one launch computes, for the rows [n0, n1) of the minibatch and all K outputs,
 // G accumulator sets (gates) of one step -- or, with nz > 1, of nz steps whose operands lie zx / zo elements apart

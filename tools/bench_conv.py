@@ -9,7 +9,9 @@ size -- the ceiling of this engine's fp32 arithmetic, without the gather a convo
 64 -> 256 on 56 x 56; 3x3 128 -> 128 on 28 x 28, pad 1; 3x3 / 2 128 -> 128 on 56 x 56, pad 1; 7x7 / 2 3 -> 64 on 224 x 224, pad 3.
 Every case is warmed up twice, then timed event to event in five windows of as many calls as fill about 40 ms (3 ... 50); the
 median window is reported with the spread. FLOP: 2 * N * K * C * R * S * ofh * ofw per pass. No gate.
-Usage: tools/bench_conv.py [--out FILE] [--quick]"""
+At stride 1 BWD is timed twice: as it is by default (conv_bwd alone) and with LIBXSMM_AMD_CONV_BWD=mfma (kernels/conv_bwd_mfma.hip
+for the pixels that have all their terms, conv_bwd for the frame); --bwd keeps those two rows of the stride-1 shapes only.
+Usage: tools/bench_conv.py [--out FILE] [--quick] [--bwd]"""
 import argparse
 import importlib
 import os
@@ -53,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_bench.txt"))
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--bwd", action="store_true")
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -61,7 +64,7 @@ def main():
     torch.cuda.set_device(0)
     lines = ["# tools/bench_conv.py: ms per pass, median of five windows (min ... max), event to event, warm; N = %d, fp32, threads = 1" % N,
              "# yardsticks: torch (conv2d, nn.grad.conv2d_input, nn.grad.conv2d_weight on plain NCHW fp32) and libxsmm_sgemm_omp of the equivalent GEMM (the engine's ceiling)"]
-    for s in (SHAPES[1:2] if args.quick else SHAPES):
+    for s in (SHAPES[1:2] if args.quick else (SHAPES[:2] if args.bwd else SHAPES)):
         C_, K, H, W, R, S, u, pad = (s[k] for k in ("C", "K", "H", "W", "R", "S", "u", "pad"))
         ofh, ofw = (H + 2 * pad - R) // u + 1, (W + 2 * pad - S) // u + 1
         flop = 2.0 * N * K * C_ * R * S * ofh * ofw
@@ -86,16 +89,20 @@ def main():
         gemm = {FWD: lambda: xs.xgemm_omp(xs.F32, "N", "N", m, n, k, 1.0, ga, m, gb, k, 0.0, gc, m),
                 BWD: lambda: xs.xgemm_omp(xs.F32, "T", "N", k, n, m, 1.0, ga, m, gb, m, 0.0, gc, k),
                 UPD: lambda: xs.xgemm_omp(xs.F32, "N", "T", m, k, n, 1.0, gb, m, gc, k, 0.0, ga, m)}
-        for kind, name in ((FWD, "fwd"), (BWD, "bwd"), (UPD, "upd")):
+        rows = [(FWD, "fwd", None), (BWD, "bwd", None)] + ([(BWD, "bwd", "mfma")] if 1 == u else []) + [(UPD, "upd", None)]
+        for kind, name, bwd_path in (r for r in rows if BWD == r[0] or not args.bwd):
+            if bwd_path:  # (read per call)
+                os.environ["LIBXSMM_AMD_CONV_BWD"] = bwd_path
             mine = timed(torch, lambda: xs.conv_execute(handle, kind))
             kernel = xs.last_kernel()
+            os.environ.pop("LIBXSMM_AMD_CONV_BWD", None)
             try:
                 theirs = timed(torch, ref[kind])
             except Exception as e:  # (a torch build without a convolution for this shape)
                 theirs = None
                 lines.append("# torch %s failed: %s" % (name, str(e).splitlines()[0][:120]))
             ceiling = timed(torch, gemm[kind])
-            lines.append("C=%-3d K=%-3d %3dx%-3d %dx%d/%d %s %-14s %s  %6.2f TFLOP/s | torch %s | sgemm_omp %dx%dx%d %s  %6.2f TFLOP/s"
+            lines.append("C=%-3d K=%-3d %3dx%-3d %dx%d/%d %s %-18s %s  %6.2f TFLOP/s | torch %s | sgemm_omp %dx%dx%d %s  %6.2f TFLOP/s"
                          % (C_, K, H, W, R, S, u, name, kernel, fmt(mine), flop / mine[0] * 1e-9, fmt(theirs), m, n, k, fmt(ceiling), flop / ceiling[0] * 1e-9))
         for t in tensors:
             L.libxsmm_dnn_destroy_tensor(t)
