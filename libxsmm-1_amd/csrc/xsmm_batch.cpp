@@ -11,8 +11,6 @@
 
 namespace xsmm {
 
-void launch_failed(const char* name, int hip_error) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, hip_error); }
-
 Residency classify(const void* a, const void* b, const void* c)
 { // (in turn, and only while all so far are GPU-reachable)
   Residency r = { pointer_kind(a), 0, 0 };
@@ -29,9 +27,8 @@ int run_smm(const SmmBatch& s, int host_visible)
   if (e < 0) e = launch_smm_jit(s, device().stream, &name);                         // shape-specialised via hiprtc (SYNC_DEVICE: whatever the verdict on the device, one of its kernels works)
   if (e < 0) e = launch_smm_generic(s, device().stream, &name);                     // any descriptor
   if (SYNC_DEVICE == s.sync) flag_slot_commit(); // the launches that read the verdict are queued
-  note_launch(name);
-  if (0 != e) launch_failed(name, e);
-  else if (0 <= host_visible) { if (0 != host_visible) (void)stream_sync(); }
+  if (!launched(name, e)) return e;
+  if (0 <= host_visible) { if (0 != host_visible) (void)stream_sync(); }
   else if (ADDR_POINTER != s.mode) settle(s.a, s.b, s.c);
   else if (is_host_visible(s.a) && is_host_visible(s.b) && is_host_visible(s.c)) { // arrays of pointers the CPU reads: look at the first operands
     settle(*static_cast<const void* const*>(s.a), *static_cast<const void* const*>(s.b), *static_cast<void* const*>(s.c));
@@ -167,7 +164,7 @@ int run_groups(std::vector<SmmBatch>& groups)
       if (!ok) { flag_slot_commit(); wanted.clear(); return -1; }
       const char* name = "";
       int e = launch_smm_jit_grouped(g, n, device().stream, &name);
-      if (0 <= e) { note_launch(name); if (0 != e) { launch_failed(name, e); result = e; } }
+      if (0 <= e) { if (!launched(name, e)) result = e; }
       else { // batch by batch (each reads its verdict slot)
         for (int i = 0; i < n; ++i) { e = run_smm(g[i]); if (0 != e) result = e; }
       }
@@ -212,7 +209,7 @@ bool upload_pointer_arrays(SmmBatch& s, void* stream, const void* a, size_t na, 
 bool stage_in(const void* const host[3], const size_t bytes[3], char* dev[3])
 {
   for (int o = 0; o < 3; ++o) {
-    dev[o] = (nullptr != host[o] ? static_cast<char*>(scratch(3 + o, bytes[o])) : nullptr);
+    dev[o] = (nullptr != host[o] ? static_cast<char*>(scratch(ScratchSlot(SLOT_A + o), bytes[o])) : nullptr);
     if (nullptr != host[o] && nullptr == dev[o]) return false;
   }
   for (int o = 0; o < 3; ++o) if (nullptr != host[o] && 0 != h2d(dev[o], host[o], bytes[o])) return false;
@@ -307,7 +304,7 @@ int batch_execute(SmmBatch s, libxsmm_blasint index_base, libxsmm_blasint index_
   for (size_t i = 0; i < na; ++i) ta[i] = dev[0] + i * sza;
   for (size_t i = 0; i < nb; ++i) tb[i] = dev[1] + i * szb;
   for (size_t i = 0; i < nc; ++i) tc[i] = dev[2] + slot_of[i] * szc;
-  void* const xa = scratch(0, na * sizeof(void*)); void* const xb = scratch(1, nb * sizeof(void*)); void* const xc = scratch(2, nc * sizeof(void*));
+  void* const xa = scratch(SLOT_IN0, na * sizeof(void*)); void* const xb = scratch(SLOT_IN1, nb * sizeof(void*)); void* const xc = scratch(SLOT_RESULTS, nc * sizeof(void*));
   if (nullptr == xa || nullptr == xb || nullptr == xc) return EXIT_FAILURE;
   if (0 != h2d(xa, ta.data(), na * sizeof(void*)) || 0 != h2d(xb, tb.data(), nb * sizeof(void*)) || 0 != h2d(xc, tc.data(), nc * sizeof(void*))) return EXIT_FAILURE;
   if (0 != stream_sync()) return EXIT_FAILURE;

@@ -157,7 +157,7 @@ void batch_flush_record()
   if (!dev.empty()) {
     constexpr size_t TABLE = 2 * 3 * BATCH_HULL_CALLS, TABLES = (MERGE_MAX_CALLS + BATCH_HULL_CALLS - 1) / BATCH_HULL_CALLS;
     // (a capture that began with the record open: nothing may be waited for -- the calls run one after the other)
-    unsigned long long* const d_hulls = defer_capturing(stream) ? nullptr : static_cast<unsigned long long*>(scratch(7, TABLES * TABLE * sizeof(unsigned long long)));
+    unsigned long long* const d_hulls = defer_capturing(stream) ? nullptr : static_cast<unsigned long long*>(scratch(SLOT_HULLS, TABLES * TABLE * sizeof(unsigned long long)));
     r.table.resize(TABLES * TABLE);
     hulls_ok = (nullptr != d_hulls);
     size_t tables = 0;

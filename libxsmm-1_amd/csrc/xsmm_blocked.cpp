@@ -117,16 +117,13 @@ int bgemm_copy(const libxsmm_blocked_gemm_handle* h, int which, const void* src,
   const size_t plain = ((size_t)(cols - 1) * ldv + rows) * h->typesize, blocked = (size_t)rows * cols * h->typesize;
   const bool out = (3 == which);
   const size_t src_bytes = out ? blocked : plain, dst_bytes = out ? plain : blocked;
-  const void* ds = src; void* dd = dst;
-  const bool src_host = !is_device_ptr(src), dst_host = !is_device_ptr(dst);
-  if (src_host) { void* t = scratch(3, src_bytes); if (nullptr == t || 0 != h2d(t, src, src_bytes)) return EXIT_FAILURE; ds = t; }
-  if (dst_host) { void* t = scratch(4, dst_bytes); if (nullptr == t) return EXIT_FAILURE; if (out && ldv != rows && 0 != h2d(t, dst, dst_bytes)) return EXIT_FAILURE; dd = t; }
-  const int e = launch_bgemm_copy(g, which, ds, ldv, dd, device().stream); note_launch("bgemm_copy");
+  Staged s; // (a plain destination with a pitch keeps what lies between its columns)
+  const Operand* const os = s.in(src, src_bytes, SLOT_A);
+  const Operand* const od = s.out(dst, dst_bytes, SLOT_B, out && ldv != rows);
+  if (!s.place()) return EXIT_FAILURE;
+  const int e = launch_bgemm_copy(g, which, os->dev, ldv, od->dev, device().stream); note_launch("bgemm_copy");
   if (0 != e) return EXIT_FAILURE;
-  if (dst_host) return 0 == d2h(dst, dd, dst_bytes) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (src_host) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  settle(src, dst);
-  return EXIT_SUCCESS;
+  return s.finish(WAIT_OPERANDS, { od }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 }
 
@@ -143,16 +140,13 @@ int bgemm_permute(const libxsmm_blocked_gemm_handle* h, int which, const void* s
   if (!device_ready()) { fail_no_device("libxsmm_blocked_gemm_convert/transpose"); return EXIT_FAILURE; }
   BgemmGeom g; g.typesize = h->typesize; g.m = h->m; g.n = h->n; g.k = h->k; g.bm = h->bm; g.bn = h->bn; g.bk = h->bk; g.mb = h->mb; g.nb = h->nb; g.kb = h->kb;
   const size_t bytes = (size_t)(4 == which ? (size_t)h->m * h->n : (size_t)h->k * h->n) * h->typesize;
-  const void* ds = src; void* dd = dst;
-  const bool src_host = !is_device_ptr(src), dst_host = !is_device_ptr(dst);
-  if (src_host) { void* t = scratch(3, bytes); if (nullptr == t || 0 != h2d(t, src, bytes)) return EXIT_FAILURE; ds = t; }
-  if (dst_host) { void* t = scratch(4, bytes); if (nullptr == t) return EXIT_FAILURE; dd = t; }
-  const int e = launch_bgemm_copy(g, which, ds, 0, dd, device().stream); note_launch(4 == which ? "bgemm_convert_b_to_a" : "bgemm_transpose_b");
+  Staged s;
+  const Operand* const os = s.in(src, bytes, SLOT_A);
+  const Operand* const od = s.out(dst, bytes, SLOT_B, false);
+  if (!s.place()) return EXIT_FAILURE;
+  const int e = launch_bgemm_copy(g, which, os->dev, 0, od->dev, device().stream); note_launch(4 == which ? "bgemm_convert_b_to_a" : "bgemm_transpose_b");
   if (0 != e) return EXIT_FAILURE;
-  if (dst_host) return 0 == d2h(dst, dd, bytes) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (src_host) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  settle(src, dst);
-  return EXIT_SUCCESS;
+  return s.finish(WAIT_OPERANDS, { od }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 }
 
@@ -170,11 +164,12 @@ void bgemm_run(const libxsmm_blocked_gemm_handle* h, const void* a, const void* 
   if (!device_ready()) { fail_no_device("libxsmm_blocked_gemm"); return; }
   const int ts = h->typesize;
   const size_t ea = (size_t)h->m * h->k * ts, eb = (size_t)h->k * h->n * ts, ec = (size_t)h->m * h->n * ts;
-  const void* da = a; const void* db = b; void* dc = c;
-  const bool c_host = !is_device_ptr(c);
-  if (!is_device_ptr(a)) { void* t = scratch(3, ea); if (nullptr == t || 0 != h2d(t, a, ea)) return; da = t; }
-  if (!is_device_ptr(b)) { void* t = scratch(4, eb); if (nullptr == t || 0 != h2d(t, b, eb)) return; db = t; }
-  if (c_host) { void* t = scratch(5, ec); if (nullptr == t || 0 != h2d(t, c, ec)) return; dc = t; }
+  Staged st;
+  const Operand* const oa = st.in(a, ea, SLOT_A);
+  const Operand* const ob = st.in(b, eb, SLOT_B);
+  const Operand* const oc = st.out(c, ec, SLOT_C, true);
+  if (!st.place()) return;
+  const void* const da = oa->dev; const void* const db = ob->dev; void* const dc = oc->dev;
   SmmBatch s; memset(&s, 0, sizeof(s));
   s.typesize = ts; s.m = h->bm; s.n = h->bn; s.k = h->bk; s.lda = h->bm; s.ldb = h->bk; s.ldc = h->bm;
   s.flags = 0; // C blocks always accumulate (tpl :101,149: real_c += l_out)
@@ -199,11 +194,7 @@ void bgemm_run(const libxsmm_blocked_gemm_handle* h, const void* a, const void* 
     flag_slot_commit();
   }
   if (e < 0) e = launch_smm_generic(s, device().stream, &name);
-  note_launch(name);
-  if (0 != e) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e); return; }
-  if (c_host) (void)d2h(c, dc, ec);
-  else if (da != a || db != b) (void)stream_sync();
-  else settle(a, b, c);
+  if (launched(name, e)) (void)st.finish(WAIT_OPERANDS, { oc });
 }
 }
 

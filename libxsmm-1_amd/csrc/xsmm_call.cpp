@@ -36,8 +36,7 @@ int lowp_launch(const SmmBatch& s)
   const char* name = "";
   int e = launch_smm_jit(s, device().stream, &name); // large strided batches of small tight items: specialised streaming form
   if (e < 0) e = launch_smm_lowp(s, device().stream, &name);
-  note_launch(name);
-  if (0 != e) launch_failed(name, e);
+  (void)launched(name, e);
   return e;
 }
 
@@ -124,10 +123,9 @@ void call_kernel(Kernel* k, const void* a, const void* b, void* c, const void* x
       return;
     }
     const char* name = "";
-    const int e = launch_smm_lowp_reduce(s, device().stream, &name); note_launch(name);
+    const int e = launch_smm_lowp_reduce(s, device().stream, &name);
     index_upload_commit();
-    if (0 != e) launch_failed(name, e);
-    else if (0 != (kc & 2)) (void)stream_sync();
+    if (launched(name, e) && 0 != (kc & 2)) (void)stream_sync();
     return;
   }
   if (KC_LOWP == k->kclass) { // i16 -> f32 kernels are called as kernel(a, b, c, pa, pb, pc, &scf) (samples/xgemm/kernel.c:262)
@@ -172,8 +170,8 @@ void call_kernel(Kernel* k, const void* a, const void* b, void* c, const void* x
     auto launch = [&](const void* pb, void* pc) {
       const char* name = "";
       p.b = pb; p.c = pc;
-      const int e = launch_csr_panels(p, device().stream, &name); note_launch(name);
-      if (0 != e) launch_failed(name, e);
+      const int e = launch_csr_panels(p, device().stream, &name);
+      (void)launched(name, e);
       return e;
     };
     const int kb = pointer_kind(b), kc = (0 != (kb & 1) ? pointer_kind(c) : 0);

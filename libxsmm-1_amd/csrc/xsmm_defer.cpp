@@ -220,13 +220,8 @@ template<typename Launch> bool open_burst(Ring& r, int first, Launch launch)
   bool ok = (0 == launch_defer_gate(reinterpret_cast<unsigned long long*>(sl.word), sl.count, dev.stream));
   if (ok) {
     const char* name = "";
-    const int e = launch(sl, dev.stream, &name);
-    if (0 != e) { // (the gate is queued already: let it through with nothing recorded)
-      sl.word->store(SEALED, std::memory_order_release);
-      fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-      ok = false;
-    }
-    else note_launch(name);
+    ok = queued(name, launch(sl, dev.stream, &name));
+    if (!ok) sl.word->store(SEALED, std::memory_order_release); // (the gate is queued already: let it through with nothing recorded)
   }
   if (!ok) { record_flush(); return false; }
   if (hipSuccess == hipEventRecord(sl.done, (hipStream_t)dev.stream)) sl.pending = true; else (void)hipGetLastError();

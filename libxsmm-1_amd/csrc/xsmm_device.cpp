@@ -20,7 +20,7 @@ std::atomic<unsigned long long> g_launches{0};
 thread_local const char* tl_last_kernel = "";
 
 struct Scratch { void* ptr = nullptr; size_t size = 0; void* stream = nullptr; bool used = false; };
-thread_local Scratch tl_scratch[16];
+thread_local Scratch tl_scratch[SLOT_COUNT];
 }
 
 // The engine's current stream is a per-thread setting (every entry point may be called from any thread, as in the
@@ -58,26 +58,6 @@ int pointer_kind(const void* p)
   return (reach ? 1 : 0) | (host ? 2 : 0);
 }
 
-bool is_device_ptr(const void* p)
-{
-  if (nullptr == p || !device_ready()) return false;
-  hipPointerAttribute_t attr;
-  memset(&attr, 0, sizeof(attr));
-  const hipError_t e = hipPointerGetAttributes(&attr, p);
-  if (hipSuccess != e) { (void)hipGetLastError(); return false; } // plain host memory on older runtimes
-  return hipMemoryTypeDevice == attr.type || hipMemoryTypeManaged == attr.type || hipMemoryTypeHost == attr.type
-      || hipMemoryTypeArray == attr.type;
-}
-
-bool is_host_visible(const void* p)
-{ // pinned host memory (libxsmm_malloc, hipHostMalloc) and managed memory: the GPU works on it in place, the CPU may read it
-  if (nullptr == p || !device_ready()) return false;
-  hipPointerAttribute_t attr;
-  memset(&attr, 0, sizeof(attr));
-  if (hipSuccess != hipPointerGetAttributes(&attr, p)) { (void)hipGetLastError(); return false; }
-  return hipMemoryTypeHost == attr.type || hipMemoryTypeManaged == attr.type;
-}
-
 void settle(const void* p0, const void* p1, const void* p2)
 { // Work on device memory stays asynchronous (the caller needs a copy or a synchronisation to touch it anyway). Operands
   // in memory the CPU addresses directly (libxsmm_malloc / pinned / managed) must be done with when the call returns: an
@@ -107,6 +87,17 @@ int d2h(void* dst, const void* src, size_t bytes)
   hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)device().stream);
   if (hipSuccess == e) e = hipStreamSynchronize((hipStream_t)device().stream);
   return (int)e;
+}
+
+int d2h_async(void* dst, const void* src, size_t bytes)
+{
+  if (0 == bytes) return 0;
+  return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)device().stream);
+}
+
+int copy2d(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t row_bytes, size_t rows, bool to_device)
+{
+  return (int)hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, row_bytes, rows, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, (hipStream_t)device().stream);
 }
 
 int stream_sync() { return (int)hipStreamSynchronize((hipStream_t)device().stream); }
@@ -316,9 +307,9 @@ void index_upload_commit()
   }
 }
 
-void* scratch(int slot, size_t bytes)
+void* scratch(ScratchSlot slot, size_t bytes)
 {
-  Scratch& s = tl_scratch[slot & 15];
+  Scratch& s = tl_scratch[slot];
   // Launches are asynchronous: whatever was queued on the stream that used this buffer last may still be reading it.
   // (Scratch only serves the staging of host-resident operands -- the compatibility path -- so the wait costs nothing
   // on the device-resident path.)

@@ -345,7 +345,7 @@ const DnnCopyGeom& geom_of(const CopyShape& c)
 }
 
 // The copy on the GPU: at least one operand is plain device memory (or the form is the one that does not wait). An operand in
-// pageable memory travels through scratch slot 0 -- only one can, the other is device memory. Nothing waits before the launch:
+// pageable memory travels through SLOT_IN0 -- only one can, the other is device memory. Nothing waits before the launch:
 // the stream orders the copy behind what was queued before. wait: complete on return.
 libxsmm_dnn_err_t copy_on_device(const CopyShape& c, void* tensor_data, int kind_tensor, void* plain, int kind_plain, size_t bytes, bool in, bool wait)
 {
@@ -355,11 +355,11 @@ libxsmm_dnn_err_t copy_on_device(const CopyShape& c, void* tensor_data, int kind
   void* const dst = in ? tensor_data : plain;
   void* dsrc = src; void* ddst = dst;
   if (0 == ((in ? kind_plain : kind_tensor) & 1)) {
-    dsrc = scratch(0, bytes);
+    dsrc = scratch(SLOT_IN0, bytes);
     if (nullptr == dsrc || 0 != h2d(dsrc, src, bytes)) return LIBXSMM_DNN_ERR_GENERAL;
   }
   else if (0 == ((in ? kind_tensor : kind_plain) & 1)) { // (every element is written: nothing travels to the device first)
-    ddst = scratch(0, bytes);
+    ddst = scratch(SLOT_IN0, bytes);
     if (nullptr == ddst) return LIBXSMM_DNN_ERR_GENERAL;
   }
   const char* name = "dnn_copy";

@@ -239,7 +239,7 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fusedbatchnorm_execute_st(libxsmm_dnn_
   }
   // what the pass wrote travels back if it was staged
   bool ok;
-  if (!bwd) ok = stats ? s.finish({ oout, omean, orstd, ovar }) : s.finish({ oout });
-  else ok = stats ? s.finish({ odin, odgamma, odbeta, relu ? odout : nullptr, eltwise ? oadd : nullptr }) : s.finish({ odin });
+  if (!bwd) ok = stats ? s.finish(WAIT_OPERANDS, { oout, omean, orstd, ovar }) : s.finish(WAIT_OPERANDS, { oout });
+  else ok = stats ? s.finish(WAIT_OPERANDS, { odin, odgamma, odbeta, relu ? odout : nullptr, eltwise ? oadd : nullptr }) : s.finish(WAIT_OPERANDS, { odin });
   return ok ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

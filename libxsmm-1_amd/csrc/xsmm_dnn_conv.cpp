@@ -295,7 +295,7 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_execute_st(libxsmm_dnn_layer* h, libxs
     e = launch_conv_upd(g, stream, &name);
   }
   if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
-  const bool ok = fwd ? s.finish({ oo }) : (bwd ? s.finish({ oi }) : s.finish({ of }));
+  const bool ok = fwd ? s.finish(WAIT_OPERANDS, { oo }) : (bwd ? s.finish(WAIT_OPERANDS, { oi }) : s.finish(WAIT_OPERANDS, { of }));
   return ok ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }
 
@@ -323,7 +323,7 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_trans_reg_filter(const libxsmm_dnn_lay
   const char* name = "";
   const int e = launch_conv_trans_filter(g, stream, &name);
   if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
-  return s.finish({ ot }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
+  return s.finish(WAIT_OPERANDS, { ot }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }
 
 LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_transpose_filter(libxsmm_dnn_layer* h, const libxsmm_dnn_tensor_type type)

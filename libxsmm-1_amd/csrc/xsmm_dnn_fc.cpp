@@ -321,5 +321,5 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_fullyconnected_execute_st(libxsmm_dnn_
   const char* name = "";
   const int e = launch_fc(g, stream, &name);
   if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
-  return s.finish({ od }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
+  return s.finish(WAIT_OPERANDS, { od }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

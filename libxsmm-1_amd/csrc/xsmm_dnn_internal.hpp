@@ -8,8 +8,6 @@
 #include "../../include/libxsmm_dnn.h"
 #include "kernels/dnn_copy_plan.h"
 
-#include <initializer_list>
-
 struct libxsmm_dnn_tensor { // src/libxsmm_main.h:339-343
   libxsmm_dnn_tensor_datalayout* layout;
   void* data;
@@ -155,21 +153,10 @@ bool activation_layout(libxsmm_dnn_tensor_datalayout* l, libxsmm_dnn_tensor_form
 // (ltid >= threads included). threads >= 1, ltid >= 0.
 bool thread_share(long long work, int threads, int ltid, long long* b0, long long* b1);
 
-// The tensors of a pass where the kernels can reach them. Those in pageable host memory share one block of device scratch
-// (slot 6 of the calling thread), carved up at 256-byte offsets in the order in which they are asked for, and are uploaded.
-struct Operand { void* dev; void* host; size_t bytes; size_t offset; }; // host: nullptr unless staged
-struct Staging {
-  Operand op[24]; int n = 0; size_t total = 0; bool wait = false;
-  const Operand* add(const libxsmm_dnn_tensor* t); // (dev is valid after place)
-  bool place();                                    // false: no memory, or a copy failed
-  // after the launches: the staged ones of the operands the pass wrote (nullptr: skipped) travel back, and the stream is idle on
-  // return if anything was staged or is host-visible; false: a copy or the wait failed
-  bool finish(std::initializer_list<const Operand*> written);
-};
-inline void* dev_of(const Operand* o) { return nullptr != o ? o->dev : nullptr; }
+// The tensors of a pass where the kernels can reach them (Staged, xsmm_internal.hpp): those in pageable host memory share the
+// block of SLOT_BLOCK and are uploaded.
+struct Staging : Staged { const Operand* add(const libxsmm_dnn_tensor* t); };
 inline bool aligned16(const Operand* o) { return 0 == reinterpret_cast<uintptr_t>(dev_of(o)) % 16; }
-
-bool launched(const char* name, int hip_error); // counts the launch; false: it failed (and says so on stderr)
 
 template<typename H> size_t scratch_size_of(const H* h, libxsmm_dnn_err_t* status)
 { // (64 bytes more for a caller that does not align)

@@ -1,6 +1,6 @@
 // xsmm_dnn_layer.cpp -- what the DNN layers share on the host (declared in xsmm_dnn_internal.hpp): layouts, the
-// feature-map blocking, the split of a pass over logical threads, the staging of operands in pageable host memory, and the
-// report of a failed launch. The templates over the handle type (scratch and tensor binding) are in the header.
+// feature-map blocking, the split of a pass over logical threads, and the adapter that hands a tensor to the staging of operands in
+// pageable host memory. The templates over the handle type (scratch and tensor binding) are in the header.
 #include "xsmm_dnn_internal.hpp"
 
 #include <cstring>
@@ -93,43 +93,8 @@ bool thread_share(long long work, int threads, int ltid, long long* b0, long lon
 
 const Operand* Staging::add(const libxsmm_dnn_tensor* t)
 {
-  Operand* const o = &op[n++];
   libxsmm_dnn_err_t st;
-  o->bytes = (size_t)libxsmm_dnn_get_tensor_elements(t->layout, &st) * libxsmm_dnn_typesize(t->layout->datatype);
-  const int kind = pointer_kind(t->data);
-  o->dev = t->data; o->host = nullptr; o->offset = 0;
-  if (0 != (kind & 2)) wait = true;
-  if (0 == (kind & 1)) { o->host = t->data; o->dev = nullptr; o->offset = total; total += (o->bytes + 255) & ~(size_t)255; wait = true; }
-  return o;
-}
-
-bool Staging::place()
-{
-  if (0 == total) return true;
-  char* const base = static_cast<char*>(scratch(6, total));
-  if (nullptr == base) return false;
-  for (int i = 0; i < n; ++i) {
-    if (nullptr == op[i].host) continue;
-    op[i].dev = base + op[i].offset;
-    if (0 != h2d(op[i].dev, op[i].host, op[i].bytes)) return false;
-  }
-  return true;
-}
-
-bool Staging::finish(std::initializer_list<const Operand*> written)
-{
-  for (const Operand* o : written) {
-    if (nullptr != o && nullptr != o->host && 0 != d2h(o->host, o->dev, o->bytes)) return false;
-  }
-  return !wait || 0 == stream_sync();
-}
-
-bool launched(const char* name, int hip_error)
-{
-  note_launch(name);
-  if (0 == hip_error) return true;
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, hip_error);
-  return false;
+  return out(t->data, (size_t)libxsmm_dnn_get_tensor_elements(t->layout, &st) * libxsmm_dnn_typesize(t->layout->datatype), SLOT_BLOCK, true);
 }
 
 } // namespace xsmm

@@ -164,6 +164,6 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_pooling_execute_st(libxsmm_dnn_pooling
   const int e = launch_pool(g, stream, &name);
   if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
   // what the pass wrote travels back if it was staged: dinput (BWD), output and mask (FWD)
-  const bool ok = bwd ? s.finish({ oi }) : s.finish({ oo, om });
+  const bool ok = bwd ? s.finish(WAIT_OPERANDS, { oi }) : s.finish(WAIT_OPERANDS, { oo, om });
   return ok ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

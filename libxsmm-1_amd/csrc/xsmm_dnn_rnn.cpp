@@ -501,7 +501,7 @@ libxsmm_dnn_err_t execute_backward(libxsmm_dnn_rnncell* h, libxsmm_dnn_compute_k
     e = launch_rnn_bwd_bias(deltas, f32(odb), (int)ld, (int)N, T, stream, &name);
     if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;
   }
-  return s.finish({ odx, odw, odr, odb, odcsp, odhp }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
+  return s.finish(WAIT_OPERANDS, { odx, odw, odr, odb, odcsp, odhp }) ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }
 
 } // namespace
@@ -617,6 +617,6 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_rnncell_execute_st(libxsmm_dnn_rnncell
     }
   }
   // what the pass wrote travels back if it was staged
-  const bool ok = simple ? s.finish({ oh, oz }) : (lstm ? s.finish({ oh, ocs, oi, of, oo, oci, oco }) : s.finish({ oh, oi, of, oo, oci }));
+  const bool ok = simple ? s.finish(WAIT_OPERANDS, { oh, oz }) : (lstm ? s.finish(WAIT_OPERANDS, { oh, ocs, oi, of, oo, oci, oco }) : s.finish(WAIT_OPERANDS, { oh, oi, of, oo, oci }));
   return ok ? LIBXSMM_DNN_SUCCESS : LIBXSMM_DNN_ERR_GENERAL;
 }

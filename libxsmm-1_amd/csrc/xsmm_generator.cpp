@@ -589,14 +589,15 @@ LIBXSMM_API int libxsmm_amd_spgemm_execute_batch(const libxsmm_amd_spgemm* handl
   }
   const size_t bytes_dense = ((size_t)(batch - 1) * (size_t)stride_dense + ext_dense) * ts;
   const size_t bytes_c = ((size_t)(batch - 1) * (size_t)stride_c + ext_c) * ts;
-  const void* dv = sparse_values; const void* dd = dense; void* dc = c;
-  const bool c_host = !is_device_ptr(c);
   // (a pattern without entries has no values to stage: its kernel holds no statement that reads them, and a request for
   // 0 bytes of scratch is answered with whatever the slot holds, a null pointer on a thread that never staged anything)
-  const bool stage_values = (0 != handle->nnz && !is_device_ptr(sparse_values));
-  if (stage_values) { void* t = scratch(0, handle->nnz * ts); if (nullptr == t || 0 != h2d(t, sparse_values, handle->nnz * ts)) return EXIT_FAILURE; dv = t; }
-  if (!is_device_ptr(dense)) { void* t = scratch(3, bytes_dense); if (nullptr == t || 0 != h2d(t, dense, bytes_dense)) return EXIT_FAILURE; dd = t; }
-  if (c_host) { void* t = scratch(5, bytes_c); if (nullptr == t || 0 != h2d(t, c, bytes_c)) return EXIT_FAILURE; dc = t; }
+  Staged st;
+  const Operand* const ov = (0 != handle->nnz ? st.in(sparse_values, handle->nnz * ts, SLOT_IN0) : nullptr);
+  const Operand* const od = st.in(dense, bytes_dense, SLOT_A);
+  const Operand* const oc = st.out(c, bytes_c, SLOT_C, true);
+  if (nullptr == ov && is_host_visible(sparse_values)) st.visible = true; // (never read, but the CPU caller may still reuse it next)
+  if (!st.place()) return EXIT_FAILURE;
+  const void* const dv = (nullptr != ov ? ov->dev : sparse_values); const void* const dd = od->dev; void* dc = oc->dev;
   // argument order of the emitted kernel: (A, B, C, ...) with the sparse operand's values in A (A sparse) or B (B sparse)
   const bool dense_is_a = (SP_CSC_BSPARSE == handle->kind || SP_SOA_BSPARSE == handle->kind || SP_SOA_RM_AC == handle->kind);
   const void* pa = (dense_is_a ? dd : dv);
@@ -610,10 +611,7 @@ LIBXSMM_API int libxsmm_amd_spgemm_execute_batch(const libxsmm_amd_spgemm* handl
                                        "soa_asparse_text", "soa_bsparse_text", "soa_rm_ac_text", "soa_rm_bc_text" };
   note_launch(names[handle->kind]);
   if (0 != e) return EXIT_FAILURE;
-  if (c_host) return 0 == d2h(c, dc, bytes_c) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (dv != sparse_values || dd != dense) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE; // staged inputs must have landed
-  settle(sparse_values, dense, c);
-  return EXIT_SUCCESS;
+  return st.finish(WAIT_OPERANDS, { oc }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 LIBXSMM_API int libxsmm_amd_spgemm_source(const libxsmm_gemm_descriptor* descriptor, int is_csr, const unsigned int* row_idx,

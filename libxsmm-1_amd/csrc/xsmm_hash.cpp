@@ -25,12 +25,7 @@ void complain(int* flag, const char* what, const char* msg)
   if (0 != libxsmm_verbosity && once(flag)) fprintf(stderr, "LIBXSMM ERROR: %s: %s\n", what, msg);
 }
 
-int report(int e, const char* name)
-{
-  if (0 == e) { note_launch(name); return EXIT_SUCCESS; }
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-  return EXIT_FAILURE;
-}
+int report(int e, const char* name) { return queued(name, e) ? EXIT_SUCCESS : EXIT_FAILURE; }
 
 // ---- host loops ------------------------------------------------------------------------------------------------------------
 unsigned int host_hash(const void* data, size_t size, unsigned int seed)
@@ -96,8 +91,6 @@ int hash_run(Form form, bool compare, unsigned int* results, long long* first_di
   }
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  const int kind_results = pointer_kind(results), kind_first = pointer_kind(first_diff);
-  if (FORM_ASYNC == form && 0 == (kind_results & 1)) { complain(flag, what, "the result must be memory the GPU reaches!"); return EXIT_FAILURE; }
 
   HashArgs args; memset(&args, 0, sizeof(args));
   args.a = a; args.b = b; args.line_bytes = line_bytes; args.lines = lines; args.lda = (1 < lines ? lda : 0); args.ldb = (1 < lines ? ldb : 0);
@@ -106,26 +99,20 @@ int hash_run(Form form, bool compare, unsigned int* results, long long* first_di
   // operands the GPU does not reach are staged
   const size_t ext_a = (size_t)(batch - 1) * (size_t)stride_a + (size_t)(lines - 1) * (size_t)args.lda + line_bytes;
   const size_t ext_b = (size_t)(batch - 1) * (size_t)stride_b + (size_t)(lines - 1) * (size_t)args.ldb + line_bytes;
-  if (0 == (pointer_kind(a) & 1)) {
-    void* const p = scratch(0, ext_a);
-    if (nullptr == p || 0 != h2d(p, a, ext_a)) return EXIT_FAILURE;
-    args.a = p;
-  }
-  if (compare && 0 == (pointer_kind(b) & 1)) {
-    void* const p = scratch(1, ext_b);
-    if (nullptr == p || 0 != h2d(p, b, ext_b)) return EXIT_FAILURE;
-    args.b = p;
-  }
-
+  Staged s;
+  const Operand* const oa = s.in(a, ext_a, SLOT_IN0);
+  const Operand* const ob = (compare ? s.in(b, ext_b, SLOT_IN1) : nullptr);
   // the workspace: [the lowest differing item][the partials of a large item][staged results][staged first_diff]
-  const bool stage_results = (0 == (kind_results & 1)), stage_first = (nullptr != first_diff && 0 == (kind_first & 1));
-  const size_t head = sizeof(long long) + sizeof(unsigned int) * HASH_MAX_BLOCKS, nres = (size_t)(FORM_BATCH == form ? batch : 1);
-  char* const ws = static_cast<char*>(scratch(8, head + (stage_results ? sizeof(unsigned int) * nres : 0) + sizeof(long long)));
-  if (nullptr == ws) return EXIT_FAILURE;
-  long long* const ws_first = reinterpret_cast<long long*>(ws);
-  unsigned int* const partial = reinterpret_cast<unsigned int*>(ws + sizeof(long long));
-  unsigned int* const d_results = stage_results ? reinterpret_cast<unsigned int*>(ws + head) : results;
-  long long* const d_first = stage_first ? reinterpret_cast<long long*>(ws + head + (stage_results ? sizeof(unsigned int) * nres : 0)) : first_diff;
+  const Operand* const ows = s.work(sizeof(long long) + sizeof(unsigned int) * HASH_MAX_BLOCKS, SLOT_HASH);
+  const Operand* const ores = s.out(results, sizeof(unsigned int) * (size_t)(FORM_BATCH == form ? batch : 1), SLOT_HASH, false);
+  const Operand* const ofirst = s.out(first_diff, sizeof(*first_diff), SLOT_HASH, false);
+  if (FORM_ASYNC == form && nullptr != ores->host) { complain(flag, what, "the result must be memory the GPU reaches!"); return EXIT_FAILURE; }
+  if (!s.place()) return EXIT_FAILURE;
+  args.a = oa->dev; args.b = dev_of(ob);
+  long long* const ws_first = static_cast<long long*>(ows->dev);
+  unsigned int* const partial = reinterpret_cast<unsigned int*>(static_cast<char*>(ows->dev) + sizeof(long long));
+  unsigned int* const d_results = static_cast<unsigned int*>(ores->dev);
+  long long* const d_first = static_cast<long long*>(dev_of(ofirst));
 
   int rc = EXIT_SUCCESS;
   if (nullptr != first_diff) rc = (0 == launch_hash_first(ws_first, nullptr, true, stream)) ? EXIT_SUCCESS : EXIT_FAILURE;
@@ -145,15 +132,7 @@ int hash_run(Form form, bool compare, unsigned int* results, long long* first_di
   if (EXIT_SUCCESS == rc && nullptr != first_diff) rc = report(launch_hash_first(ws_first, d_first, false, stream), "hash_first");
   if (EXIT_SUCCESS != rc) return rc;
 
-  if (stage_results || stage_first) { // one copy per staged result, then one wait
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    if (stage_results) e = hipMemcpyAsync(results, d_results, sizeof(unsigned int) * nres, hipMemcpyDefault, st);
-    if (hipSuccess == e && stage_first) e = hipMemcpyAsync(first_diff, d_first, sizeof(*first_diff), hipMemcpyDefault, st);
-    if (hipSuccess == e) e = hipStreamSynchronize(st);
-    if (hipSuccess != e) { (void)hipGetLastError(); return EXIT_FAILURE; }
-  }
-  return EXIT_SUCCESS;
+  return s.finish(WAIT_RESULTS, { ores, ofirst }) ? EXIT_SUCCESS : EXIT_FAILURE; // one copy per staged result, then one wait
 }
 
 bool on_device(const void* p) { return 1 == pointer_kind(p); } // plain device memory (false without a device)
@@ -207,16 +186,13 @@ LIBXSMM_API unsigned int libxsmm_diff_n(const void* a, const void* bn, unsigned 
   DiffKey key; memset(&key, 0, sizeof(key));
   const void* d_a = a;
   if (0 == (pointer_kind(a) & 1)) { memcpy(key.b, a, size); d_a = nullptr; }
-  const void* d_bn = bn;
-  if (0 == (pointer_kind(bn) & 1)) {
-    const size_t ext = (size_t)(n - 1) * stride + size;
-    void* const p = scratch(1, ext);
-    if (nullptr == p || 0 != h2d(p, bn, ext)) return 0;
-    d_bn = p;
-  }
-  unsigned int* const best = static_cast<unsigned int*>(scratch(8, sizeof(long long)));
-  unsigned int r = 0xffffffffu;
-  if (nullptr == best || EXIT_SUCCESS != report(launch_diff_n(key, d_a, d_bn, size, stride, hint, n, best, stream), "diff_n") || 0 != d2h(&r, best, sizeof(r))) {
+  Staged s;
+  const Operand* const obn = s.in(bn, (size_t)(n - 1) * stride + size, SLOT_IN1);
+  const Operand* const obest = s.work(sizeof(long long), SLOT_HASH);
+  if (!s.place()) return 0;
+  unsigned int* const best = static_cast<unsigned int*>(obest->dev);
+  unsigned int r = 0xffffffffu; // (its read-back is the one wait of the call)
+  if (EXIT_SUCCESS != report(launch_diff_n(key, d_a, obn->dev, size, stride, hint, n, best, stream), "diff_n") || 0 != d2h(&r, best, sizeof(r))) {
     (void)hipGetLastError();
     return 0;
   }

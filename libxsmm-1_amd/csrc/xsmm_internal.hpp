@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -99,7 +100,6 @@ Residency classify(const void* a, const void* b, const void* c);
 // operand is memory the CPU addresses as well (the call waits for the stream)
 int run_smm(const SmmBatch& s, int host_visible = -1);
 int run_groups(std::vector<SmmBatch>& groups);
-void launch_failed(const char* name, int hip_error);      // the one message of a launch that failed
 size_t span_a(const SmmBatch& s);                         // elements touched by one A operand (span_b, span_c: B, C)
 size_t span_b(const SmmBatch& s);
 size_t span_c(const SmmBatch& s);
@@ -108,7 +108,7 @@ const int* device_indexes(const int* idx, int index_stride, long long n, bool* o
 // launch the record): s.a, s.b, s.c become the uploaded copies, the steps those of tight arrays. false: an upload failed (the
 // caller's commit releases the entries).
 bool upload_pointer_arrays(SmmBatch& s, void* stream, const void* a, size_t na, const void* b, size_t nb, const void* c, size_t nc);
-// Host spans into the thread's scratch slots 3, 4, 5 (a NULL span is left out); dev receives the device copies. false: failed.
+// Host spans into the thread's scratch slots SLOT_A, SLOT_B, SLOT_C (a NULL span is left out); dev receives the device copies. false: failed.
 bool stage_in(const void* const host[3], const size_t bytes[3], char* dev[3]);
 int stage_out(void* host_c, const void* dev_c, size_t bytes); // C back where it came from (waits for the stream); 0: done
 int batch_execute(SmmBatch s, libxsmm_blasint index_base, libxsmm_blasint index_stride,
@@ -232,9 +232,9 @@ Device& device();
 Device& device_raw();                     // the same without launching what is open on the thread (record_flush)
 bool device_ready();                      // probes once; false if no HIP device
 void fail_no_device(const char* what);    // prints a loud error (always) -- the product has no CPU compute path
-bool is_device_ptr(const void* p);
-int pointer_kind(const void* p);         // bit 0: the GPU reaches it; bit 1: pinned host / managed memory (the CPU addresses it as well)
-bool is_host_visible(const void* p);      // pinned host or managed memory (processed in place, but the CPU reads it directly)
+int pointer_kind(const void* p);         // the one driver query. bit 0: the GPU reaches it; bit 1: pinned host / managed memory (the CPU addresses it as well)
+inline bool is_device_ptr(const void* p) { return 0 != (pointer_kind(p) & 1); }
+inline bool is_host_visible(const void* p) { return 0 != (pointer_kind(p) & 2); } // processed in place, but the CPU reads it directly
 void settle(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr); // wait for the stream if an operand is host-visible
 int flag_slot_set(int* slot, int equal_pairs, int decreasing_pairs); // the verdict without a check kernel (0: ok)
 constexpr int INDEX_UPLOAD_RING = 256;   // staged arrays a thread may hold before index_upload_commit (a grouped call stages three arrays per group plus its table)
@@ -248,12 +248,73 @@ void flag_slot_commit();                  // after the launches that read the ca
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
 int h2d(void* dst, const void* src, size_t bytes);
-int d2h(void* dst, const void* src, size_t bytes);
+int d2h(void* dst, const void* src, size_t bytes);          // waits for the stream
+int d2h_async(void* dst, const void* src, size_t bytes);
+// rows of row_bytes bytes between pitched images on the stream; to_device: host -> device, else device -> host
+int copy2d(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t row_bytes, size_t rows, bool to_device);
 int stream_sync();
 void note_launch(const char* name);
+// The one report of a launch: false if it failed (and says so on stderr). launched counts the launch and makes it last_kernel
+// either way; queued only if it succeeded (last_kernel names what was queued, never a launch that failed). DESIGN.md 8w.
+bool launched(const char* name, int hip_error);
+bool queued(const char* name, int hip_error);
 
-// grow-only device scratch, one per thread-local slot id
-void* scratch(int slot, size_t bytes);
+// Grow-only device scratch, one buffer per slot and thread. A buffer is reused in stream order (scratch() waits only if the
+// stream changed or the buffer must grow), so two users of one slot are safe whenever the later one is queued behind the earlier
+// one on the same call path or in a later call -- what must never share a slot are two operands of ONE launch.
+enum ScratchSlot : int {
+  SLOT_IN0 = 0,   // first read-only operand: xcopy in, quant in, matdiff ref, hash a, the text kernels' values, the DNN tensor copy;
+                  // the batch front end's uploaded array of A pointers (no entry point has both)
+  SLOT_IN1 = 1,   // second operand: xcopy out, quant out, matdiff tst, hash b, diff_n's items; the array of B pointers
+  SLOT_RESULTS = 2, // matdiff's staged results [info][items][item]; the array of C pointers
+  SLOT_A = 3,     // the GEMM-like triples: A of the batch front end, tgemm / lowp gemm, blocked gemm (copy and permute: src), first
+                  // operand of packed, dense of the text kernels, spmdm's image of A (and its widened bf16 A)
+  SLOT_B = 4,     // B of the same (copy and permute: dst), fsspmdm's panels of B, spmdm's image of B
+  SLOT_C = 5,     // C of the same
+  SLOT_BLOCK = 6, // the DNN layers' one block of staged tensors; matdiff's records and partials; spmdm's raw bf16 operand. A DNN pass
+                  // calls neither of the others between place() and finish()
+  SLOT_HULLS = 7, // the address hulls of recorded batch calls (xsmm_batch_record.cpp)
+  SLOT_HASH = 8,  // hash / compare: [lowest differing item][partials][staged results][staged first_diff]; diff_n's result word
+  SLOT_COUNT = 16
+};
+void* scratch(ScratchSlot slot, size_t bytes);
+
+// ---- operands in any memory (xsmm_staging.cpp) ------------------------------------------------------------------
+// The operands of one call where the kernels can reach them. An operand the GPU reaches stays where it is (dev is the caller's
+// pointer); one in pageable host memory gets a place in the device scratch of its slot. Operands that name the same slot share
+// one block, carved up at 256-byte offsets in the order in which they are asked for. One driver query per operand.
+struct Operand {
+  void* dev; void* host;                  // dev is valid after place(); host: nullptr unless staged
+  size_t bytes, offset; int slot;         // slot < 0: the caller's memory
+  bool upload;
+  size_t row_bytes, pitch;                // pitch != 0: host is pitched rows of row_bytes, dev their tight image
+};
+constexpr int STAGED_MAX = 24;
+enum WaitFor : int {
+  WAIT_RESULTS = 0,   // only for written operands that travelled back (an upload from pageable memory has consumed the host buffer
+                      // when it returns, and a result the GPU reaches is written by the last kernel: nobody waits)
+  WAIT_OPERANDS = 1   // ... and if any operand was staged or is host-visible: the CPU caller reads or overwrites it next
+};
+struct Staged {
+  Operand op[STAGED_MAX]; int n = 0; size_t total[SLOT_COUNT] = {}; bool visible = false, staged = false, copied = false, failed = false;
+  // Every one returns nullptr for p == nullptr (no operand) and when the object is full (ok() is false from then on).
+  const Operand* in(const void* p, size_t bytes, ScratchSlot slot) { return add(const_cast<void*>(p), bytes, slot, true, 0, 0); } // the span as it lies
+  // upload: the pass leaves bytes in the span that must survive (or reads it)
+  const Operand* out(void* p, size_t bytes, ScratchSlot slot, bool upload) { return add(p, bytes, slot, upload, 0, 0); }
+  // rows of row_bytes bytes, pitch bytes apart: the device sees a tight image, what lies between the rows never travels
+  const Operand* out2d(void* p, size_t row_bytes, size_t rows, size_t pitch, ScratchSlot slot, bool upload) { return add(p, row_bytes * rows, slot, upload, row_bytes, pitch); }
+  const Operand* work(size_t bytes, ScratchSlot slot);   // device memory of the call's own in the block of slot
+  bool ok() const { return !failed; }
+  bool place();                                          // allocates and uploads; false: no memory, a copy failed, or !ok()
+  // after the launches: the staged ones of the operands the pass wrote (nullptr: skipped) travel back, then at most one wait.
+  // back alone queues the copies: for a caller whose own read-back is the wait (the forms with the reference's signature)
+  bool back(std::initializer_list<const Operand*> written);
+  bool finish(WaitFor wait, std::initializer_list<const Operand*> written);
+private:
+  const Operand* add(void* p, size_t bytes, ScratchSlot slot, bool upload, size_t row_bytes, size_t pitch);
+  Operand* carve(size_t bytes, ScratchSlot slot);
+};
+inline void* dev_of(const Operand* o) { return nullptr != o ? o->dev : nullptr; }
 
 enum KernelClass : int { KC_DENSE = 0, KC_REDUCE = 1, KC_CSR_REG = 2, KC_TEXT = 3 /* pattern kernel compiled from generated text (SOA family) */,
   KC_LOWP = 4 /* i16 / bf16 inputs (kernels/smm_lowp.hip) */,
@@ -330,7 +391,7 @@ struct TgemmArgs {                        // C(m x n) = op(A) * op(B) + (beta0 ?
 int launch_tgemm(const TgemmArgs& args, void* stream, const char** name); // returns hipError_t as int
 // One rectangle {m0, m1, n0, n1} of C = op(A) * op(B) + (beta0 ? 0 : C) for a tiled kernel, operands in any memory and plain
 // column-major: ti and to are the element sizes of A / B and of C. Memory the GPU reaches is processed in place, pageable
-// spans of A and B are staged (scratch slots 3 and 4), a pageable C travels as a tight image of the rectangle (slot 5);
+// spans of A and B are staged (SLOT_A and SLOT_B), a pageable C travels as a tight image of the rectangle (SLOT_C);
 // host-visible memory is complete on return. launch queues the kernel for the rectangle's part of the operands as the GPU
 // sees them and returns hipError_t as int plus the kernel's name. Returns EXIT_SUCCESS or EXIT_FAILURE.
 typedef std::function<int(void* stream, const void* a, const void* b, void* c, long long ldc, int m, int n, const char** name)> RectLaunch;

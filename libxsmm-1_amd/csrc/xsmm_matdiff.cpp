@@ -24,12 +24,7 @@ void complain(int* flag, const char* what, const char* msg)
   if (0 != libxsmm_verbosity && once(flag)) fprintf(stderr, "LIBXSMM ERROR: %s: %s\n", what, msg);
 }
 
-int report(int e, const char* name)
-{
-  if (0 == e) { note_launch(name); return EXIT_SUCCESS; }
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-  return EXIT_FAILURE;
-}
+int report(int e, const char* name) { return queued(name, e) ? EXIT_SUCCESS : EXIT_FAILURE; }
 
 size_t type_size(int datatype)
 {
@@ -86,8 +81,6 @@ int matdiff_run(Form form, libxsmm_matdiff_info* info, libxsmm_matdiff_info* ite
   }
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  const int kind_info = pointer_kind(info), kind_items = pointer_kind(items), kind_item = pointer_kind(item);
-  if (FORM_ASYNC == form && 0 == (kind_info & 1)) { complain(flag, what, "info must be memory the GPU reaches!"); return EXIT_FAILURE; }
 
   MatdiffArgs a; memset(&a, 0, sizeof(a));
   a.datatype = (int)datatype; a.batch = batch; a.sr = stride_ref; a.st = stride_tst;
@@ -99,17 +92,16 @@ int matdiff_run(Form form, libxsmm_matdiff_info* info, libxsmm_matdiff_info* ite
   // operands the GPU does not reach are staged
   const size_t ext_r = ((size_t)(batch - 1) * (size_t)a.sr + (size_t)(a.nn - 1) * (size_t)a.ldr + (size_t)a.mm) * ts;
   const size_t ext_t = ((size_t)(batch - 1) * (size_t)a.st + (size_t)(a.nn - 1) * (size_t)a.ldt + (size_t)a.mm) * ts;
-  a.ref = ref; a.tst = tst;
-  if (0 == (pointer_kind(ref) & 1)) {
-    void* const p = scratch(0, ext_r);
-    if (nullptr == p || 0 != h2d(p, ref, ext_r)) return EXIT_FAILURE;
-    a.ref = p;
-  }
-  if (nullptr != tst && 0 == (pointer_kind(tst) & 1)) {
-    void* const p = scratch(1, ext_t);
-    if (nullptr == p || 0 != h2d(p, tst, ext_t)) return EXIT_FAILURE;
-    a.tst = p;
-  }
+  Staged s;
+  const Operand* const oref = s.in(ref, ext_r, SLOT_IN0);
+  const Operand* const otst = s.in(tst, ext_t, SLOT_IN1);
+  // results that the GPU does not reach are staged: [info][items][item]
+  const Operand* const oinfo = s.out(info, sizeof(*info), SLOT_RESULTS, false);
+  const Operand* const oitems = s.out(items, sizeof(*items) * (size_t)batch, SLOT_RESULTS, false);
+  const Operand* const oitem = s.out(item, sizeof(*item), SLOT_RESULTS, false);
+  if (FORM_ASYNC == form && nullptr != oinfo->host) { complain(flag, what, "info must be memory the GPU reaches!"); return EXIT_FAILURE; }
+  if (!s.place()) return EXIT_FAILURE;
+  a.ref = oref->dev; a.tst = dev_of(otst);
   a.vec_ref = vector_loads(a.ref, ts, a.ldr, a.sr) ? 1 : 0;
   a.vec_tst = (nullptr != a.tst && vector_loads(a.tst, ts, a.ldt, a.st)) ? 1 : 0;
 
@@ -119,22 +111,15 @@ int matdiff_run(Form form, libxsmm_matdiff_info* info, libxsmm_matdiff_info* ite
   MatdiffArgs one = a; one.batch = 1;
   const size_t ws_tiled = small ? 0 : matdiff_tiled_workspace(one);
   const size_t nrec = (size_t)(batch + level1 + level2);
-  char* const ws = static_cast<char*>(scratch(6, nrec * sizeof(MatdiffRecord) + ws_tiled));
+  char* const ws = static_cast<char*>(scratch(SLOT_BLOCK, nrec * sizeof(MatdiffRecord) + ws_tiled));
   if (nullptr == ws) return EXIT_FAILURE;
   MatdiffRecord* const rec = reinterpret_cast<MatdiffRecord*>(ws);
   MatdiffRecord* level[2] = { rec + batch, rec + batch + level1 };
   void* const tiled = ws + nrec * sizeof(MatdiffRecord);
 
-  // results that the GPU does not reach are staged: [info][items][item]
-  const bool stage_info = (0 == (kind_info & 1)), stage_items = (nullptr != items && 0 == (kind_items & 1)), stage_item = (nullptr != item && 0 == (kind_item & 1));
-  char* staged = nullptr;
-  if (stage_info || stage_items || stage_item) {
-    staged = static_cast<char*>(scratch(2, sizeof(libxsmm_matdiff_info) * (size_t)(1 + batch) + sizeof(long long)));
-    if (nullptr == staged) return EXIT_FAILURE;
-  }
-  libxsmm_matdiff_info* const d_info = stage_info ? reinterpret_cast<libxsmm_matdiff_info*>(staged) : info;
-  libxsmm_matdiff_info* const d_items = stage_items ? reinterpret_cast<libxsmm_matdiff_info*>(staged) + 1 : items;
-  long long* const d_item = stage_item ? reinterpret_cast<long long*>(staged + sizeof(libxsmm_matdiff_info) * (size_t)(1 + batch)) : item;
+  libxsmm_matdiff_info* const d_info = static_cast<libxsmm_matdiff_info*>(oinfo->dev);
+  libxsmm_matdiff_info* const d_items = static_cast<libxsmm_matdiff_info*>(dev_of(oitems));
+  long long* const d_item = static_cast<long long*>(dev_of(oitem));
 
   int rc;
   if (small) rc = report(launch_matdiff_items(a, rec, stream), "matdiff_items");
@@ -162,16 +147,9 @@ int matdiff_run(Form form, libxsmm_matdiff_info* info, libxsmm_matdiff_info* ite
   }
   if (EXIT_SUCCESS != rc) return rc;
 
-  if (nullptr != staged) { // one copy per staged result, then one wait
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    if (stage_info) e = hipMemcpyAsync(info, d_info, sizeof(*info), hipMemcpyDefault, st);
-    if (hipSuccess == e && stage_items) e = hipMemcpyAsync(items, d_items, sizeof(*items) * (size_t)batch, hipMemcpyDefault, st);
-    if (hipSuccess == e && stage_item) e = hipMemcpyAsync(item, d_item, sizeof(*item), hipMemcpyDefault, st);
-    if (hipSuccess == e) e = hipStreamSynchronize(st);
-    if (hipSuccess != e) { (void)hipGetLastError(); return EXIT_FAILURE; }
-  }
-  else if (FORM_SYNC == form) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
+  // one copy per staged result, then one wait; libxsmm_matdiff's caller reads info next
+  if (!s.finish(WAIT_RESULTS, { oinfo, oitems, oitem })) return EXIT_FAILURE;
+  if (FORM_SYNC == form && !s.copied) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
   return EXIT_SUCCESS;
 }
 

@@ -271,27 +271,16 @@ int execute(Kernel* k, const void* a, const void* b, void* c, long long npacks, 
   for (int i = 0; i < 3; ++i) if (s.op[i].used && nullptr == src[i]) return EXIT_FAILURE;
   if (0 == npacks) return EXIT_SUCCESS;
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
-  void* dev[3] = { nullptr, nullptr, nullptr };
-  size_t bytes[3] = { 0, 0, 0 };
-  bool staged[3] = { false, false, false }, visible = false;
+  Staged st; // the CPU's memory: through device copies of the spans
+  const Operand* o[3] = { nullptr, nullptr, nullptr };
   for (int i = 0; i < 3; ++i) {
-    if (!s.op[i].used) continue;
-    bytes[i] = ((size_t)(npacks - 1) * s.op[i].ps + s.op[i].extent) * s.ts;
-    const int kind = pointer_kind(src[i]);
-    if (0 != (kind & 1)) { dev[i] = const_cast<void*>(src[i]); visible = visible || 0 != (kind & 2); }
-    else { // the CPU's memory: through a device copy
-      dev[i] = scratch(3 + i, bytes[i]);
-      if (nullptr == dev[i] || 0 != h2d(dev[i], src[i], bytes[i])) return EXIT_FAILURE;
-      staged[i] = true;
-    }
+    if (s.op[i].used) o[i] = st.out(const_cast<void*>(src[i]), ((size_t)(npacks - 1) * s.op[i].ps + s.op[i].extent) * s.ts, ScratchSlot(SLOT_A + i), true);
   }
+  if (!st.place()) return EXIT_FAILURE;
   const char* name = "";
-  const int e = launch(*p, form_of(s, aligned16(s, dev[0], dev[1], dev[2])), dev[0], dev[1], dev[2], npacks, nullptr, nullptr, device().stream, &name);
-  note_launch(name);
-  if (0 != e) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e); return EXIT_FAILURE; }
-  if (staged[s.written]) return 0 == d2h(const_cast<void*>(src[s.written]), dev[s.written], bytes[s.written]) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (staged[0] || staged[1] || staged[2] || visible) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
+  const int e = launch(*p, form_of(s, aligned16(s, dev_of(o[0]), dev_of(o[1]), dev_of(o[2]))), dev_of(o[0]), dev_of(o[1]), dev_of(o[2]), npacks, nullptr, nullptr, device().stream, &name);
+  if (!launched(name, e)) return EXIT_FAILURE;
+  return st.finish(WAIT_OPERANDS, { o[s.written] }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 Kernel* make_kernel(const void* desc, int kind)

@@ -43,45 +43,6 @@ bool tiled_enabled()
   return nullptr == e || 0 != atoi(e);
 }
 
-// ---- operands in any memory --------------------------------------------------------------------------------------------
-struct Staged {
-  const void* din; void* dout;  // what the kernels see
-  void* out; size_t out_bytes;  // the caller's output, if it was staged
-  bool wait;                    // an operand is host-visible or was staged: complete on return
-};
-
-bool stage(Staged* s, const void* in, size_t in_bytes, void* out, size_t out_bytes)
-{
-  const int kind_in = pointer_kind(in), kind_out = pointer_kind(out);
-  s->din = in; s->dout = out; s->out = nullptr; s->out_bytes = out_bytes;
-  s->wait = (0 != ((kind_in | kind_out) & 2));
-  if (0 == (kind_in & 1)) {
-    void* const p = scratch(0, in_bytes);
-    if (nullptr == p || 0 != h2d(p, in, in_bytes)) return false;
-    s->din = p; s->wait = true;
-  }
-  if (0 == (kind_out & 1)) { // (every element of the output is written: nothing travels to the device first)
-    s->dout = scratch(1, out_bytes);
-    if (nullptr == s->dout) return false;
-    s->out = out; s->wait = true;
-  }
-  return true;
-}
-
-int finish(const Staged& s)
-{
-  if (nullptr != s.out) return 0 == d2h(s.out, s.dout, s.out_bytes) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (s.wait) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
-}
-
-int report(int e, const char* name)
-{
-  if (0 == e) { note_launch(name); return EXIT_SUCCESS; } // (last_kernel names what was queued, never a launch that failed)
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-  return EXIT_FAILURE;
-}
-
 // ---- quantisation ----------------------------------------------------------------------------------------------------------
 struct QuantCall {
   const float* in; short* out; unsigned char* scf;
@@ -100,10 +61,12 @@ int quantize_run(const QuantCall& q, bool async, const char* what, int* flag)
   if (async && 0 == (pointer_kind(q.scf) & 1)) { complain(flag, what, "scf must be memory the GPU reaches!"); return EXIT_FAILURE; }
   int* const slot = flag_slot(); // [0]: the maximum; [1]: the scf byte of the reference forms
   if (nullptr == slot) return EXIT_FAILURE;
-  Staged s;
-  if (!stage(&s, q.in, (size_t)q.total * sizeof(float), q.out, (size_t)q.total * sizeof(short))) { flag_slot_commit(); return EXIT_FAILURE; }
-  const float* const din = static_cast<const float*>(s.din);
-  short* const dout = static_cast<short*>(s.dout);
+  Staged s; // (every element of the output is written: nothing travels to the device first)
+  const Operand* const oi = s.in(q.in, (size_t)q.total * sizeof(float), SLOT_IN0);
+  const Operand* const oo = s.out(q.out, (size_t)q.total * sizeof(short), SLOT_IN1, false);
+  if (!s.place()) { flag_slot_commit(); return EXIT_FAILURE; }
+  const float* const din = static_cast<const float*>(oi->dev);
+  short* const dout = static_cast<short*>(oo->dev);
   QuantHead h;
   h.mode = q.mode; h.add_shift = q.add_shift; h.seed = 0;
   h.maxword = reinterpret_cast<const unsigned*>(slot);
@@ -112,24 +75,22 @@ int quantize_run(const QuantCall& q, bool async, const char* what, int* flag)
     h.seed = g_seed.load(std::memory_order_relaxed);
     if (0 == h.seed) h.seed = (unsigned int)(libxsmm_timer_tick() % 0xffffffffu);
   }
-  int rc = report(launch_quant_absmax(din, q.total, reinterpret_cast<unsigned*>(slot), stream), "quant_absmax");
-  if (EXIT_SUCCESS == rc) {
+  bool ok = queued("quant_absmax", launch_quant_absmax(din, q.total, reinterpret_cast<unsigned*>(slot), stream));
+  if (ok) {
     const unsigned CB = q.g.cb16 * q.g.lp;
     if (0 == q.layout || (1 == q.layout && q.g.cb32 == CB)) { // identical blockings: the same order on both sides
-      rc = report(launch_quant_flat(din, dout, q.total, h, stream), "quant_flat");
+      ok = queued("quant_flat", launch_quant_flat(din, dout, q.total, h, stream));
     }
     else if (1 == q.layout && 1 == q.g.cb32 && 0 == CB % 2 && 0 == reinterpret_cast<uintptr_t>(dout) % 4 && tiled_enabled()) {
-      rc = report(launch_quant_act_tiled(din, dout, q.total / ((long long)CB * q.g.H * q.g.W), (int)CB, (long long)q.g.H * q.g.W, h, stream), "quant_act_tiled");
+      ok = queued("quant_act_tiled", launch_quant_act_tiled(din, dout, q.total / ((long long)CB * q.g.H * q.g.W), (int)CB, (long long)q.g.H * q.g.W, h, stream));
     }
-    else rc = report(launch_quant_layout(din, dout, q.g, h, stream), 1 == q.layout ? "quant_act" : "quant_fil");
+    else ok = queued(1 == q.layout ? "quant_act" : "quant_fil", launch_quant_layout(din, dout, q.g, h, stream));
   }
   flag_slot_commit();
-  if (EXIT_SUCCESS != rc) return rc;
-  if (!async) { // the host byte of the reference's signature: one wait per call
-    if (nullptr != s.out && hipSuccess != hipMemcpyAsync(s.out, s.dout, s.out_bytes, hipMemcpyDefault, (hipStream_t)stream)) { (void)hipGetLastError(); return EXIT_FAILURE; }
-    return 0 == d2h(q.scf, h.scf, 1) ? EXIT_SUCCESS : EXIT_FAILURE;
-  }
-  return finish(s);
+  if (!ok) return EXIT_FAILURE;
+  // the host byte of the reference's signature: its read-back is the one wait of the call
+  if (!async) return (s.back({ oo }) && 0 == d2h(q.scf, h.scf, 1)) ? EXIT_SUCCESS : EXIT_FAILURE;
+  return s.finish(WAIT_OPERANDS, { oo }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 bool mode_of(int round_mode, int* mode)
@@ -198,12 +159,14 @@ void map_run(int op, const void* in, void* out, long long n, float scale, const 
   void* const stream = device().stream; // (seals an open burst of deferred calls)
   const bool widen = (0 == op || 4 == op); // 2 bytes in, 4 out
   Staged s;
-  if (!stage(&s, in, (size_t)n * (widen ? 2 : 4), out, (size_t)n * (widen ? 4 : 2))) return;
+  const Operand* const oi = s.in(in, (size_t)n * (widen ? 2 : 4), SLOT_IN0);
+  const Operand* const oo = s.out(out, (size_t)n * (widen ? 4 : 2), SLOT_IN1, false);
+  if (!s.place()) return;
   int e;
-  if (0 == op) e = launch_dequant_flat(static_cast<const short*>(s.din), static_cast<float*>(s.dout), n, scale, stream);
-  else if (4 == op) e = launch_bf16_widen(static_cast<const unsigned short*>(s.din), static_cast<float*>(s.dout), n, stream);
-  else e = launch_bf16_narrow(op - 1, static_cast<const float*>(s.din), static_cast<unsigned short*>(s.dout), n, stream);
-  if (EXIT_SUCCESS == report(e, names[op])) (void)finish(s);
+  if (0 == op) e = launch_dequant_flat(static_cast<const short*>(oi->dev), static_cast<float*>(oo->dev), n, scale, stream);
+  else if (4 == op) e = launch_bf16_widen(static_cast<const unsigned short*>(oi->dev), static_cast<float*>(oo->dev), n, stream);
+  else e = launch_bf16_narrow(op - 1, static_cast<const float*>(oi->dev), static_cast<unsigned short*>(oo->dev), n, stream);
+  if (queued(names[op], e)) (void)s.finish(WAIT_OPERANDS, { oo });
 }
 
 } // namespace

@@ -129,14 +129,14 @@ int fsspmdm_run(const H* h, const T* B, T* C, long long batch)
   // costing a launch each (xsmm_defer.cpp)
   if (1 == batch && nullptr != h->jit && 0 == (h->N % h->jit_vec)
     && defer_panels(h, h->jit, B, C, h->typesize, h->M, h->N, h->K, h->ldb, h->ldc, h->jit_vec)) return EXIT_SUCCESS;
-  if (is_device_ptr(B) && is_device_ptr(C)) { const int e = launch(B, C); if (0 == e) settle(B, C); return 0 == e ? EXIT_SUCCESS : EXIT_FAILURE; }
   // host panels: stage rows [0,K) x columns [0, N*batch) of B and rows [0,M) of C (strided by ldb/ldc)
   const long long ncols = (long long)h->N * batch;
   const size_t eb = (size_t)(h->K - 1) * h->ldb + ncols, ec = (size_t)(h->M - 1) * h->ldc + ncols;
-  char* const db = static_cast<char*>(scratch(4, eb * sizeof(T))); char* const dc = static_cast<char*>(scratch(5, ec * sizeof(T)));
-  if (nullptr == db || nullptr == dc || 0 != h2d(db, B, eb * sizeof(T)) || 0 != h2d(dc, C, ec * sizeof(T))) return EXIT_FAILURE;
-  if (0 != launch(db, dc)) return EXIT_FAILURE;
-  return 0 == d2h(C, dc, ec * sizeof(T)) ? EXIT_SUCCESS : EXIT_FAILURE;
+  Staged s;
+  const Operand* const ob = s.in(B, eb * sizeof(T), SLOT_B);
+  const Operand* const oc = s.out(C, ec * sizeof(T), SLOT_C, true);
+  if (!s.place() || 0 != launch(ob->dev, oc->dev)) return EXIT_FAILURE;
+  return s.finish(WAIT_OPERANDS, { oc }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 template<typename H> void fsspmdm_destroy(H* h)
@@ -276,7 +276,7 @@ int copy_window(float* dev, float* host, int ld, int r0, int nr, int c0, int nc,
 // templates do element by element (EXPAND_BFLOAT16 before the compare / the copy into scratch_B).
 // (first, count): the elements a block call needs when they are one contiguous piece of the matrix -- rows of A, rows of a transposed
 // B -- else the whole matrix; the scratch images keep the shape of the whole matrix, so the kernels address them as usual
-const float* widen_bf16(const libxsmm_bfloat16* p, size_t elems, int slot_raw, int slot_wide, bool* ok, size_t first = 0, size_t count = 0)
+const float* widen_bf16(const libxsmm_bfloat16* p, size_t elems, ScratchSlot slot_raw, ScratchSlot slot_wide, bool* ok, size_t first = 0, size_t count = 0)
 {
   if (0 == count || first + count > elems) { first = 0; count = elems; }
   const libxsmm_bfloat16* src = p;
@@ -312,8 +312,7 @@ int spmdm_create_slices(const libxsmm_spmdm_handle* handle, int ta, const float*
   const bool all = (0 == mb0 && mbn == handle->mb);
   const int e = launch_spmdm_create_blocks(handle->m, handle->k, handle->bm, handle->bk, handle->mb, all ? 0 : mb0, all ? 1 : handle->mb,
     all ? handle->mb * handle->kb : handle->kb, ta, da, s.rowidx, s.colidx, s.values, device().stream, &name);
-  note_launch(name);
-  if (0 != e) fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
+  (void)launched(name, e);
   return e;
 }
 
@@ -329,8 +328,7 @@ int spmdm_compute_tiles(const libxsmm_spmdm_handle* handle, int tb, int tc, floa
     e = launch_spmdm_compute_generic(1, handle->m, handle->n, handle->k, handle->bm, handle->bk, handle->mb, handle->kb, tb, tc, beta,
       s.rowidx, s.colidx, s.values, (long long)s.rstride, (long long)s.cap, db, dc, 0, 0, m0, m1, n0, n1, device().stream, &name);
   }
-  note_launch(name);
-  if (0 != e) fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
+  (void)launched(name, e);
   return e;
 }
 
@@ -345,7 +343,7 @@ int spmdm_create(const libxsmm_spmdm_handle* handle, char transa, const float* a
   const int ta = is_trans(transa) ? 1 : 0;
   const float* da = a;
   if (!staged_input && !is_device_ptr(a)) { // host matrix: only the rows of these blocks travel
-    float* const d = static_cast<float*>(scratch(3, (size_t)handle->m * handle->k * sizeof(float)));
+    float* const d = static_cast<float*>(scratch(SLOT_A, (size_t)handle->m * handle->k * sizeof(float)));
     if (nullptr == d) return -1;
     const int r0 = mb0 * handle->bm, nr = LIBXSMM_MIN(mbn * handle->bm, handle->m - r0);
     const int e = ta ? copy_window(d, const_cast<float*>(a), handle->m, 0, handle->k, r0, nr, true) : copy_window(d, const_cast<float*>(a), handle->k, r0, nr, 0, handle->k, true);
@@ -366,7 +364,7 @@ int spmdm_compute(const libxsmm_spmdm_handle* handle, char transb, const float* 
   const int tb = is_trans(transb) ? 1 : 0, tc = is_trans(transc) ? 1 : 0;
   const float* db = b;
   if (!staged_b && !is_device_ptr(b)) {
-    float* const d = static_cast<float*>(scratch(4, (size_t)handle->k * handle->n * sizeof(float)));
+    float* const d = static_cast<float*>(scratch(SLOT_B, (size_t)handle->k * handle->n * sizeof(float)));
     if (nullptr == d) return -1;
     // columns [n0, n1) of B (all k): B[k][n] resp. rows [n0, n1) of B[n][k]
     const int e = tb ? copy_window(d, const_cast<float*>(b), handle->k, n0, n1 - n0, 0, handle->k, true) : copy_window(d, const_cast<float*>(b), handle->n, 0, handle->k, n0, n1 - n0, true);
@@ -377,7 +375,7 @@ int spmdm_compute(const libxsmm_spmdm_handle* handle, char transb, const float* 
   float* dc = c;
   const bool c_host = !is_device_ptr(c);
   if (c_host) { // the tile travels in (beta != 0) and out; nothing else of C is touched
-    dc = static_cast<float*>(scratch(5, (size_t)handle->m * handle->n * sizeof(float)));
+    dc = static_cast<float*>(scratch(SLOT_C, (size_t)handle->m * handle->n * sizeof(float)));
     if (nullptr == dc) return -1;
     if (0.f != beta) {
       const int e = tc ? copy_window(dc, c, handle->m, n0, n1 - n0, m0, m1 - m0, true) : copy_window(dc, c, handle->n, m0, m1 - m0, n0, n1 - n0, true);
@@ -416,7 +414,7 @@ int create_blocks_bf16(const libxsmm_spmdm_handle* handle, char transa, const li
   bool ok = true;
   const size_t r0 = (size_t)mb0 * handle->bm, nr = (size_t)LIBXSMM_MIN(mbn * handle->bm, handle->m - (int)r0);
   const bool rows_contiguous = !is_trans(transa);
-  const float* const da = widen_bf16(a, (size_t)handle->m * handle->k, 6, 3, &ok, rows_contiguous ? r0 * handle->k : 0, rows_contiguous ? nr * handle->k : 0);
+  const float* const da = widen_bf16(a, (size_t)handle->m * handle->k, SLOT_BLOCK, SLOT_A, &ok, rows_contiguous ? r0 * handle->k : 0, rows_contiguous ? nr * handle->k : 0);
   if (!ok) return -1;
   return spmdm_create(handle, transa, da, mb0, mbn, true, !is_device_ptr(a));
 }
@@ -426,7 +424,7 @@ int compute_tiles_bf16(const libxsmm_spmdm_handle* handle, char transb, const li
 { // only the columns [n0, n1) of B are widened where they are one piece (a transposed B: rows of B^T; else: all of B)
   bool ok = true;
   const bool piece = is_trans(transb);
-  const float* const db = widen_bf16(b, (size_t)handle->k * handle->n, 6, 4, &ok, piece ? (size_t)n0 * handle->k : 0, piece ? (size_t)(n1 - n0) * handle->k : 0);
+  const float* const db = widen_bf16(b, (size_t)handle->k * handle->n, SLOT_BLOCK, SLOT_B, &ok, piece ? (size_t)n0 * handle->k : 0, piece ? (size_t)(n1 - n0) * handle->k : 0);
   if (!ok) return -1;
   return spmdm_compute(handle, transb, db, true, transc, beta, c, mb0, mbn, n0, n1, !is_device_ptr(b));
 }
@@ -501,7 +499,7 @@ void spmdm_flush_record()
     const float* wide = nullptr;
     if (p.bf16 && 1 < p.rects.size()) { // several rectangles: B is widened once
       bool ok = true;
-      wide = widen_bf16(static_cast<const libxsmm_bfloat16*>(p.src), (size_t)h->k * h->n, 6, 4, &ok);
+      wide = widen_bf16(static_cast<const libxsmm_bfloat16*>(p.src), (size_t)h->k * h->n, SLOT_BLOCK, SLOT_B, &ok);
       if (!ok) { p.rects.clear(); p.kind = 0; return; }
     }
     for (const SpmdmRect& r : p.rects) {
@@ -592,7 +590,7 @@ LIBXSMM_API int libxsmm_amd_spmdm_createSparseSlice_bfloat16_all(const libxsmm_s
   if (nullptr == handle || nullptr == a || nullptr == libxsmm_output_csr_a || nullptr == handle->base_ptr_scratch_A) return EXIT_FAILURE;
   if (!device_ready()) { fail_no_device("libxsmm_amd_spmdm_createSparseSlice_bfloat16_all"); return EXIT_FAILURE; }
   bool ok = true;
-  const float* const da = widen_bf16(a, (size_t)handle->m * handle->k, 6, 3, &ok);
+  const float* const da = widen_bf16(a, (size_t)handle->m * handle->k, SLOT_BLOCK, SLOT_A, &ok);
   if (!ok) return EXIT_FAILURE;
   return 0 == spmdm_create(handle, transa, da, 0, handle->mb, true, !is_device_ptr(a)) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
@@ -604,7 +602,7 @@ LIBXSMM_API int libxsmm_amd_spmdm_compute_bfloat16_all(const libxsmm_spmdm_handl
   if (nullptr == handle || nullptr == a_sparse || nullptr == b || nullptr == c || nullptr == beta) return EXIT_FAILURE;
   if (!device_ready()) { fail_no_device("libxsmm_amd_spmdm_compute_bfloat16_all"); return EXIT_FAILURE; }
   bool ok = true;
-  const float* const db = widen_bf16(b, (size_t)handle->k * handle->n, 6, 4, &ok);
+  const float* const db = widen_bf16(b, (size_t)handle->k * handle->n, SLOT_BLOCK, SLOT_B, &ok);
   if (!ok) return EXIT_FAILURE;
   return 0 == spmdm_compute(handle, transb, db, true, transc, (float)(*beta), c, 0, handle->mb, 0, handle->n, !is_device_ptr(b)) ? EXIT_SUCCESS : EXIT_FAILURE;
 }

@@ -74,49 +74,23 @@ int xsmm::run_rect(size_t ti, size_t to, bool ta, bool tb, int beta0, long long 
 {
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  const hipStream_t st = (hipStream_t)stream;
   const size_t m0 = rect[0], n0 = rect[2];
   const int m = (int)(rect[1] - rect[0]), n = (int)(rect[3] - rect[2]);
   // what the rectangle reads and writes: rows m0 ... of op(A), columns n0 ... of op(B)
-  const char* pa = static_cast<const char*>(a) + (ta ? m0 * (size_t)lda : m0) * ti;
-  const char* pb = static_cast<const char*>(b) + (tb ? n0 : n0 * (size_t)ldb) * ti;
+  const char* const pa = static_cast<const char*>(a) + (ta ? m0 * (size_t)lda : m0) * ti;
+  const char* const pb = static_cast<const char*>(b) + (tb ? n0 : n0 * (size_t)ldb) * ti;
   char* const pc = static_cast<char*>(c) + (n0 * (size_t)ldc + m0) * to;
-  const int ka = pointer_kind(pa), kb = pointer_kind(pb), kc = pointer_kind(pc);
-  const bool visible = (0 != ((ka | kb | kc) & 2));
-  bool staged = false;
-  if (0 == (ka & 1)) { // the span of A the task reads, as it lies
-    const size_t nbytes = (ta ? ((size_t)(m - 1) * lda + k) : ((size_t)(k - 1) * lda + m)) * ti;
-    void* const p = scratch(3, nbytes);
-    if (nullptr == p || 0 != h2d(p, pa, nbytes)) return EXIT_FAILURE;
-    pa = static_cast<const char*>(p); staged = true;
-  }
-  if (0 == (kb & 1)) {
-    const size_t nbytes = (tb ? ((size_t)(k - 1) * ldb + n) : ((size_t)(n - 1) * ldb + k)) * ti;
-    void* const p = scratch(4, nbytes);
-    if (nullptr == p || 0 != h2d(p, pb, nbytes)) return EXIT_FAILURE;
-    pb = static_cast<const char*>(p); staged = true;
-  }
-  char* dc = pc;
-  long long dldc = ldc;
-  const size_t tight = (size_t)m * to; // bytes of a column of the rectangle
-  if (0 == (kc & 1)) { // a tight image of the rectangle: only the rectangle travels, what lies between m and ldc keeps its bytes
-    dc = static_cast<char*>(scratch(5, tight * n));
-    if (nullptr == dc) return EXIT_FAILURE;
-    dldc = m;
-    if (0 == beta0 && hipSuccess != hipMemcpy2DAsync(dc, tight, pc, (size_t)ldc * to, tight, (size_t)n, hipMemcpyHostToDevice, st)) {
-      (void)hipGetLastError(); return EXIT_FAILURE;
-    }
-  }
+  Staged s;
+  // the spans of A and B the task reads, as they lie; a tight image of the rectangle of C: only the rectangle travels, what lies
+  // between m and ldc keeps its bytes
+  const Operand* const oa = s.in(pa, (ta ? ((size_t)(m - 1) * lda + k) : ((size_t)(k - 1) * lda + m)) * ti, SLOT_A);
+  const Operand* const ob = s.in(pb, (tb ? ((size_t)(k - 1) * ldb + n) : ((size_t)(n - 1) * ldb + k)) * ti, SLOT_B);
+  const Operand* const oc = s.out2d(pc, (size_t)m * to, (size_t)n, (size_t)ldc * to, SLOT_C, 0 == beta0);
+  if (!s.place()) return EXIT_FAILURE;
   const char* name = "";
-  const int e = launch(stream, pa, pb, dc, dldc, m, n, &name);
-  note_launch(name);
-  if (0 != e) { fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e); return EXIT_FAILURE; }
-  if (dc != pc) {
-    if (hipSuccess != hipMemcpy2DAsync(pc, (size_t)ldc * to, dc, tight, tight, (size_t)n, hipMemcpyDeviceToHost, st)) { (void)hipGetLastError(); return EXIT_FAILURE; }
-    return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  }
-  if (staged || visible) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
+  const int e = launch(stream, oa->dev, ob->dev, oc->dev, nullptr != oc->host ? m : ldc, m, n, &name);
+  if (!launched(name, e)) return EXIT_FAILURE;
+  return s.finish(WAIT_OPERANDS, { oc }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 namespace {

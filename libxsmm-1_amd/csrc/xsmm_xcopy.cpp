@@ -44,13 +44,7 @@ int unit_of(unsigned ts, uintptr_t address_bits)
 uintptr_t bits(const void* p) { return reinterpret_cast<uintptr_t>(p); }
 bool mult16(const void* p, long long pitch_bytes) { return 0 == ((bits(p) | (uintptr_t)pitch_bytes) & 15); }
 
-int report(int e, const char* name)
-{
-  note_launch(name);
-  if (0 == e) return EXIT_SUCCESS;
-  fprintf(stderr, "LIBXSMM-AMD ERROR: kernel launch failed (%s, hip error %d)\n", name, e);
-  return EXIT_FAILURE;
-}
+int report(int e, const char* name) { return launched(name, e) ? EXIT_SUCCESS : EXIT_FAILURE; }
 
 // ---- operands the GPU reaches ------------------------------------------------------------------------------------------
 int dev_copy(void* out, const void* in, long long rowbytes, long long ncols, long long pin, long long pout, void* stream)
@@ -109,39 +103,20 @@ int run2d(int op, void* out, const void* in, unsigned ts, int m, int n, long lon
 {
   if (!device_ready()) { fail_no_device(what); return EXIT_FAILURE; }
   void* const stream = device().stream; // (seals an open burst of deferred calls: everything stays in call order)
-  const hipStream_t st = (hipStream_t)stream;
   const int rows_out = (OP_TRANS == op ? n : m), cols_out = (OP_TRANS == op ? m : n); // as the destination is stored
-  const int kind_out = pointer_kind(out), kind_in = (nullptr != in && OP_ITRANS != op) ? pointer_kind(in) : 1;
-  const bool stage_out = (0 == (kind_out & 1)), stage_in = (0 == (kind_in & 1));
-  const bool visible = (0 != (kind_out & 2)) || (0 != (kind_in & 2));
   const size_t tight = (size_t)rows_out * ts; // bytes of a column of the destination
-  void* dout = out; const void* din = (OP_ITRANS == op ? nullptr : in);
-  long long dldo = ldo;
-  if (stage_in) { // the span of the input as it lies
-    const size_t nbytes = ((size_t)(n - 1) * ldi + m) * ts;
-    void* const p = scratch(0, nbytes);
-    if (nullptr == p || 0 != h2d(p, in, nbytes)) return EXIT_FAILURE;
-    din = p;
-  }
-  if (stage_out) { // a tight image of the destination; only the valid part travels (back), the padding keeps its bytes
-    dout = scratch(1, tight * cols_out);
-    if (nullptr == dout) return EXIT_FAILURE;
-    dldo = rows_out;
-    if (OP_ITRANS == op && hipSuccess != hipMemcpy2DAsync(dout, tight, out, (size_t)ldo * ts, tight, cols_out, hipMemcpyHostToDevice, st)) {
-      (void)hipGetLastError(); return EXIT_FAILURE;
-    }
-  }
+  Staged s;
+  // the span of the input as it lies; a tight image of the destination: only the valid part travels (back), the padding keeps its bytes
+  const Operand* const oi = (OP_ITRANS != op ? s.in(in, ((size_t)(n - 1) * ldi + m) * ts, SLOT_IN0) : nullptr);
+  const Operand* const oo = s.out2d(out, tight, cols_out, (size_t)ldo * ts, SLOT_IN1, OP_ITRANS == op);
+  if (!s.place()) return EXIT_FAILURE;
+  const long long dldo = (nullptr != oo->host ? rows_out : ldo);
   int rc;
-  if (OP_COPY == op) rc = dev_copy(dout, din, (long long)m * ts, n, ldi * ts, dldo * ts, stream);
-  else if (OP_TRANS == op) rc = dev_otrans(dout, din, ts, m, n, ldi, dldo, stream);
-  else rc = dev_itrans(dout, ts, n, dldo, stream);
+  if (OP_COPY == op) rc = dev_copy(oo->dev, dev_of(oi), (long long)m * ts, n, ldi * ts, dldo * ts, stream);
+  else if (OP_TRANS == op) rc = dev_otrans(oo->dev, oi->dev, ts, m, n, ldi, dldo, stream);
+  else rc = dev_itrans(oo->dev, ts, n, dldo, stream);
   if (EXIT_SUCCESS != rc) return rc;
-  if (stage_out) {
-    if (hipSuccess != hipMemcpy2DAsync(out, (size_t)ldo * ts, dout, tight, tight, cols_out, hipMemcpyDeviceToHost, st)) { (void)hipGetLastError(); return EXIT_FAILURE; }
-    return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  }
-  if (stage_in || visible) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
+  return s.finish(WAIT_OPERANDS, { oo }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 // ---- the reference's entry points ------------------------------------------------------------------------------------
@@ -246,8 +221,8 @@ int batch_move(int op, void* out, const void* in, unsigned ts, libxsmm_blasint m
 
   const void* din = in; void* dout = out;
   uintptr_t align = 0;
-  bool sync = false, staged_out = false, uploaded = false;
-  size_t out_bytes = 0;
+  bool uploaded = false;
+  Staged s; const Operand *oi = nullptr, *oo = nullptr;
   if (0 != ptrs) { // arrays of pointers: host arrays travel through the upload ring; the items must be memory the GPU reaches
     const size_t nbytes = (size_t)batch * sizeof(void*);
     const void* const arr[2] = { out, in };
@@ -265,23 +240,11 @@ int batch_move(int op, void* out, const void* in, unsigned ts, libxsmm_blasint m
     dout = const_cast<void*>(dev[0]); din = inplace ? dev[0] : dev[1];
   }
   else { // strided: pageable host memory through device copies of the spans as they lie (what is between the items travels along)
-    align = bits(out) | bits(in);
-    const int kind_out = pointer_kind(out), kind_in = (nullptr != in ? pointer_kind(in) : 1);
-    sync = (0 != (kind_out & 2)) || (0 != (kind_in & 2));
-    if (0 == (kind_out & 1)) {
-      out_bytes = ((size_t)(batch - 1) * sout + ext_out) * ts;
-      dout = scratch(1, out_bytes);
-      if (nullptr == dout || 0 != h2d(dout, out, out_bytes)) return EXIT_FAILURE;
-      staged_out = true;
-      if (inplace) din = dout;
-    }
-    if (nullptr != in && !inplace && 0 == (kind_in & 1)) {
-      const size_t nbytes = ((size_t)(batch - 1) * sin + ext_in) * ts;
-      void* const p = scratch(0, nbytes);
-      if (nullptr == p || 0 != h2d(p, in, nbytes)) return EXIT_FAILURE;
-      din = p; sync = true;
-    }
-    align = (align & 15) | bits(dout) | bits(din);
+    oo = s.out(out, ((size_t)(batch - 1) * sout + ext_out) * ts, SLOT_IN1, true);
+    if (!inplace) oi = s.in(in, ((size_t)(batch - 1) * sin + ext_in) * ts, SLOT_IN0);
+    if (!s.place()) return EXIT_FAILURE;
+    dout = oo->dev; din = inplace ? dout : dev_of(oi);
+    align = ((bits(out) | bits(in)) & 15) | bits(dout) | bits(din);
   }
 
   int rc;
@@ -302,9 +265,7 @@ int batch_move(int op, void* out, const void* in, unsigned ts, libxsmm_blasint m
   }
   if (uploaded) index_upload_commit();
   if (EXIT_SUCCESS != rc) return rc;
-  if (staged_out) return 0 == d2h(out, dout, out_bytes) ? EXIT_SUCCESS : EXIT_FAILURE;
-  if (sync) return 0 == stream_sync() ? EXIT_SUCCESS : EXIT_FAILURE;
-  return EXIT_SUCCESS;
+  return s.finish(WAIT_OPERANDS, { oo }) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
 } // namespace

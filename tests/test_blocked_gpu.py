@@ -60,6 +60,18 @@ def _blocked_product(xs, torch, geom, a, b, c, mfma, skip=None, jit=None):
         L.libxsmm_amd_set_mfma(old)
 
 
+class _Pinned:
+    """a copy of x in memory of libxsmm_malloc: the GPU works on it in place, the CPU reads it"""
+    def __init__(self, L, x):
+        self.L, self.p = L, L.libxsmm_malloc(x.nbytes)
+        assert self.p
+        self.v = np.ctypeslib.as_array(C.cast(self.p, C.POINTER(C.c_ubyte)), shape=(x.nbytes,)).view(x.dtype)
+        self.v[...] = x
+
+    def free(self):
+        self.L.libxsmm_free(self.p)
+
+
 def _plain_chain(orc, geom, a, b, c):
     """one ascending-k fma chain per element of C over the whole K, from C: the oracle's SMM on the plain matrices"""
     m, n, k = geom[:3]
@@ -141,6 +153,25 @@ def test_blocked_gemm_host_operands_and_invalid_blocks(xs, orc, torch_gpu):
     L.libxsmm_blocked_gemm_omp(h, xs.dptr(ba), xs.dptr(bb), xs.dptr(bc), 1)
     assert xs.last_kernel() == "smm_f64_generic_w32"  # (8 items: the generic kernel)
     assert 0 == L.libxsmm_blocked_gemm_copyout_c(h, xs.dptr(bc), None, xs.dptr(out))
+    # the same calls on memory of libxsmm_malloc: in place, one launch each, every result read on return with no synchronisation of ours
+    pin = {name: _Pinned(L, x) for name, x in (("a", a), ("b", b), ("c", c), ("ba", 0 * a), ("bb", 0 * b), ("bc", 0 * c), ("out", 0 * c))}
+    try:
+        def one_launch(name, f, *args):
+            before = L.libxsmm_amd_launch_count()
+            rc = f(h, *args)
+            assert rc in (0, None) and L.libxsmm_amd_launch_count() == before + 1 and xs.last_kernel() == name, (name, rc, xs.last_kernel())
+        one_launch("bgemm_copy", L.libxsmm_blocked_gemm_copyin_a, xs.dptr(pin["a"].p), None, xs.dptr(pin["ba"].p))
+        assert np.array_equal(_bits(pin["ba"].v), _bits(ba))
+        one_launch("bgemm_copy", L.libxsmm_blocked_gemm_copyin_b, xs.dptr(pin["b"].p), None, xs.dptr(pin["bb"].p))
+        assert np.array_equal(_bits(pin["bb"].v), _bits(bb))
+        one_launch("bgemm_copy", L.libxsmm_blocked_gemm_copyin_c, xs.dptr(pin["c"].p), None, xs.dptr(pin["bc"].p))
+        one_launch("smm_f64_generic_w32", L.libxsmm_blocked_gemm_omp, xs.dptr(pin["ba"].p), xs.dptr(pin["bb"].p), xs.dptr(pin["bc"].p), 1)
+        assert np.array_equal(_bits(pin["bc"].v), _bits(bc))
+        one_launch("bgemm_copy", L.libxsmm_blocked_gemm_copyout_c, xs.dptr(pin["bc"].p), None, xs.dptr(pin["out"].p))
+        assert np.array_equal(_bits(pin["out"].v), _bits(out))
+    finally:
+        for x in pin.values():
+            x.free()
     L.libxsmm_blocked_gemm_handle_destroy(h)
     expect = a.reshape(k, m).T @ b.reshape(n, k).T
     assert np.max(np.abs(out.reshape(n, m).T - expect)) <= 1e-12 * np.max(np.abs(expect)) * 4
@@ -180,6 +211,21 @@ def test_blocked_permutations(xs, orc, torch_gpu, dtype, geom):
             hdst = np.empty_like(src)
             assert 0 == f(h, xs.dptr(src), None, xs.dptr(hdst))
             assert np.array_equal(hdst, ref), which
+            # device source, pageable destination alone: read on return, a sentinel straight after the span keeps its bytes
+            tail = np.full(count + 4, -7.0, dtype=dtype)
+            before = L.libxsmm_amd_launch_count()
+            assert 0 == f(h, xs.dptr(dsrc), None, xs.dptr(tail))
+            assert np.array_equal(tail[:count], ref) and np.all(tail[count:] == -7.0), which
+            assert L.libxsmm_amd_launch_count() == before + 1 and xs.last_kernel() == "bgemm_" + which
+            # memory of libxsmm_malloc on both sides: in place, complete on return
+            psrc, pdst = _Pinned(L, src), _Pinned(L, np.full_like(src, -7.0))
+            try:
+                before = L.libxsmm_amd_launch_count()
+                assert 0 == f(h, xs.dptr(psrc.p), None, xs.dptr(pdst.p))
+                assert np.array_equal(pdst.v, ref), which
+                assert L.libxsmm_amd_launch_count() == before + 1 and xs.last_kernel() == "bgemm_" + which
+            finally:
+                psrc.free(); pdst.free()
         assert 0 != L.libxsmm_blocked_gemm_transpose_b(None, xs.dptr(src), None, xs.dptr(hdst))
     finally:
         L.libxsmm_blocked_gemm_handle_destroy(h)

@@ -222,6 +222,12 @@ def test_items_with_gaps(xs, torch_gpu, line_bytes, lines, ld, stride, batch):
         got = run_hash_batch(xs, torch, d.data_ptr() + 2, line_bytes, lines, ld, stride, batch, 5)
         assert np.array_equal(got, want)
     assert xs.last_kernel() == ("hash_items" if line_bytes * lines <= hc.ITEM_MAX else "hash_units")
+    # the items in pageable memory, the results on the device: the span is uploaded and nobody has to wait
+    out, launches = Results(torch, batch), L.libxsmm_amd_launch_count()
+    assert 0 == L.libxsmm_amd_hash_batch(out.ptr, copies[1][2:].ctypes.data, line_bytes, lines, ld, stride, batch, 5)
+    assert L.libxsmm_amd_launch_count() - launches == (1 if line_bytes * lines <= hc.ITEM_MAX else batch)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.take(), want)
     flags, first = Results(torch, batch), Results(torch, 1, torch.int64)
     assert 0 == L.libxsmm_amd_memcmp_batch(flags.ptr, first.ptr, devs[0].data_ptr() + 2, devs[1].data_ptr() + 2, line_bytes, lines, ld, ld, stride, stride, batch)
     torch.cuda.synchronize()

@@ -34,12 +34,40 @@ def run(xs, torch, case, mode, loop=None, fn=None, shift=0):
         a, b, c, sa, sb, sc = pc.call_args(case, {name: x.ctypes.data for name, x in after.items()})
         loop.pack_loop(fn, a, b, c, sa, sb, sc, npacks)
         return before, after
+    if mode == "batch_pinned":  # every operand in memory of libxsmm_malloc: in place, one launch, complete on return (no wait of ours)
+        pin = {name: L.libxsmm_aligned_malloc(x.nbytes, 256) for name, x in before.items()}
+        assert all(pin.values())
+        try:
+            views = {name: np.ctypeslib.as_array(C.cast(pin[name], C.POINTER(C.c_ubyte)), shape=(x.nbytes,)).view(x.dtype) for name, x in before.items()}
+            for name, x in before.items():
+                views[name][...] = x
+            a, b, c, sa, sb, sc = pc.call_args(case, pin)
+            n0 = L.libxsmm_amd_launch_count()
+            assert 0 == L.libxsmm_amd_packed_execute_batch(fn, a, b, c, npacks)
+            after = {name: v.copy() for name, v in views.items()}
+            assert L.libxsmm_amd_launch_count() - n0 == 1
+            return before, after
+        finally:
+            for p in pin.values():
+                L.libxsmm_free(p)
     hold = {name: torch.zeros(len(x) + shift, dtype=torch.from_numpy(x).dtype, device="cuda") for name, x in before.items()}
     dev = {name: t[shift:] for name, t in hold.items()}
     for name, x in before.items():
         dev[name].copy_(torch.from_numpy(x))
     a, b, c, sa, sb, sc = pc.call_args(case, {name: t.data_ptr() for name, t in dev.items()})
     torch.cuda.synchronize()
+    if mode == "batch_written_host":  # the written operand alone in pageable memory: one launch, complete on return (no wait of ours)
+        host = before[case.written].copy()
+        ptrs = {name: t.data_ptr() for name, t in dev.items()}
+        ptrs[case.written] = host.ctypes.data
+        a, b, c, sa, sb, sc = pc.call_args(case, ptrs)
+        n0 = L.libxsmm_amd_launch_count()
+        assert 0 == L.libxsmm_amd_packed_execute_batch(fn, a, b, c, npacks)
+        on_return = host.copy()
+        assert L.libxsmm_amd_launch_count() - n0 == 1
+        after = {name: t.cpu().numpy() for name, t in dev.items()}
+        after[case.written] = on_return
+        return before, after
     if mode == "batch":
         assert 0 == L.libxsmm_amd_packed_execute_batch(fn, a, b, c, npacks)
     elif mode == "loop":
@@ -120,9 +148,15 @@ def test_one_answer_from_every_entry_and_form(xs, orc, torch_gpu, loop, monkeypa
     small = Case(kind, dtype, m, n, k, nmat=9 * v, seed=11, layout=case.layout, **kw)
     small.ops = {name: np.ascontiguousarray(x[:9 * v]) for name, x in case.ops.items()}  # the first nine packs of the same matrices
     want = verify(xs, orc, small, *run(xs, torch_gpu, small, "batch", fn=fn))
+    name = xs.last_kernel()
     before, after = run(xs, torch_gpu, small, "host", loop, fn)
     assert np.array_equal(small.result(xs, after[small.written]), want)
     assert small.untouched(xs, before, after) is None
+    for mode in ("batch_written_host", "batch_pinned"):
+        before, after = run(xs, torch_gpu, small, mode, fn=fn)
+        assert xs.last_kernel() == name, (mode, xs.last_kernel())
+        assert np.array_equal(small.result(xs, after[small.written]), want), mode
+        assert small.untouched(xs, before, after) is None
     assert np.array_equal(want, ref[:9 * v])  # (the same matrices: the batch size does not change a result either)
 
 

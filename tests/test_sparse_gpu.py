@@ -70,6 +70,33 @@ def test_fsspmdm_synthetic(xs, orc, torch_gpu, dtype, beta, unique):
             assert np.array_equal(ref[5], Cin[5]) if unique == "palette" else np.all(ref[5] == 0.0)
         else:
             assert np.array_equal(out[5], Cin[5])
+    # the batch entry on every residency of B and C: the same kernel, one launch, the device's bits; C in host memory (pageable, or
+    # pinned memory of libxsmm_malloc, processed in place) is read on return with no synchronisation of ours
+    name = xs.last_kernel()
+    nbytes = B.nbytes
+    pin = [L.libxsmm_malloc(nbytes) for _ in range(2)]
+    assert all(pin) and B.nbytes == Cin.nbytes
+    pinned = [np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_ubyte)), shape=(nbytes,)).view(dtype).reshape(B.shape) for p in pin]
+    try:
+        for kind_b, kind_c in (("pageable", "pageable"), ("device", "pageable"), ("pageable", "device"), ("pinned", "pinned"), ("device", "pinned")):
+            hB = B.copy()
+            pinned[0][...] = B
+            pb = {"pageable": xs.dptr(hB), "device": xs.dptr(dB), "pinned": xs.dptr(pin[0])}[kind_b]
+            hC, dC = Cin.copy(), torch.from_numpy(Cin).cuda()
+            pinned[1][...] = Cin
+            pc = {"pageable": xs.dptr(hC), "device": xs.dptr(dC), "pinned": xs.dptr(pin[1])}[kind_c]
+            before = L.libxsmm_amd_launch_count()
+            assert 0 == execb(hd, pb, pc, panels)
+            got = hC.copy() if kind_c == "pageable" else (pinned[1].copy() if kind_c == "pinned" else None)
+            assert L.libxsmm_amd_launch_count() == before + 1 and xs.last_kernel() == name, (kind_b, kind_c, xs.last_kernel())
+            if got is None:
+                torch.cuda.synchronize()
+                got = dC.cpu().numpy()
+            assert np.array_equal(got.view(np.uint8), out.view(np.uint8)), (kind_b, kind_c)
+            assert np.array_equal(hB, B) and np.array_equal(pinned[0], B)
+    finally:
+        for p in pin:
+            L.libxsmm_free(p)
     destroy(hd)
 
 

@@ -149,6 +149,24 @@ def test_patterns(xs, orc, torch_gpu, kind):
             want = case.flat_c(ref, fill, guard=0)
             want[case.owned_gap(0)] = 0
             assert ho.same_values(hc, want), (case.id(), "host") + ho.differences(hc, want)
+            if kind in st.PLAIN:  # the same product on memory of libxsmm_malloc: in place, one launch, C read on return with no wait of ours
+                L = xs.lib()
+                src = (hs, hd, np.ascontiguousarray(case.flat_c(c, fill, guard=0)))
+                pin = [L.libxsmm_malloc(f.nbytes) for f in src]
+                assert all(pin)
+                try:
+                    views = [np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_ubyte)), shape=(f.nbytes,)).view(f.dtype) for p, f in zip(pin, src)]
+                    for v, f in zip(views, src):
+                        v[...] = f.reshape(-1)
+                    before = L.libxsmm_amd_launch_count()
+                    assert 0 == built.single(pin[0], pin[1], pin[2])
+                    got = views[2].copy()
+                    assert L.libxsmm_amd_launch_count() == before + 1 and xs.last_kernel() == built.kernel_name()
+                    assert np.array_equal(ho.raw(got), ho.raw(hc.reshape(-1))), (case.id(), "pinned")
+                    assert np.array_equal(ho.raw(views[1]), ho.raw(hd.reshape(-1)))
+                finally:
+                    for p in pin:
+                        L.libxsmm_free(p)
         finally:
             built.close()
 

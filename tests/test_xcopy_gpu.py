@@ -232,7 +232,9 @@ def test_stack_calls(xs, torch_gpu, case):
         di = xc.Device(torch_gpu, src)
         # strided, device memory
         do = xc.Device(torch_gpu, dst)
+        launches = xs.lib().libxsmm_amd_launch_count()
         assert 0 == strided(do.ptr(), None if op == "zero" else di.ptr(), ts, m, n, src.ld, dst.ld, src.stride, dst.stride, batch)
+        on_device = (xs.last_kernel(), xs.lib().libxsmm_amd_launch_count() - launches)
         assert xc.first_difference(do.get(), want) is None, ("strided", op, case, xs.last_kernel())
         # pointer arrays in host memory and in device memory
         do = xc.Device(torch_gpu, dst)
@@ -249,6 +251,18 @@ def test_stack_calls(xs, torch_gpu, case):
             host = xc.Stack(ts, rows, cols, ld=dst.ld, stride=dst.stride, batch=batch, off=dst.off, fill=False)
             assert 0 == strided(host.ptr(), None if op == "zero" else src.ptr(), ts, m, n, src.ld, dst.ld, src.stride, dst.stride, batch)
             assert xc.first_difference(host.host, want) is None, ("strided, host", op, case)
+            # strided, memory of libxsmm_malloc on both sides: processed in place by the same launch, complete on return (read with no
+            # synchronisation of ours)
+            pin, pout = xc.Pinned(xs, src), xc.Pinned(xs, dst)
+            try:
+                launches = xs.lib().libxsmm_amd_launch_count()
+                assert 0 == strided(pout.ptr(), None if op == "zero" else pin.ptr(), ts, m, n, src.ld, dst.ld, src.stride, dst.stride, batch)
+                got = pout.get()
+                assert (xs.last_kernel(), xs.lib().libxsmm_amd_launch_count() - launches) == on_device
+                assert xc.first_difference(got, want) is None, ("strided, pinned", op, case)
+                assert xc.first_difference(pin.get(), src.host) is None
+            finally:
+                pin.free(); pout.free()
     if m == n:  # in place: every item onto itself
         want = xc.expected_itrans(src)
         da = xc.Device(torch_gpu, src)
