@@ -54,6 +54,11 @@
  *     as an implicit GEMM, the frame around them and a physical rim as without the variable. The bits do not change; a call is
  *     then up to two launches and one more per 65535 pixel tiles. LIBXSMM_AMD_CONV_TILE=64|128 forces the tile of FWD and of this
  *     path. Unset, or in any other case, BWD is what it was (the default for now: DESIGN.md 8n).
+ *   - The environment variable LIBXSMM_AMD_CONV_UPD=mfma (read per call) sends UPD, both its GEMM form and its per-image form, to
+ *     the matrix cores unless they are switched off (LIBXSMM_AMD_MFMA, libxsmm_amd_set_mfma): a GEMM over 64 x 64 tiles of
+ *     dfilter with the unsplit reduction over (image, oj, oi), still one launch per call (libxsmm_amd_last_kernel:
+ *     conv_upd_mfma_gemm, conv_upd_mfma_image). The bits do not change and LIBXSMM_AMD_CONV_TILE is not read. Unset, UPD is
+ *     what it was (the default for now: DESIGN.md 8n).
  *
  * Threads. Work is N * K/ofmblock items (FWD), N * C/ifmblock (BWD), C/ifmblock * K/ofmblock (UPD), split as in the other layers:
  * logical thread ltid computes [ltid * chunk, min((ltid + 1) * chunk, work)), chunk = ceil(work / desc.threads). No chain crosses a

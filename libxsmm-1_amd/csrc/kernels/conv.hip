@@ -25,6 +25,8 @@
 // term out for some of its elements (BWD) and because only C * K * R * S chains are independent (UPD): DESIGN.md 8n says what
 // that costs. Index arithmetic is per thread (a few divisions), the loops add strides. With LIBXSMM_AMD_CONV_BWD=mfma and
 // strides of 1 the pixels of dinput that have all their terms go to conv_bwd_mfma.hip and conv_bwd keeps the frame around them.
+// With LIBXSMM_AMD_CONV_UPD=mfma both forms of UPD go to conv_upd_mfma.hip, a GEMM D(k, (c, kj, ki)) over (img, oj, oi) that feeds
+// the matrix cores through a pipeline of its own (a zero-fed step is exactly a term of UPD, so nothing stays behind here).
 //
 // Bounds. Every address is formed from indices that were compared against their extents first; an element outside its tile's
 // valid part, outside the share [w0, w1) or (FWD, logical padding) outside the input plane reads element 0 of its tensor and
@@ -33,6 +35,8 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdlib>
+#include <cstring>
 
 #include "../xsmm_dnn_internal.hpp"
 #include "tile_gemm.cuh"
@@ -343,6 +347,8 @@ int launch_conv_bwd(const ConvArgs& args, void* stream, const char** name)
 
 int launch_conv_upd(const ConvArgs& g, void* stream, const char** name)
 {
+  const char* const e = getenv("LIBXSMM_AMD_CONV_UPD"); // read per call, as LIBXSMM_AMD_CONV_BWD
+  if (nullptr != e && 0 == strcmp(e, "mfma") && 0 != libxsmm_amd_get_mfma()) return launch_conv_upd_mfma(g, stream, name); // conv_upd_mfma.hip
   *name = (0 != g.per_image ? "conv_upd_image" : "conv_upd_gemm");
   dim3 grid;
   if (!item_grid((long long)g.R * g.S * g.ifmblock * g.ofmblock, (long long)g.w1 - g.w0, &grid)) return (int)hipErrorInvalidValue;

@@ -1,6 +1,7 @@
 // xsmm_dnn_conv.cpp -- the convolution layer (include/libxsmm_dnn_convolution.h): handle, layouts, scratch and tensor binding as
 // in the reference's generic path, and libxsmm_dnn_execute_st as one launch of kernels/conv.hip per call (FWD: one per slab of
-// 65535 pixel tiles; BWD with LIBXSMM_AMD_CONV_BWD=mfma: conv_bwd for the frame, then kernels/conv_bwd_mfma.hip slab by slab).
+// 65535 pixel tiles; BWD with LIBXSMM_AMD_CONV_BWD=mfma: conv_bwd for the frame, then kernels/conv_bwd_mfma.hip slab by slab;
+// UPD with LIBXSMM_AMD_CONV_UPD=mfma: one launch of kernels/conv_upd_mfma.hip instead).
 //
 // Reference: src/libxsmm_dnn.c (create :191-308, layouts :363-997, trans_reg_filter :1571-1604, binding :1607-1717, scratch
 // :1720-2097, execute :2100-2235, the helpers :2238-2391), src/libxsmm_dnn_handle.c:61-167 (the scratch sizes of the generic path),
@@ -292,6 +293,7 @@ LIBXSMM_API libxsmm_dnn_err_t libxsmm_dnn_execute_st(libxsmm_dnn_layer* h, libxs
   else { // upd template :91-92
     const bool physical = (0 == g.logical);
     g.per_image = ((1 == d.R && 1 == d.S && physical) || (1 == d.u && 1 == d.v)) ? 0 : 1;
+    // (launch_conv_upd reads LIBXSMM_AMD_CONV_UPD: either way one launch over the share, and the caller's scratch stays unread)
     e = launch_conv_upd(g, stream, &name);
   }
   if (!launched(name, e)) return LIBXSMM_DNN_ERR_GENERAL;

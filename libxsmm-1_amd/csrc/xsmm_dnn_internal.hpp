@@ -72,6 +72,9 @@ int launch_conv_trans_filter(const ConvArgs& args, void* stream, const char** na
 // strides are 1, the matrix cores are not switched off and the rectangle is not empty (else false, args untouched); its launch
 bool conv_bwd_full_rect(ConvArgs* args);
 int launch_conv_bwd_mfma(const ConvArgs& args, void* stream, const char** name);
+// UPD on the matrix cores (kernels/conv_upd_mfma.hip): both forms in one launch; launch_conv_upd goes there if LIBXSMM_AMD_CONV_UPD=mfma
+// asks for the path and the matrix cores are not switched off
+int launch_conv_upd_mfma(const ConvArgs& args, void* stream, const char** name);
 
 // RNN cell layer (xsmm_dnn_rnn.cpp, kernels/rnn.hip): one launch computes, for the rows [n0, n1) of the minibatch and all K outputs,
 // G accumulator sets (gates) of one step -- or, with nz > 1, of nz steps whose operands lie zx / zo elements apart

@@ -11,7 +11,11 @@ Every case is warmed up twice, then timed event to event in five windows of as m
 median window is reported with the spread. FLOP: 2 * N * K * C * R * S * ofh * ofw per pass. No gate.
 At stride 1 BWD is timed twice: as it is by default (conv_bwd alone) and with LIBXSMM_AMD_CONV_BWD=mfma (kernels/conv_bwd_mfma.hip
 for the pixels that have all their terms, conv_bwd for the frame); --bwd keeps those two rows of the stride-1 shapes only.
-Usage: tools/bench_conv.py [--out FILE] [--quick] [--bwd]"""
+--upd keeps UPD of all four shapes, timed with LIBXSMM_AMD_CONV_UPD unset (conv_upd_gemm / conv_upd_image) and set to mfma
+(kernels/conv_upd_mfma.hip) in windows that alternate, and states beside the set row the derived floor of the matrix-core path:
+32 cycles per term and wave (one v_mfma_f32_32x32x2_f32 advances a 32 x 32 tile by two terms in 64 cycles), N * ofh * ofw terms,
+once per round of 64 x 64 tiles over the compute units, at the device's clock.
+Usage: tools/bench_conv.py [--out FILE] [--quick] [--bwd | --upd]"""
 import argparse
 import importlib
 import os
@@ -24,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 N = 64
+CLOCK_MHZ = 2400  # the peak engine clock of the MI355X, for the derived floor of --upd (the clock under load is not read)
 SHAPES = [dict(C=64, K=256, H=56, W=56, R=1, S=1, u=1, pad=0), dict(C=128, K=128, H=28, W=28, R=3, S=3, u=1, pad=1),
           dict(C=128, K=128, H=56, W=56, R=3, S=3, u=2, pad=1), dict(C=3, K=64, H=224, W=224, R=7, S=7, u=2, pad=3)]
 FWD, BWD, UPD, ALL = 0, 1, 2, 4
@@ -47,6 +52,27 @@ def timed(torch, call):
     return windows[2], windows[0], windows[4]
 
 
+def timed_pair(torch, call, env, value):
+    """timed() of call with the variable env unset and set to value (read per call), the windows of the two alternating"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    windows, reps = ([], []), []
+    for v in (None, value):
+        os.environ.pop(env, None) if v is None else os.environ.__setitem__(env, v)
+        call(); call(); torch.cuda.synchronize()
+        e0.record(); call(); e1.record(); torch.cuda.synchronize()
+        reps.append(int(min(50, max(3, 200.0 / 5 / max(e0.elapsed_time(e1), 1e-3)))))
+    for _ in range(5):
+        for i, v in enumerate((None, value)):
+            os.environ.pop(env, None) if v is None else os.environ.__setitem__(env, v)
+            e0.record()
+            for _ in range(reps[i]):
+                call()
+            e1.record(); torch.cuda.synchronize()
+            windows[i].append(e0.elapsed_time(e1) / reps[i])
+    os.environ.pop(env, None)
+    return [(sorted(w)[2], min(w), max(w)) for w in windows]
+
+
 def fmt(t):
     return "not measured" if t is None else "%9.4f ms (%.4f ... %.4f)" % t
 
@@ -56,6 +82,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_bench.txt"))
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--bwd", action="store_true")
+    ap.add_argument("--upd", action="store_true")
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -89,8 +116,21 @@ def main():
         gemm = {FWD: lambda: xs.xgemm_omp(xs.F32, "N", "N", m, n, k, 1.0, ga, m, gb, k, 0.0, gc, m),
                 BWD: lambda: xs.xgemm_omp(xs.F32, "T", "N", k, n, m, 1.0, ga, m, gb, m, 0.0, gc, k),
                 UPD: lambda: xs.xgemm_omp(xs.F32, "N", "T", m, k, n, 1.0, gb, m, gc, k, 0.0, ga, m)}
+        if args.upd:
+            props = torch.cuda.get_device_properties(0)
+            tiles = -(-K // 64) * -(-(C_ * R * S) // 64)
+            floor = -(-tiles // props.multi_processor_count) * N * ofh * ofw * 32 / (CLOCK_MHZ * 1e6) * 1e3  # ms
+            theirs, ceiling = timed(torch, ref[UPD]), timed(torch, gemm[UPD])
+            for path, mine in zip(("unset", "mfma"), timed_pair(torch, lambda: xs.conv_execute(handle, UPD), "LIBXSMM_AMD_CONV_UPD", "mfma")):
+                os.environ.pop("LIBXSMM_AMD_CONV_UPD", None) if "unset" == path else os.environ.__setitem__("LIBXSMM_AMD_CONV_UPD", path)
+                xs.conv_execute(handle, UPD)
+                os.environ.pop("LIBXSMM_AMD_CONV_UPD", None)
+                lines.append("C=%-3d K=%-3d %3dx%-3d %dx%d/%d upd %-5s %-19s %s  %6.2f TFLOP/s | floor %s | torch %s | sgemm_omp %dx%dx%d %s"
+                             % (C_, K, H, W, R, S, u, path, xs.last_kernel(), fmt(mine), flop / mine[0] * 1e-9,
+                                "%.4f ms = %4.1f %% (%d tiles at %d MHz)" % (floor, 100 * floor / mine[0], tiles, CLOCK_MHZ) if "mfma" == path else "-",
+                                fmt(theirs), m, k, n, fmt(ceiling)))
         rows = [(FWD, "fwd", None), (BWD, "bwd", None)] + ([(BWD, "bwd", "mfma")] if 1 == u else []) + [(UPD, "upd", None)]
-        for kind, name, bwd_path in (r for r in rows if BWD == r[0] or not args.bwd):
+        for kind, name, bwd_path in (r for r in rows if (BWD == r[0] or not args.bwd) and not args.upd):
             if bwd_path:  # (read per call)
                 os.environ["LIBXSMM_AMD_CONV_BWD"] = bwd_path
             mine = timed(torch, lambda: xs.conv_execute(handle, kind))
